@@ -15,14 +15,21 @@ bracketed by barrier + device sync.  `python bench.py --gpus N` without RANK in 
 environment starts the N ranks itself (a child `python -m torch.distributed.run`, before this
 process touches torch or HIP) and relays rank 0's JSON line.
 
-Rank 0 prints one JSON line (contract in the task description) with two extra objects:
+Rank 0 prints one JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...) with
   roofline      dominant kernel (force_sym_kernel<double,...>; the line names the one that ran)
                 algorithmic fp64 flop (14 per ordered pair) / its HIP-event
                 duration measured inside this run, against the fp64 vector peak of MI355X.
+A plain run does only that: set-up, warm-up, the K timed steps, the line.  `--full` adds what takes
+work of its own:
+  energy_drift_rel_timed_region  total energy before / after the timed steps.
+  collective    (runs with a communicator) what the per-step all-reduce is and costs on the node.
   cpu_baseline  the CPU oracle (oracle/, "port" of the reference's algorithm, OpenMP over all
                 host cores) timed on a bounded sample of the same workload (rank 0, N=1 only),
                 the energy drift of the GPU run against the oracle's over those same steps, and
                 the reference's own materialised-tensor formulation timed per SURVEY.md 8(d).
+  gpu_rows, modes  this engine at the cpu_baseline sizes, and every precision mode at N = 65 536.
+`--dump-outputs DIR` writes the state the timed steps leave (positions, velocities, accelerations) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared array for array.
 """
 import argparse
 import json
@@ -39,6 +46,7 @@ FP64_VECTOR_PEAK_TFLOPS = 78.6     # MI355X fp64 vector (= fp64 matrix) peak, AM
 FP32_VECTOR_PEAK_TFLOPS = 157.3    # /opt/skills/guides/MI355X_MICROARCH.md
 FLOP_PER_PAIR_2D = 14              # 5*D + 4, SURVEY.md section 8d
 SPINUP_EVALS = 40                  # untimed force evaluations (incl. warm-up steps) before the timed region
+DUMP_BYTES = 60 * 10 ** 6          # --dump-outputs: at most this much in all (larger runs: a seeded sample of rows)
 
 
 def parse():
@@ -50,13 +58,21 @@ def parse():
                     help="particles (default: BASELINE config 2); use --particles under torch.distributed.run, whose\n"
                          "own parser takes --n for an abbreviation of --nnodes")
     ap.add_argument("--mode", default="float64")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample length")
+    ap.add_argument("--full", action="store_true",
+                    help="also the energy drift, the collective report, the CPU baseline, gpu_rows and modes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the timed steps leave as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline, gpu_rows and modes")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample length (--full)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch plumbing only: rendezvous (gloo when there is no GPU), barrier, one JSON line; no HIP work")
     ap.add_argument("--ref-sizes", default="1024,4096,8192",
-                    help="sizes at which the reference's materialised torch formulation is timed (SURVEY.md 8d); '' = skip")
-    return ap.parse_args()
+                    help="sizes at which the reference's materialised torch formulation is timed (SURVEY.md 8d, --full); "
+                         "'' = skip")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_launch(args):
@@ -292,6 +308,31 @@ def pmc_traffic(kernel_name):
     return None, "kernel not in profiles/pmc_latest.json"
 
 
+def read_outputs(sim):
+    """The arrays a caller of the timed path receives after its last step: fp64 state stays fp64, every other dtype
+    becomes fp32.  Above DUMP_BYTES in all, the same seeded sample of rows of every array.  Called on every rank."""
+    import numpy as np
+    import torch
+    arrays = {}
+    for name in ("positions", "velocities", "accelerations"):
+        t = getattr(sim, name).detach().cpu()
+        arrays[name] = (t if t.dtype == torch.float64 else t.float()).numpy()
+    n = sim.num_stars
+    row_bytes = sum(a.nbytes for a in arrays.values()) // max(n, 1)
+    keep = DUMP_BYTES // max(row_bytes, 1)
+    if n > keep:
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+    return arrays
+
+
+def write_outputs(arrays, out_dir):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -356,7 +397,7 @@ def main():
     # short warm-ups are topped up with force evaluations that leave the state untouched (untimed)
     spinup = max(0, SPINUP_EVALS - args.warmup) if n >= 16384 else 0
     sim.spin_up(spinup)
-    e0 = sim.get_total_energy()
+    e0 = sim.get_total_energy() if args.full else None
     sim.kernel_time()                 # reset the event accumulators
     barrier()
     t0 = time.perf_counter()
@@ -370,9 +411,12 @@ def main():
         elapsed = float(t.item())
     kern_ms, launches = sim.kernel_time()
     kernel_name = sim.force_kernel_name()
-    e1 = sim.get_total_energy()
+    outputs = read_outputs(sim) if args.dump_outputs else None
+    if outputs is not None and rank == 0:
+        write_outputs(outputs, args.dump_outputs)
+    e1 = sim.get_total_energy() if args.full else None
     collective = None
-    if world > 1 or runtime.force_comm():
+    if args.full and (world > 1 or runtime.force_comm()):
         collective = collective_report(sim, runtime, nb, dist, world, n, pos, vel, mass, mode, dev)
 
     if rank == 0:
@@ -404,9 +448,6 @@ def main():
                        "parallelism": runtime.partition_label(world)},
             "collective": collective,
             "pair_interactions_per_s": float(n) * n * args.steps / elapsed,
-            "energy_drift_rel_timed_region": (e1 - e0) / abs(e0),
-            "energy_drift_note": "raw drift over the timed steps (after warm-up), for the record only; the metric's "
-                                 "rel-err against the oracle is cpu_baseline.energy_drift_vs_oracle",
             "roofline": {
                 "bound": "mfma",
                 "bound_note": "compute-bound: priced against the dense fp64 (fp32 modes: fp32) MFMA peak, which on MI355X "
@@ -424,7 +465,11 @@ def main():
                                 "sums order-deterministic, DESIGN.md section 2",
             },
         }
-        if world == 1 and not args.no_cpu_baseline and is64:
+        if args.full:
+            out["energy_drift_rel_timed_region"] = (e1 - e0) / abs(e0)
+            out["energy_drift_note"] = ("raw drift over the timed steps (after warm-up), for the record only; the metric's "
+                                        "rel-err against the oracle is cpu_baseline.energy_drift_vs_oracle")
+        if args.full and world == 1 and not args.no_cpu_baseline and is64:
             def gpu_drift(k):
                 s2 = nb.GalaxySimulation(pos.double().to(dev), vel.double().to(dev), mass.double().to(dev),
                                          precision_mode=mode, G=0.001, softening=0.1, dt=0.01, device=dev)

@@ -269,3 +269,15 @@ def test_bench_starts_its_own_ranks():
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
     assert json.loads(lines[0]) == {"dry_run": True, "n_gpus": 2, "gpus_arg": 2}
+
+
+def test_bench_options():
+    """The plain line's extras live behind --full, --dump-outputs DIR writes the final state, --steps sets the timed
+    steps and must be at least 1."""
+    import subprocess
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
+                         timeout=120)
+    assert res.returncode == 0 and "--full" in res.stdout and "--dump-outputs" in res.stdout, res.stdout
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--dry-run"],
+                         capture_output=True, text=True, timeout=120)
+    assert res.returncode == 2 and "--steps" in res.stderr, res.stderr[-2000:]

@@ -785,6 +785,35 @@ def test_split_sweeps_match_whole_sweeps(nb, monkeypatch, split):
         assert relerr(s32.accelerations.numpy(), r32) < 2e-6, mode
 
 
+def test_bench_plain_line_and_dumped_outputs(nb, tmp_path):
+    """`bench.py` without --full prints the headline line only; --dump-outputs writes the state its timed steps left,
+    which equals the same seeded galaxy stepped warm-up + timed steps by the engine directly."""
+    import subprocess
+    import sys
+    from nbody_cosmological_simulation_amd import galaxy
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir = tmp_path / "outputs"
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--n", "4096", "--steps", "7",
+                          "--warmup", "3", "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+    line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    assert line["steps"] == 7 and line["dtype"] == "f64" and line["ms_per_step"] > 0
+    assert not {"cpu_baseline", "gpu_rows", "modes", "energy_drift_rel_timed_region"} & set(line)
+    pos, vel, mass = galaxy.create_disk_galaxy(4096, seed=42, device="cpu")
+    dev = torch.device("cuda", 0)
+    sim = nb.GalaxySimulation(pos.to(dev), vel.to(dev), mass.to(dev), precision_mode=nb.PrecisionMode.FLOAT64, G=0.001,
+                              softening=0.1, dt=0.01, device=dev)
+    sim.run(3)
+    sim.run(7)
+    for name in ("positions", "velocities", "accelerations"):
+        got = np.load(out_dir / f"{name}.npy")
+        assert got.dtype == np.float64 and got.shape == (4096, 2), (name, got.dtype, got.shape)
+        assert relerr(got, getattr(sim, name).cpu().numpy()) < 1e-13, name
+    sim.close()
+
+
 def test_c_client_of_the_cabi(nb, tmp_path):
     """A plain-C program (no Python, no torch) drives the engine through include/nbody_amd.h; its
     numbers must equal the Python mirror's on the same inputs and agree with the oracle."""
