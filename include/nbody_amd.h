@@ -281,7 +281,8 @@ int nb_comm_p2p_allreduce(void *host_inout, int64_t count, int32_t dtype, double
 /* The work plan of the pair-symmetric kernels for one rank, computed WITHOUT a device (pure host code; what
  * nb_set_state uploads).  For tests of the partition: the union over ranks must cover every tile pair once.
  * info[0..11] = enabled, targets per lane R, tile size, padded tiles, padded particles, work items, row slots,
- * column-slab entries, source tiles per item, pipeline chunks, column-slab MiB, row-slab MiB.
+ * column-slab entries, source tiles per item, pipeline chunks, column-slab MiB, row-slab MiB; info[12] = step pieces
+ * of the row-split work items (0: classic items), info[13] = targets per thread of the one-sided fp64 kernel.
  * work: items x 8 int32 {tile_i, jt_begin, jt_end, slot, slot_stride, col_ord, s_begin, s_count};
  * row_slot0 / row_nslots / col_upto: one int32 per padded tile; chunk_work / chunk_tile: chunks + 1 offsets
  * (work-item ranges / tile boundaries; chunk_tile is the same on every rank).  Any output may be NULL.

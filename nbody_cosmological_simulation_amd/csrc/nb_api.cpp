@@ -607,10 +607,12 @@ int nb_plan_debug(const nb_config *cfg, int32_t is_f64, int32_t multi, int32_t c
     in.multi = multi != 0;
     in.cus = cus > 0 ? cus : 256;
     SymPlanHost h;
-    nb_plan_sym(in, nb_read_knobs(), h);
+    const NbKnobs knobs = nb_read_knobs();
+    nb_plan_sym(in, knobs, h);
     const int nchunks = h.enabled ? 1 : 0;      // (the pipelined multi-GPU step of round 2 is gone: always one chunk)
     const int32_t vals[16] = {h.enabled, h.r, h.tile_b, h.tiles, h.np, (int32_t)h.work.size(), h.nslots, h.ncol, h.cl, nchunks,
-                              (int32_t)(h.col_bytes >> 20), (int32_t)(h.row_bytes >> 20), 0, 0, 0, 0};
+                              (int32_t)(h.col_bytes >> 20), (int32_t)(h.row_bytes >> 20), h.rowsplit,
+                              onesided_r(in.n, knobs), 0, 0};
     memcpy(info, vals, sizeof vals);
     if (!h.enabled) return NB_OK;
     if (work) {

@@ -201,6 +201,8 @@ int comm_allreduce_max_u32(nb_sim *s, unsigned int *buf);
 int p2p_check(nb_sim *s);
 
 // ---- nb_step.cpp ---------------------------------------------------------------------------------------------------
+// targets per thread of the one-sided fp64 kernel (FLOAT64 pairs; the cast / half-typed variants always take 2)
+int onesided_r(int n, const NbKnobs &knobs);
 void compute_geometry(nb_sim *s);
 // one evaluation of simulation.py:74-118; optionally followed by the closing half kick (:141)
 // defer_kick: the caller will apply the closing half kick itself (fused into the next step's

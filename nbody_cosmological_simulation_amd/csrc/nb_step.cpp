@@ -30,6 +30,16 @@ struct NbTuning {
 };
 static const NbTuning g_tune{};
 
+// targets per thread of the one-sided fp64 kernel.  Small systems are parallelism-bound, not
+// throughput-bound: R = 1 doubles the workgroups (N = 1024: 27.8 -> 17.6 us per step, N = 4096:
+// 32.5 -> 22.6 us)
+int onesided_r(int n, const NbKnobs &knobs)
+{
+    if (knobs.r_onesided == 1 || knobs.r_onesided == 2 || knobs.r_onesided == 4)   // NB_R tuning knob
+        return knobs.r_onesided;
+    return (n <= g_tune.onesided_r1_max_n) ? 1 : 2;
+}
+
 void compute_geometry(nb_sim *s)
 {
     const int n = s->cfg.n;
@@ -37,12 +47,7 @@ void compute_geometry(nb_sim *s)
     g.n = n;
     g.j_begin = (int)((int64_t)s->cfg.rank * n / s->cfg.nranks);
     g.j_end = (int)((int64_t)(s->cfg.rank + 1) * n / s->cfg.nranks);
-    // targets per thread of the one-sided fp64 kernel.  Small systems are parallelism-bound, not
-    // throughput-bound: R = 1 doubles the workgroups (N = 1024: 27.8 -> 17.6 us per step, N = 4096:
-    // 32.5 -> 22.6 us)
-    g.r = (n <= g_tune.onesided_r1_max_n) ? 1 : 2;
-    if (s->knobs.r_onesided == 1 || s->knobs.r_onesided == 2 || s->knobs.r_onesided == 4)   // NB_R tuning knob
-        g.r = s->knobs.r_onesided;
+    g.r = onesided_r(n, s->knobs);
     const int njr = std::max(g.j_end - g.j_begin, 1);
     const int itiles = (n + NB_BLOCK * g.r - 1) / (NB_BLOCK * g.r);
     const int max_chunks = (njr + NB_TJ - 1) / NB_TJ;

@@ -1,0 +1,174 @@
+"""Work-plan shapes of the force path, read through the device-free C-ABI entry nb_plan_debug.
+
+One place for two things:
+  plan() / shape_key()  what the planner (nb_plan.cpp) hands a rank: targets per lane R, source tiles per item cl,
+                        row-split items, the step pieces its sweeps are cut into;
+  COVERED               the shape keys tests/test_gpu_plan_shapes.py runs against the oracle on the GPU.
+tests/test_distributed_cpu.py sweeps the planner over sizes, modes and rank counts and fails on a CPU machine when
+it emits a key that is not in COVERED: a retune that creates a new shape needs a GPU case for it.
+"""
+import ctypes as C
+
+import numpy as np
+
+# mode codes of nb_config.mode (include/nbody_amd.h)
+FLOAT64, FLOAT32, BFLOAT16, FLOAT16, INT8 = 0, 1, 2, 3, 4
+
+_INFO = ["enabled", "r", "tile_b", "tiles", "np", "nwork", "nslots", "ncol", "cl", "nchunks", "col_mib", "row_mib",
+         "rowsplit", "onesided_r"]
+
+
+def plan(n, dim, rank=0, world=1, is_f64=True, mode=FLOAT64, cus=256, work=True, no_comm=False):
+    """The plan of one rank (the knobs NB_SYM* are read from the environment, as nb_create does)."""
+    from nbody_cosmological_simulation_amd import _native as N
+    L = N.lib()
+    cfg = N.NbConfig(n=n, dim=dim, mode=mode, levels=0, G=1e-3, softening_sq=0.01, dt=0.01, device=0, rank=rank,
+                     nranks=world, flags=N.NB_FLAG_NO_COMM if no_comm else 0)
+    info = (C.c_int32 * 16)()
+    N.check(L.nb_plan_debug(C.byref(cfg), int(is_f64), 0, cus, info, None, 0, None, None, None, None, None))
+    out = dict(zip(_INFO, list(info)))
+    if out["enabled"] and work:
+        w = np.zeros((out["nwork"], 8), np.int32)
+        N.check(L.nb_plan_debug(C.byref(cfg), int(is_f64), 0, cus, info, w.ctypes.data_as(C.POINTER(C.c_int32)),
+                                out["nwork"], None, None, None, None, None))
+        out["work"] = w
+    return out
+
+
+def pieces(p):
+    """Sorted distinct numbers of step pieces the sweeps of a plan are cut into (work items that share target tile
+    and source range are the pieces of one sweep)."""
+    _, counts = np.unique(p["work"][:, :3], axis=0, return_counts=True)
+    return tuple(int(c) for c in np.unique(counts))
+
+
+def shape_key(p, dim, is_f64):
+    """(R, dim, fp64, row-split, piece counts, cl == 1) of an enabled plan."""
+    return (p["r"], dim, bool(is_f64), p["rowsplit"] > 0, pieces(p), p["cl"] == 1)
+
+
+def onesided_key(p, dim, is_f64):
+    """Key of a plan that leaves the force to the one-sided kernels (fp32 state: always two targets per thread)."""
+    return ("onesided", p["onesided_r"] if is_f64 else 2, dim, bool(is_f64))
+
+
+def rank_keys(n, dim, world=1, is_f64=True, mode=FLOAT64, cus=256, no_comm=False):
+    """Shape keys of every rank of a plan (no_comm: comm-less shards, as the GPU cases run them with NB_SYM=2)."""
+    keys = set()
+    for r in range(world):
+        p = plan(n, dim, r, world, is_f64=is_f64, mode=mode, cus=cus, no_comm=no_comm)
+        keys.add(shape_key(p, dim, is_f64) if p["enabled"] else onesided_key(p, dim, is_f64))
+    return keys
+
+
+def K(r, dim, f64, rowsplit, pieces_, cl1=True):
+    return (r, dim, f64, rowsplit, tuple(pieces_), cl1)
+
+
+# The GPU cases of tests/test_gpu_plan_shapes.py: (id, N, dim, state dtype, mode, ranks, knobs, shape keys of the
+# ranks' plans, force kernel).  Ranks > 1 run as comm-less shards (NB_SYM=2) whose partial forces are summed.
+# Sizes are ragged (N % tile != 0, tiles % 4 != 0) where the shape allows it.
+F64, F32 = "float64", "float32"
+SYM64, SYM32, ONE64, ONE32 = "force_sym_kernel<double", "force_sym_kernel<float", "force_f64_kernel", "force_f32_kernel"
+CASES = [
+    # ---- default plans, fp64, 2-D
+    ("f64-d2-tiny-p8", 700, 2, F64, "float64", 1, {}, {K(1, 2, True, False, (8,))}, SYM64),
+    ("f64-d2-tiny-p4", 1000, 2, F64, "float64", 1, {}, {K(1, 2, True, False, (4,))}, SYM64),
+    ("f64-d2-tiny-p2", 1400, 2, F64, "float64", 1, {}, {K(1, 2, True, False, (2,))}, SYM64),
+    ("f64-d2-tiny-p1", 2000, 2, F64, "float64", 1, {}, {K(1, 2, True, False, (1,))}, SYM64),
+    ("f64-d2-onesided-r1", 4000, 2, F64, "float64", 1, {"NB_NO_SMALLN": "1"}, {("onesided", 1, 2, True)}, ONE64),
+    ("f64-d2-rowsplit2", 5200, 2, F64, "float64", 1, {}, {K(4, 2, True, True, (2,))}, SYM64),
+    ("f64-d2-rowsplit3", 6300, 2, F64, "float64", 1, {}, {K(4, 2, True, True, (3,))}, SYM64),
+    ("f64-d2-rowsplit1", 12000, 2, F64, "float64", 1, {}, {K(4, 2, True, True, (1,))}, SYM64),
+    ("f64-d2-classic6", 5800, 2, F64, "float64", 1, {}, {K(4, 2, True, False, (6,))}, SYM64),
+    ("f64-d2-classic6-b", 9900, 2, F64, "float64", 1, {}, {K(4, 2, True, False, (6,))}, SYM64),
+    ("f64-d2-classic2", 15400, 2, F64, "float64", 1, {}, {K(4, 2, True, False, (2,))}, SYM64),
+    ("f64-d2-whole", 22400, 2, F64, "float64", 1, {}, {K(4, 2, True, False, (1,))}, SYM64),
+    ("f64-d2-tail8", 23800, 2, F64, "float64", 1, {}, {K(4, 2, True, False, (1, 8))}, SYM64),
+    ("f64-d2-tail4", 32300, 2, F64, "float64", 1, {}, {K(4, 2, True, False, (1, 4))}, SYM64),
+    ("f64-d2-cl3-tail4", 56700, 2, F64, "float64", 1, {}, {K(4, 2, True, False, (1, 4), False)}, SYM64),
+    ("f64-d2-cl2", 52700, 2, F64, "float64", 1, {}, {K(4, 2, True, False, (1,), False)}, SYM64),
+    ("f64-d2-onesided-r2-1m", 1 << 20, 2, F64, "float64", 1, {}, {("onesided", 2, 2, True)}, ONE64),
+    # ---- default plans, fp64, 3-D
+    ("f64-d3-onesided-r1", 5000, 3, F64, "float64", 1, {"NB_NO_SMALLN": "1"}, {("onesided", 1, 3, True)}, ONE64),
+    ("f64-d3-classic3", 8200, 3, F64, "float64", 1, {}, {K(4, 3, True, False, (3,))}, SYM64),
+    ("f64-d3-classic4", 8900, 3, F64, "float64", 1, {}, {K(4, 3, True, False, (4,))}, SYM64),
+    ("f64-d3-classic5", 9700, 3, F64, "float64", 1, {}, {K(4, 3, True, False, (5,))}, SYM64),
+    ("f64-d3-classic5-b", 13000, 3, F64, "float64", 1, {}, {K(4, 3, True, False, (5,))}, SYM64),
+    ("f64-d3-classic2", 10100, 3, F64, "float64", 1, {}, {K(4, 3, True, False, (2,))}, SYM64),
+    ("f64-d3-whole", 22400, 3, F64, "float64", 1, {}, {K(4, 3, True, False, (1,))}, SYM64),
+    ("f64-d3-tail8", 23800, 3, F64, "float64", 1, {}, {K(4, 3, True, False, (1, 8))}, SYM64),
+    ("f64-d3-tail4", 32300, 3, F64, "float64", 1, {}, {K(4, 3, True, False, (1, 4))}, SYM64),
+    ("f64-d3-cl2-tail4", 46600, 3, F64, "float64", 1, {}, {K(4, 3, True, False, (1, 4), False)}, SYM64),
+    ("f64-d3-cl2", 52700, 3, F64, "float64", 1, {}, {K(4, 3, True, False, (1,), False)}, SYM64),
+    ("f64-d3-onesided-r2", 535841, 3, F64, "float64", 1, {}, {("onesided", 2, 3, True)}, ONE64),
+    # ---- default plans, fp32 family
+    ("f32-d2-onesided", 1000, 2, F32, "float32", 1, {"NB_SYM": "0", "NB_NO_SMALLN": "1"}, {("onesided", 2, 2, False)}, ONE32),
+    ("f32-d3-onesided", 2000, 3, F32, "float16", 1, {"NB_NO_SMALLN": "1"}, {("onesided", 2, 3, False)}, ONE32),
+    ("f32-d2-p8", 1100, 2, F32, "float32", 1, {"NB_NO_SMALLN": "1"}, {K(2, 2, False, False, (8,))}, SYM32),
+    ("f32-d2-p4", 1500, 2, F32, "float16", 1, {"NB_NO_SMALLN": "1"}, {K(2, 2, False, False, (4,))}, SYM32),
+    ("f32-d2-p2", 4000, 2, F32, "int8_sim", 1, {}, {K(2, 2, False, False, (2,))}, SYM32),
+    ("f32-d2-whole", 7100, 2, F32, "float32", 1, {}, {K(2, 2, False, False, (1,))}, SYM32),
+    ("f32-d2-tail2", 11500, 2, F32, "float32", 1, {}, {K(2, 2, False, False, (1, 2))}, SYM32),
+    ("f32-d3-p2", 4100, 3, F32, "float32", 1, {}, {K(2, 3, False, False, (2,))}, SYM32),
+    ("f32-d3-whole", 7100, 3, F32, "float16", 1, {}, {K(2, 3, False, False, (1,))}, SYM32),
+    ("f32-d3-tail2", 11500, 3, F32, "float32", 1, {}, {K(2, 3, False, False, (1, 2))}, SYM32),
+    ("f32-d2-r4-p4", 21100, 2, F32, "float32", 1, {}, {K(4, 2, False, False, (4,))}, SYM32),
+    ("f32-d2-r4-whole", 22400, 2, F32, "float32", 1, {}, {K(4, 2, False, False, (1,))}, SYM32),
+    ("f32-d2-r4-tail8", 23800, 2, F32, "float32", 1, {}, {K(4, 2, False, False, (1, 8))}, SYM32),
+    ("f32-d2-r4-tail4", 32300, 2, F32, "float32", 1, {}, {K(4, 2, False, False, (1, 4))}, SYM32),
+    ("f32-d2-r4-cl2-tail4", 65600, 2, F32, "float32", 1, {}, {K(4, 2, False, False, (1, 4), False)}, SYM32),
+    ("f32-d2-r4-cl2", 71500, 2, F32, "float32", 1, {}, {K(4, 2, False, False, (1,), False)}, SYM32),
+    ("f32-d3-r4-p4", 21100, 3, F32, "float32", 1, {}, {K(4, 3, False, False, (4,))}, SYM32),
+    ("f32-d3-r4-whole", 22400, 3, F32, "float32", 1, {}, {K(4, 3, False, False, (1,))}, SYM32),
+    ("f32-d3-r4-tail8", 23800, 3, F32, "float32", 1, {}, {K(4, 3, False, False, (1, 8))}, SYM32),
+    ("f32-d3-r4-tail4", 32300, 3, F32, "float32", 1, {}, {K(4, 3, False, False, (1, 4))}, SYM32),
+    ("f32-d3-r4-cl2-tail4", 65600, 3, F32, "float32", 1, {}, {K(4, 3, False, False, (1, 4), False)}, SYM32),
+    ("f32-d3-r4-cl2", 71500, 3, F32, "float32", 1, {}, {K(4, 3, False, False, (1,), False)}, SYM32),
+    ("f32-d3-onesided-1m", 1 << 20, 3, F32, "float32", 1, {}, {("onesided", 2, 3, False)}, ONE32),
+    # ---- multi-rank plans (comm-less shards, NB_SYM=2)
+    ("f64-d2-9000-p2", 9000, 2, F64, "float64", 2, {}, {K(4, 2, True, True, (3,))}, SYM64),
+    ("f64-d2-9000-p3", 9000, 2, F64, "float64", 3, {}, {K(4, 2, True, True, (2,))}, SYM64),
+    ("f64-d2-9000-p4", 9000, 2, F64, "float64", 4, {}, {K(4, 2, True, False, (5,)), K(4, 2, True, True, (3,))}, SYM64),
+    ("f64-d2-9000-p8", 9000, 2, F64, "float64", 8,
+     {}, {K(4, 2, True, False, (6,)), K(4, 2, True, True, (2,)), K(4, 2, True, True, (3,)), K(4, 2, True, True, (4,))}, SYM64),
+    ("f64-d2-16384-p4", 16384, 2, F64, "float64", 4, {}, {K(4, 2, True, True, (2,))}, SYM64),
+    ("f64-d2-16384-p8", 16384, 2, F64, "float64", 8, {}, {K(4, 2, True, False, (6,))}, SYM64),
+    ("f64-d2-19800-p2", 19800, 2, F64, "float64", 2, {}, {K(4, 2, True, False, (3,))}, SYM64),
+    ("f64-d3-8192-p8", 8192, 3, F64, "float64", 8, {}, {K(4, 3, True, False, (8,))}, SYM64),
+    ("f64-d3-8192-p2", 8192, 3, F64, "float64", 2, {}, {K(4, 3, True, False, (6,))}, SYM64),
+    ("f32-d3-4096-p3", 4096, 3, F32, "float32", 3, {}, {K(2, 3, False, False, (4,))}, SYM32),
+    ("f32-d3-4096-p8", 4096, 3, F32, "float32", 8, {}, {K(2, 3, False, False, (4,)), K(2, 3, False, False, (8,))}, SYM32),
+    ("f32-d2-21100-p2", 21100, 2, F32, "float32", 2, {}, {K(4, 2, False, False, (2,))}, SYM32),
+    ("f32-d2-22400-p3", 22400, 2, F32, "float32", 3, {}, {K(4, 2, False, False, (3,))}, SYM32),
+    ("f32-d2-28625-p8", 28625, 2, F32, "float32", 8, {}, {K(4, 2, False, False, (5,)), K(4, 2, False, False, (6,))}, SYM32),
+    ("f32-d3-21100-p2", 21100, 3, F32, "float32", 2, {}, {K(4, 3, False, False, (2,))}, SYM32),
+    ("f32-d3-22400-p3", 22400, 3, F32, "float32", 3, {}, {K(4, 3, False, False, (3,))}, SYM32),
+    ("f32-d3-28625-p8", 28625, 3, F32, "float32", 8, {}, {K(4, 3, False, False, (5,)), K(4, 3, False, False, (6,))}, SYM32),
+    # ---- shapes forced through the per-handle knobs
+    ("knob-r2-f64", 3000, 2, F64, "float64", 1, {"NB_SYM": "1", "NB_SYM_R": "2"}, {K(2, 2, True, False, (2,))}, SYM64),
+    ("knob-r1-f64", 3100, 2, F64, "float64", 1, {"NB_SYM": "1", "NB_SYM_R": "1"}, {K(1, 2, True, False, (1,))}, SYM64),
+    ("knob-r4-f32", 3000, 2, F32, "float32", 1, {"NB_SYM": "1", "NB_SYM_R": "4"}, {K(4, 2, False, False, (8,))}, SYM32),
+    ("knob-cl3", 20000, 2, F64, "float64", 1, {"NB_SYM_CL": "3"}, {K(4, 2, True, False, (4,), False)}, SYM64),
+    ("knob-cl8", 30000, 3, F64, "float64", 1, {"NB_SYM_CL": "8"}, {K(4, 3, True, False, (2,), False)}, SYM64),
+    ("knob-cl5-f32", 30000, 2, F32, "float32", 1, {"NB_SYM_CL": "5"}, {K(4, 2, False, False, (4,), False)}, SYM32),
+    ("knob-split3", 8000, 2, F64, "float64", 1, {"NB_SYM_SPLIT": "3"}, {K(4, 2, True, False, (3,))}, SYM64),
+    ("knob-split5", 9000, 3, F64, "float64", 1, {"NB_SYM_SPLIT": "5"}, {K(4, 3, True, False, (5,))}, SYM64),
+    ("knob-split7", 8000, 2, F32, "float32", 1, {"NB_SYM_SPLIT": "7"}, {K(2, 2, False, False, (7,))}, SYM32),
+    ("knob-split16", 8000, 2, F64, "float64", 1, {"NB_SYM_SPLIT": "16"}, {K(4, 2, True, False, (16,))}, SYM64),
+    ("knob-rowsplit1", 8000, 2, F64, "float64", 1, {"NB_SYM_ROWSPLIT": "1"}, {K(4, 2, True, True, (1,))}, SYM64),
+    ("knob-rowsplit2", 8000, 2, F64, "float64", 1, {"NB_SYM_ROWSPLIT": "2"}, {K(4, 2, True, True, (2,))}, SYM64),
+    ("knob-rowsplit3", 8000, 2, F64, "float64", 1, {"NB_SYM_ROWSPLIT": "3"}, {K(4, 2, True, True, (3,))}, SYM64),
+    ("knob-rowsplit4", 8000, 2, F64, "float64", 1, {"NB_SYM_ROWSPLIT": "4"}, {K(4, 2, True, True, (4,))}, SYM64),
+    ("knob-rowsplit8", 8000, 2, F64, "float64", 1, {"NB_SYM_ROWSPLIT": "8"}, {K(4, 2, True, True, (8,))}, SYM64),
+    ("knob-tail2", 23800, 2, F64, "float64", 1, {"NB_SYM_TAIL": "2"}, {K(4, 2, True, False, (1, 2))}, SYM64),
+    ("knob-tail4", 23800, 3, F64, "float64", 1, {"NB_SYM_TAIL": "4"}, {K(4, 3, True, False, (1, 4))}, SYM64),
+    ("knob-tail16", 23800, 2, F32, "float32", 1, {"NB_SYM_TAIL": "16"}, {K(4, 2, False, False, (1, 16))}, SYM32),
+    ("knob-onesided-r1", 12000, 2, F64, "float64", 1, {"NB_SYM": "0", "NB_R": "1"}, {("onesided", 1, 2, True)}, ONE64),
+    ("knob-onesided-r2", 5000, 3, F64, "float64", 1, {"NB_SYM": "0", "NB_R": "2", "NB_NO_SMALLN": "1"},
+     {("onesided", 2, 3, True)}, ONE64),
+    ("knob-onesided-r4", 12000, 2, F64, "float64", 1, {"NB_SYM": "0", "NB_R": "4"}, {("onesided", 4, 2, True)}, ONE64),
+]
+
+# the shape keys the GPU module compares with the oracle: one entry per key, from the case table above
+COVERED = sorted({k for case in CASES for k in case[7]}, key=str)

@@ -281,3 +281,23 @@ def test_bench_options():
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--dry-run"],
                          capture_output=True, text=True, timeout=120)
     assert res.returncode == 2 and "--steps" in res.stderr, res.stderr[-2000:]
+
+
+def test_every_planned_shape_has_a_gpu_case():
+    """Coverage contract of tests/test_gpu_plan_shapes.py: every work-plan shape the planner emits by default --
+    (R, dim, fp64, row-split, step pieces per sweep, cl == 1), or the one-sided kernel with its targets per thread --
+    over sizes 64 ... 1M, both dims, fp64 / fp32 / INT8 plans and every rank of 1, 2, 3, 4 and 8 ranks, must be one a
+    GPU case runs against the oracle (plan_shapes.COVERED).  A retune that creates a new shape fails here until a GPU
+    case covers it."""
+    import plan_shapes as S
+    sizes = sorted(set(np.geomspace(64, 1 << 20, 120).astype(int).tolist()) | {1 << k for k in range(6, 21)})
+    covered = set(S.COVERED)
+    missing = {}
+    for n in sizes:
+        for dim in (2, 3):
+            for is_f64, mode in ((True, S.FLOAT64), (False, S.FLOAT32), (False, S.INT8)):
+                for world in (1, 2, 3, 4, 8):
+                    for key in S.rank_keys(n, dim, world, is_f64, mode):
+                        if key not in covered:
+                            missing.setdefault(key, (n, world, mode))
+    assert not missing, "shapes without a GPU case (key: first N, ranks, mode): " + repr(missing)
