@@ -282,7 +282,9 @@ int nb_comm_p2p_allreduce(void *host_inout, int64_t count, int32_t dtype, double
  * nb_set_state uploads).  For tests of the partition: the union over ranks must cover every tile pair once.
  * info[0..11] = enabled, targets per lane R, tile size, padded tiles, padded particles, work items, row slots,
  * column-slab entries, source tiles per item, pipeline chunks, column-slab MiB, row-slab MiB; info[12] = step pieces
- * of the row-split work items (0: classic items), info[13] = targets per thread of the one-sided fp64 kernel.
+ * of the row-split work items (0: classic items), info[13] = targets per thread of the one-sided fp64 kernel,
+ * info[14] / info[15] = source chunks of the one-sided kernels (force, potential energy, generic) and sources per chunk
+ * for this rank's j-range.
  * work: items x 8 int32 {tile_i, jt_begin, jt_end, slot, slot_stride, col_ord, s_begin, s_count};
  * row_slot0 / row_nslots / col_upto: one int32 per padded tile; chunk_work / chunk_tile: chunks + 1 offsets
  * (work-item ranges / tile boundaries; chunk_tile is the same on every rank).  Any output may be NULL.
@@ -300,6 +302,10 @@ int nb_kernel_time(nb_sim *s, double *total_ms, int32_t *launches);
  * rocprofv3 rows by prefix): "force_sym_kernel<double", "force_sym_kernel<float", "force_f64_kernel",
  * "force_f32_kernel" or "none". */
 const char *nb_force_kernel_name(nb_sim *s);
+/* The potential-energy kernel variant the last nb_energy(..., potential) launched, with its template arguments, e.g.
+ * "potential_sym_kernel<double,2,4,f32t=0,uniform=0,mass=f32,rowsplit>" or "potential_kernel<double,3,pa_f32=1,hp=f16>";
+ * "none" before the first potential-energy evaluation. */
+const char *nb_pe_kernel_name(nb_sim *s);
 /* Block until all work queued on the handle's stream has finished. */
 int nb_synchronize(nb_sim *s);
 

@@ -609,10 +609,11 @@ int nb_plan_debug(const nb_config *cfg, int32_t is_f64, int32_t multi, int32_t c
     SymPlanHost h;
     const NbKnobs knobs = nb_read_knobs();
     nb_plan_sym(in, knobs, h);
+    const ForceGeom geom = onesided_geometry(*cfg, knobs);     // the one-sided kernels' source chunks of this rank
     const int nchunks = h.enabled ? 1 : 0;      // (the pipelined multi-GPU step of round 2 is gone: always one chunk)
     const int32_t vals[16] = {h.enabled, h.r, h.tile_b, h.tiles, h.np, (int32_t)h.work.size(), h.nslots, h.ncol, h.cl, nchunks,
                               (int32_t)(h.col_bytes >> 20), (int32_t)(h.row_bytes >> 20), h.rowsplit,
-                              onesided_r(in.n, knobs), 0, 0};
+                              onesided_r(in.n, knobs), geom.nchunks, geom.chunk_len};
     memcpy(info, vals, sizeof vals);
     if (!h.enabled) return NB_OK;
     if (work) {
@@ -637,6 +638,8 @@ int nb_kernel_time(nb_sim *s, double *total_ms, int32_t *launches)
 }
 
 const char *nb_force_kernel_name(nb_sim *s) { return s ? s->last_kernel : "none"; }
+
+const char *nb_pe_kernel_name(nb_sim *s) { return s ? s->pe_kernel : "none"; }
 
 int nb_synchronize(nb_sim *s)
 {

@@ -422,7 +422,15 @@ potential_kernel(const T *__restrict__ pos, const T *__restrict__ mass, ForceGeo
                 }
                 d2 = round_hp<HP>(d2);
                 const float dist = round_hp<HP>(__builtin_sqrtf(round_hp<HP>(__fadd_rn(d2, eps2_f))));
-                term = (double)round_hp<HP>(__fdiv_rn(round_hp<HP>(nbdev::mass_prod_f32((float)mi, (float)sj[D][jj], mass_dt)), dist));
+                // (mass_prod * mask) / dist is typed promote(masses, positions) upstream: fp64 masses keep an fp64
+                // product and quotient, masses of another 16-bit type or fp32 an fp32 quotient; only masses typed
+                // like the half positions round the quotient to the half type
+                if (mass_dt == NB_F64)
+                    term = ((double)mi * (double)sj[D][jj]) / (double)dist;
+                else if (HP < 0 || mass_dt != HP)
+                    term = (double)__fdiv_rn(nbdev::mass_prod_f32((float)mi, (float)sj[D][jj], mass_dt), dist);
+                else
+                    term = (double)round_hp<HP>(__fdiv_rn(nbdev::mass_prod_f32((float)mi, (float)sj[D][jj], mass_dt), dist));
             } else {
                 double q = eps2;
 #pragma unroll

@@ -128,6 +128,7 @@ struct nb_sim {
     bool mass_uniform = false;           // all masses equal (checked on the device at upload)
     double mass_value = 0.0;
     const char *last_kernel = "none";
+    char pe_kernel[96] = "none";         // variant the last potential-energy evaluation launched (nb_pe_kernel_name)
     ForceGeom geom{};
     // pair-symmetric path (nb_force_sym.hip): device mirror of the host plan (nb_plan.h)
     struct SymPlan {
@@ -203,6 +204,8 @@ int p2p_check(nb_sim *s);
 // ---- nb_step.cpp ---------------------------------------------------------------------------------------------------
 // targets per thread of the one-sided fp64 kernel (FLOAT64 pairs; the cast / half-typed variants always take 2)
 int onesided_r(int n, const NbKnobs &knobs);
+// source chunks of the one-sided kernels (force, potential energy, generic) for this rank's j-range
+ForceGeom onesided_geometry(const nb_config &c, const NbKnobs &knobs);
 void compute_geometry(nb_sim *s);
 // one evaluation of simulation.py:74-118; optionally followed by the closing half kick (:141)
 // defer_kick: the caller will apply the closing half kick itself (fused into the next step's

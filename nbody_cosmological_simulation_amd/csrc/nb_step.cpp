@@ -40,14 +40,14 @@ int onesided_r(int n, const NbKnobs &knobs)
     return (n <= g_tune.onesided_r1_max_n) ? 1 : 2;
 }
 
-void compute_geometry(nb_sim *s)
+ForceGeom onesided_geometry(const nb_config &c, const NbKnobs &knobs)
 {
-    const int n = s->cfg.n;
+    const int n = c.n;
     ForceGeom g{};
     g.n = n;
-    g.j_begin = (int)((int64_t)s->cfg.rank * n / s->cfg.nranks);
-    g.j_end = (int)((int64_t)(s->cfg.rank + 1) * n / s->cfg.nranks);
-    g.r = onesided_r(n, s->knobs);
+    g.j_begin = (int)((int64_t)c.rank * n / c.nranks);
+    g.j_end = (int)((int64_t)(c.rank + 1) * n / c.nranks);
+    g.r = onesided_r(n, knobs);
     const int njr = std::max(g.j_end - g.j_begin, 1);
     const int itiles = (n + NB_BLOCK * g.r - 1) / (NB_BLOCK * g.r);
     const int max_chunks = (njr + NB_TJ - 1) / NB_TJ;
@@ -57,8 +57,10 @@ void compute_geometry(nb_sim *s)
     chunk = (chunk + NB_TJ - 1) / NB_TJ * NB_TJ;
     g.chunk_len = chunk;
     g.nchunks = (njr + chunk - 1) / chunk;
-    s->geom = g;
+    return g;
 }
+
+void compute_geometry(nb_sim *s) { s->geom = onesided_geometry(s->cfg, s->knobs); }
 
 int acc_logical_dtype(const nb_sim *s)
 {
@@ -578,6 +580,16 @@ int step_run(nb_sim *s, int nsteps)
     return NB_OK;
 }
 
+static const char *dtype_name(int dt)
+{
+    switch (dt) {
+    case NB_F16: return "f16";
+    case NB_BF16: return "bf16";
+    case NB_F32: return "f32";
+    default: return "f64";
+    }
+}
+
 int energy_eval(nb_sim *s, double *kinetic, double *potential)
 {
     const nb_config &c = s->cfg;
@@ -607,11 +619,25 @@ int energy_eval(nb_sim *s, double *kinetic, double *potential)
                                            s->logical[0] != NB_F64, s->logical[2], c.softening_sq, pe_uniform ? 1 : 0,
                                            s->stream));
             HIPCHK(nb_launch_final_sum(s->scratch, sp.nwork, s->scalars + 3, s->stream));
+            // the instantiation nb_launch_potential_sym picks (fp32 storage: always fp32 terms); the narrow-mass
+            // sweep (masses carried as float) and the row-split items are branches of their own
+            const bool f32t = !s->is_f64 || s->logical[0] != NB_F64;
+            const bool narrow_mass = s->is_f64 && !f32t && !pe_uniform && s->logical[2] != NB_F64;
+            snprintf(s->pe_kernel, sizeof s->pe_kernel, "potential_sym_kernel<%s,%d,%d,f32t=%d,uniform=%d%s%s%s>",
+                     s->is_f64 ? "double" : "float", c.dim, sp.r, f32t ? 1 : 0, pe_uniform ? 1 : 0,
+                     narrow_mass ? ",mass=" : "", narrow_mass ? dtype_name(s->logical[2]) : "", sp.rowsplit ? ",rowsplit" : "");
         } else {
             HIPCHK(nb_launch_potential(s->pos, s->mass, s->geom, c.dim, s->is_f64, s->logical[0] != NB_F64,
                                        s->logical[2], hp_x, c.softening_sq,
                                        (float)round_dt(hp_x >= 0 ? hp_x : NB_F32, c.softening_sq), s->scratch,
                                        s->scalars + 3, s->stream));
+            // nb_launch_potential: fp32 storage and half-typed positions always take fp32 pair arithmetic; fp64 pair
+            // arithmetic rounds the mass product to the masses' dtype when they are typed narrower (run-time branch)
+            const bool pa_f32 = !s->is_f64 || s->logical[0] != NB_F64 || hp_x >= 0;
+            const bool narrow_mass = !pa_f32 && s->logical[2] != NB_F64;
+            snprintf(s->pe_kernel, sizeof s->pe_kernel, "potential_kernel<%s,%d,pa_f32=%d,hp=%s%s%s>",
+                     s->is_f64 ? "double" : "float", c.dim, pa_f32 ? 1 : 0, hp_x >= 0 ? dtype_name(hp_x) : "none",
+                     narrow_mass ? ",mass=" : "", narrow_mass ? dtype_name(s->logical[2]) : "");
         }
         if ((c.nranks > 1 && !(c.flags & NB_FLAG_NO_COMM)) || s->comm) {
             if (!s->comm) return fail(NB_ERR_COMM, "nranks > 1 but nb_comm_init was not called");

@@ -419,6 +419,11 @@ class GalaxySimulation:
         """Kernel the last force evaluation launched (matches the rocprofv3 kernel-trace rows)."""
         return N.lib().nb_force_kernel_name(self._handle).decode()
 
+    def pe_kernel_name(self) -> str:
+        """Potential-energy kernel variant the last evaluation launched, template arguments included ("none" before
+        the first)."""
+        return N.lib().nb_pe_kernel_name(self._handle).decode()
+
     def quant_debug(self, bins: bool = False):
         """Grid internals of the last force evaluation (INT8/INT4/CUSTOM modes)."""
         import numpy as np

@@ -1,21 +1,25 @@
 """Work-plan shapes of the force path, read through the device-free C-ABI entry nb_plan_debug.
 
-One place for two things:
+One place for three things:
   plan() / shape_key()  what the planner (nb_plan.cpp) hands a rank: targets per lane R, source tiles per item cl,
-                        row-split items, the step pieces its sweeps are cut into;
-  COVERED               the shape keys tests/test_gpu_plan_shapes.py runs against the oracle on the GPU.
+                        row-split items, the step pieces its sweeps are cut into, the one-sided kernels' source chunks;
+  COVERED               the shape keys tests/test_gpu_plan_shapes.py runs against the oracle on the GPU;
+  pe_variant()          the potential-energy kernel variant energy_eval (nb_step.cpp) picks for a plan and a dtype
+                        chain -- tests/test_gpu_energy_shapes.py asserts it against nb_pe_kernel_name on the GPU.
 tests/test_distributed_cpu.py sweeps the planner over sizes, modes and rank counts and fails on a CPU machine when
-it emits a key that is not in COVERED: a retune that creates a new shape needs a GPU case for it.
+it emits a key (or a PE variant) that no GPU case covers: a retune that creates a new shape needs a GPU case for it.
 """
 import ctypes as C
 
 import numpy as np
 
-# mode codes of nb_config.mode (include/nbody_amd.h)
+# mode codes of nb_config.mode and dtype codes of nb_dtype (include/nbody_amd.h)
 FLOAT64, FLOAT32, BFLOAT16, FLOAT16, INT8 = 0, 1, 2, 3, 4
+DT_F16, DT_BF16, DT_F32, DT_F64 = 0, 1, 2, 3
+_DT_NAME = {DT_F16: "f16", DT_BF16: "bf16", DT_F32: "f32", DT_F64: "f64"}
 
 _INFO = ["enabled", "r", "tile_b", "tiles", "np", "nwork", "nslots", "ncol", "cl", "nchunks", "col_mib", "row_mib",
-         "rowsplit", "onesided_r"]
+         "rowsplit", "onesided_r", "os_nchunks", "os_chunk_len"]
 
 
 def plan(n, dim, rank=0, world=1, is_f64=True, mode=FLOAT64, cus=256, work=True, no_comm=False):
@@ -33,6 +37,25 @@ def plan(n, dim, rank=0, world=1, is_f64=True, mode=FLOAT64, cus=256, work=True,
                                 out["nwork"], None, None, None, None, None))
         out["work"] = w
     return out
+
+
+def pe_variant(p, dim, storage_f64, pos_dt, mass_dt, uniform, no_pe_sym=False):
+    """The potential-energy kernel energy_eval launches, as nb_pe_kernel_name reports it, for a rank's plan `p` (from
+    plan(); only enabled / r / rowsplit are read), the state's storage type, the logical dtypes of positions and
+    masses (DT_*) and whether all masses are equal.  The pair-symmetric kernel walks the force plan's work list when
+    the plan has two or four targets per lane and the positions are not half-typed; everything else (R = 1 plans,
+    one-sided force plans, half-typed positions, NB_NO_PE_SYM) takes the one-sided kernel."""
+    hp = pos_dt in (DT_F16, DT_BF16)
+    T = "double" if storage_f64 else "float"
+    if p["enabled"] and not hp and p["r"] in (2, 4) and not no_pe_sym:
+        f32t = not storage_f64 or pos_dt != DT_F64
+        narrow = storage_f64 and not f32t and not uniform and mass_dt != DT_F64
+        return (f"potential_sym_kernel<{T},{dim},{p['r']},f32t={int(f32t)},uniform={int(bool(uniform))}"
+                f"{',mass=' + _DT_NAME[mass_dt] if narrow else ''}{',rowsplit' if p['rowsplit'] > 0 else ''}>")
+    pa_f32 = not storage_f64 or pos_dt != DT_F64
+    narrow = not pa_f32 and mass_dt != DT_F64
+    return (f"potential_kernel<{T},{dim},pa_f32={int(pa_f32)},hp={_DT_NAME[pos_dt] if hp else 'none'}"
+            f"{',mass=' + _DT_NAME[mass_dt] if narrow else ''}>")
 
 
 def pieces(p):

@@ -301,3 +301,45 @@ def test_every_planned_shape_has_a_gpu_case():
                         if key not in covered:
                             missing.setdefault(key, (n, world, mode))
     assert not missing, "shapes without a GPU case (key: first N, ranks, mode): " + repr(missing)
+
+
+def test_every_pe_variant_has_a_gpu_case(monkeypatch):
+    """Coverage contract of tests/test_gpu_energy_shapes.py: every potential-energy kernel variant energy_eval picks
+    (plan_shapes.pe_variant) over sizes 64 ... 1M, both dims, 1, 2, 3, 4 and 8 ranks, the dtype chains below and
+    mixed / equal masses must be one a GPU case compares with the oracle (the cases' variants, from the same mirror the
+    GPU module asserts against nb_pe_kernel_name).  A retune or a new dtype route fails here until a GPU case covers it."""
+    import plan_shapes as S
+    import test_gpu_energy_shapes as E
+    F16, BF16, F32, F64 = S.DT_F16, S.DT_BF16, S.DT_F32, S.DT_F64
+    covered = set()
+    for case in E.ALL_CASES:
+        with monkeypatch.context() as mp:
+            for k, v in case[6].items():
+                mp.setenv(k, v)
+            if case[5] > 1:
+                mp.setenv("NB_SYM", "2")
+            covered |= E.expected_variants(case)
+    # (fp64 storage, mode, positions, masses): fp64 state; fp32 state in FLOAT64 mode at tick 0 and after a step;
+    # fp32 state under a cast / grid mode; fp64 state under a cast mode; half-typed positions on fp32 / fp64 storage
+    # with masses of their own type, fp32 or fp64; fp32 positions beside fp64 masses
+    chains = [(True, S.FLOAT64, F64, F64), (True, S.FLOAT64, F32, F32), (True, S.FLOAT64, F64, F32),
+              (False, S.FLOAT32, F32, F32), (False, S.INT8, F32, F32), (True, S.FLOAT32, F64, F64),
+              (False, S.FLOAT32, F16, F16), (False, S.FLOAT32, BF16, BF16), (False, S.FLOAT32, F16, F32),
+              (True, S.FLOAT64, F16, F16), (True, S.FLOAT32, F16, F64), (True, S.FLOAT32, BF16, F64),
+              (True, S.FLOAT32, BF16, BF16), (True, S.FLOAT32, F32, F64), (True, S.FLOAT64, F32, F64)]
+    sizes = sorted(set(np.geomspace(64, 1 << 20, 120).astype(int).tolist()) | {1 << k for k in range(6, 21)})
+    plans = {}
+    missing = {}
+    for n in sizes:
+        for dim in (2, 3):
+            for world in (1, 2, 3, 4, 8):
+                for f64, mode, pos_dt, mass_dt in chains:
+                    for r in range(world):
+                        key = (n, dim, r, world, f64, mode)
+                        if key not in plans:
+                            plans[key] = S.plan(n, dim, r, world, f64, mode, no_comm=world > 1, work=False)
+                        for uniform in (False, True):
+                            v = S.pe_variant(plans[key], dim, f64, pos_dt, mass_dt, uniform)
+                            if v not in covered:
+                                missing.setdefault(v, (n, world, mode, pos_dt, mass_dt))
+    assert not missing, "PE variants without a GPU case (variant: first N, ranks, mode, dtypes): " + repr(missing)
