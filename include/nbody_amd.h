@@ -306,6 +306,18 @@ const char *nb_force_kernel_name(nb_sim *s);
  * "potential_sym_kernel<double,2,4,f32t=0,uniform=0,mass=f32,rowsplit>" or "potential_kernel<double,3,pa_f32=1,hp=f16>";
  * "none" before the first potential-energy evaluation. */
 const char *nb_pe_kernel_name(nb_sim *s);
+/* Where the leapfrog kicks of the last nb_step / nb_kick_drift / nb_kick ran, noted on the host where the launches are
+ * issued (no device work): up to three space-separated parts, each a '+'-joined list of "<site>[:<kick mode>]",
+ *   open=   opening kick + drift of the call's first step: "spec_read" (the previous call's speculative positions,
+ *           kick applied on read), "pack:1", "kick_drift", "kick_a32" (fp32-typed accelerations on fp64 storage)
+ *   mid=    interior steps: closing kick + next opening kick + drift in one launch (mode 2: "reduce_sym:2", "reduce:2",
+ *           "small:2", "fq_finish:2,packed,red_mm", "p2p:2,x64", "sums64:2", "pack:2" for a deferred closing kick), or
+ *           the separate launches of a step that cannot fuse them
+ *   close=  closing kick of the last step: mode 1, or 3 when the launch also leaves the next step's positions
+ *           ("reduce_sym:3", "small:3"); "|4" marks a launch that applied its step's opening kick on read; "axpy"
+ * e.g. "open=spec_read close=reduce_sym:3|4", "open=kick_drift mid=small:2 close=small:3".  "none" before the first.
+ * The pointer is owned by the handle and valid until the next call on it. */
+const char *nb_step_path_name(nb_sim *s);
 /* Block until all work queued on the handle's stream has finished. */
 int nb_synchronize(nb_sim *s);
 

@@ -31,7 +31,7 @@ EXPORTS = [
     "nb_grid_quantize", "nb_grid_quantize_safe", "nb_comm_unique_id", "nb_comm_init", "nb_comm_ready",
     "nb_comm_shutdown", "nb_comm_quiesce", "nb_comm_p2p_export", "nb_comm_p2p_import", "nb_comm_p2p_selftest",
     "nb_comm_p2p_enable", "nb_comm_p2p_state", "nb_comm_p2p_allreduce", "nb_comm_allreduce_time", "nb_comm_p2p_virtual_test", "nb_plan_debug", "nb_set_hook_stream", "nb_metrics", "nb_metrics_tensors",
-    "nb_kernel_time", "nb_force_kernel_name", "nb_pe_kernel_name", "nb_synchronize", "nb_device_count", "nb_abi_version", "nb_last_error",
+    "nb_kernel_time", "nb_force_kernel_name", "nb_pe_kernel_name", "nb_step_path_name", "nb_synchronize", "nb_device_count", "nb_abi_version", "nb_last_error",
 ]
 
 
@@ -109,6 +109,7 @@ def lib():
         "nb_kernel_time": ([vp, pdbl, pi32], C.c_int),
         "nb_force_kernel_name": ([vp], C.c_char_p),
         "nb_pe_kernel_name": ([vp], C.c_char_p),
+        "nb_step_path_name": ([vp], C.c_char_p),
         "nb_synchronize": ([vp], C.c_int),
         "nb_device_count": ([pi32], C.c_int),
         "nb_abi_version": ([], C.c_int),

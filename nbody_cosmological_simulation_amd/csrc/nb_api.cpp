@@ -487,7 +487,11 @@ int nb_kick_drift(nb_sim *s)
     s->spec_open = false;          // state / parameters change: the speculative next positions are void
     if (!s->have_vel || !s->have_pos || !s->have_acc) return fail(NB_ERR_INVALID, "state incomplete");
     DeviceGuard guard(s->cfg.device);
-    HIPCHK(nb_launch_kick_drift(s->pos, s->vel, s->acc, s->cfg.dt / 2, s->cfg.dt, nd(s), s->is_f64, s->stream));
+    const char *site = "";
+    path_clear(s);
+    if (int rc = launch_plain_kick(s, true, &site)) return rc;
+    path_note(s, 0, site);
+    s->path_open_kd = true;
     s->logical[1] = promote(s->logical[1], s->logical[3]);
     s->logical[0] = promote(s->logical[0], s->logical[1]);
     return NB_OK;
@@ -499,7 +503,13 @@ int nb_kick(nb_sim *s)
     s->spec_open = false;          // state / parameters change: the speculative next positions are void
     if (!s->have_vel || !s->have_acc) return fail(NB_ERR_INVALID, "state incomplete");
     DeviceGuard guard(s->cfg.device);
-    HIPCHK(nb_launch_axpy(s->vel, s->acc, s->cfg.dt / 2, nd(s), s->is_f64, s->stream));
+    const char *site = "";
+    // the closing kick of an override step (nb_kick_drift, caller's forces, nb_kick) keeps that step's opening note
+    const std::string open_note = s->path_open_kd ? s->path_part[0] : std::string();
+    path_clear(s);
+    s->path_part[0] = open_note;
+    if (int rc = launch_plain_kick(s, false, &site)) return rc;
+    path_note(s, 2, site);
     s->logical[1] = promote(s->logical[1], s->logical[3]);
     return NB_OK;
 }
@@ -640,6 +650,8 @@ int nb_kernel_time(nb_sim *s, double *total_ms, int32_t *launches)
 const char *nb_force_kernel_name(nb_sim *s) { return s ? s->last_kernel : "none"; }
 
 const char *nb_pe_kernel_name(nb_sim *s) { return s ? s->pe_kernel : "none"; }
+
+const char *nb_step_path_name(nb_sim *s) { return s ? path_name(s) : "none"; }
 
 int nb_synchronize(nb_sim *s)
 {

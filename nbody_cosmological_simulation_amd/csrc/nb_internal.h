@@ -193,6 +193,9 @@ hipError_t nb_launch_reduce(const double *partial, int nchunks, int64_t count, v
 hipError_t nb_launch_axpy(void *y, const void *x, double scalar, int64_t count, int is_f64, hipStream_t st);
 hipError_t nb_launch_kick_drift(void *pos, void *vel, const void *acc, double half_dt, double dt,
                                 int64_t count, int is_f64, hipStream_t st);
+// fp64 storage, fp32-typed accelerations: the kick (and, drift != 0, the drift) with torch's typing of each operation
+hipError_t nb_launch_kick_a32(void *pos, void *vel, const void *acc, double half_dt, double dt, int64_t count,
+                              int vel_f64, int pos_f64, int drift, hipStream_t st);
 hipError_t nb_launch_convert(const void *in, int in_dt, void *out, int out_dt, int64_t count, hipStream_t st);
 
 // linear force grid (quantization.py:74-88) applied in place inside the step, fp32, with bin output
@@ -205,7 +208,8 @@ hipError_t nb_launch_force_quant_bins(const float *in, float *out, int64_t count
                                       int16_t *bins, hipStream_t st);
 
 hipError_t nb_launch_kinetic(const void *vel, const void *mass, int n, int dim, int is_f64, int vel_f32_logical,
-                             int half_pa, double *scratch, double *out, hipStream_t st);
+                             int half_pa, int mass_dt /* nb_dtype of the masses */, double *scratch, double *out,
+                             hipStream_t st);
 hipError_t nb_launch_potential(const void *pos, const void *mass, const ForceGeom &g, int dim, int is_f64,
                                int pa_f32, int mass_dt /* nb_dtype of the masses */, int half_pa, double eps2_py, float eps2_half,
                                double *scratch, double *out, hipStream_t st);

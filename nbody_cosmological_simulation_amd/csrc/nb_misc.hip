@@ -70,6 +70,35 @@ kick_drift_kernel(T *__restrict__ pos, T *__restrict__ vel, const T *__restrict_
     }
 }
 
+// The same two updates on fp64 storage when the accelerations are fp32-typed (cast / grid modes before the first
+// promotion, caller-made fp32 accelerations): torch types `acc * (dt/2)` like the accelerations -- an fp32 product with
+// the scalar cast to fp32 -- and each sum like promote(left, right).  v64 / p64: velocities / positions typed fp64 (else
+// fp32 or a half type, whose sum is an fp32 one).  Only the non-uniform dtype chains come here; uniform state takes the
+// plain kernels above.
+template <bool DRIFT>
+__global__ void __launch_bounds__(EW_BLOCK)
+kick_a32_kernel(double *__restrict__ pos, double *__restrict__ vel, const double *__restrict__ acc, double half_dt,
+                double dt, int64_t count, int v64, int p64)
+{
+    const float hs = (float)half_dt, ds = (float)dt;
+    for (int64_t idx = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; idx < count;
+         idx += (int64_t)gridDim.x * EW_BLOCK) {
+        const float t = __fmul_rn((float)acc[idx], hs);
+        const double v = v64 ? __dadd_rn(vel[idx], (double)t) : (double)__fadd_rn((float)vel[idx], t);
+        vel[idx] = v;
+        if (DRIFT) {
+            double x;
+            if (v64) {
+                x = axpy1(pos[idx], v, dt);
+            } else {
+                const float u = __fmul_rn((float)v, ds);
+                x = p64 ? __dadd_rn(pos[idx], (double)u) : (double)__fadd_rn((float)pos[idx], u);
+            }
+            pos[idx] = x;
+        }
+    }
+}
+
 // ---- dtype conversion -----------------------------------------------------------------------
 template <typename T> __device__ __forceinline__ double load_as_double(const T *p, int64_t i) { return (double)p[i]; }
 template <> __device__ __forceinline__ double load_as_double<_Float16>(const _Float16 *p, int64_t i) { return (double)(float)p[i]; }
@@ -337,10 +366,13 @@ __device__ __forceinline__ double block_sum(double v, double *s_red)
     return t;
 }
 
-// 0.5 * sum m * |v|^2 (simulation.py:170-174).  VF32: velocities hold fp32-typed values.
+// 0.5 * sum m * |v|^2 (simulation.py:170-174).  VF32: velocities hold fp32-typed values.  The product m * |v|^2 is typed
+// promote(velocities, masses): fp64 masses keep an fp64 product of the unrounded mass, masses typed like the half
+// velocities round it to the half type, every other pair is an fp32 product.  Each operation rounds once (no FMA).
 template <typename T, bool VF32, int HP = -1>
 __global__ void __launch_bounds__(NB_BLOCK)
-kinetic_kernel(const T *__restrict__ vel, const T *__restrict__ mass, int n, int dim, double *__restrict__ part)
+kinetic_kernel(const T *__restrict__ vel, const T *__restrict__ mass, int n, int dim, int mass_dt,
+               double *__restrict__ part)
 {
     __shared__ double s_red[NB_BLOCK / 64];
     double s = 0.0;
@@ -353,14 +385,20 @@ kinetic_kernel(const T *__restrict__ vel, const T *__restrict__ mass, int n, int
                 v2 = (k == 0) ? sq : __fadd_rn(v2, sq);
             }
             v2 = round_hp<HP>(v2);
-            s += (double)round_hp<HP>(__fmul_rn((float)mass[i], v2));
+            if (mass_dt == NB_F64)
+                s += __dmul_rn((double)mass[i], (double)v2);
+            else if (HP >= 0 && mass_dt == HP)
+                s += (double)round_hp<HP>(__fmul_rn((float)mass[i], v2));
+            else
+                s += (double)__fmul_rn((float)mass[i], v2);
         } else {
             double v2 = 0.0;
             for (int k = 0; k < dim; ++k) {
                 const double v = (double)vel[(size_t)i * dim + k];
-                v2 += v * v;
+                const double sq = __dmul_rn(v, v);
+                v2 = (k == 0) ? sq : __dadd_rn(v2, sq);
             }
-            s += (double)mass[i] * v2;
+            s += __dmul_rn((double)mass[i], v2);
         }
     }
     const double t = block_sum<T>(s, s_red);
@@ -499,6 +537,19 @@ hipError_t nb_launch_kick_drift(void *pos, void *vel, const void *acc, double ha
     return hipGetLastError();
 }
 
+hipError_t nb_launch_kick_a32(void *pos, void *vel, const void *acc, double half_dt, double dt, int64_t count,
+                              int vel_f64, int pos_f64, int drift, hipStream_t st)
+{
+    const int grid = ew_grid(count);
+    if (drift)
+        hipLaunchKernelGGL((kick_a32_kernel<true>), dim3(grid), dim3(EW_BLOCK), 0, st, (double *)pos, (double *)vel,
+                           (const double *)acc, half_dt, dt, count, vel_f64, pos_f64);
+    else
+        hipLaunchKernelGGL((kick_a32_kernel<false>), dim3(grid), dim3(EW_BLOCK), 0, st, (double *)pos, (double *)vel,
+                           (const double *)acc, half_dt, dt, count, vel_f64, pos_f64);
+    return hipGetLastError();
+}
+
 hipError_t nb_launch_convert(const void *in, int in_dt, void *out, int out_dt, int64_t count, hipStream_t st)
 {
     switch (in_dt) {
@@ -622,25 +673,25 @@ hipError_t nb_launch_final_sum(const double *part, int count, double *out, hipSt
 }
 
 hipError_t nb_launch_kinetic(const void *vel, const void *mass, int n, int dim, int is_f64, int vel_f32_logical,
-                             int half_pa, double *scratch, double *out, hipStream_t st)
+                             int half_pa, int mass_dt, double *scratch, double *out, hipStream_t st)
 {
     int blocks = (n + NB_BLOCK - 1) / NB_BLOCK;
     if (blocks > 1024) blocks = 1024;
     if (is_f64) {
         if (half_pa == NB_F16)
-            hipLaunchKernelGGL((kinetic_kernel<double, true, NB_F16>), dim3(blocks), dim3(NB_BLOCK), 0, st, (const double *)vel, (const double *)mass, n, dim, scratch);
+            hipLaunchKernelGGL((kinetic_kernel<double, true, NB_F16>), dim3(blocks), dim3(NB_BLOCK), 0, st, (const double *)vel, (const double *)mass, n, dim, mass_dt, scratch);
         else if (half_pa == NB_BF16)
-            hipLaunchKernelGGL((kinetic_kernel<double, true, NB_BF16>), dim3(blocks), dim3(NB_BLOCK), 0, st, (const double *)vel, (const double *)mass, n, dim, scratch);
+            hipLaunchKernelGGL((kinetic_kernel<double, true, NB_BF16>), dim3(blocks), dim3(NB_BLOCK), 0, st, (const double *)vel, (const double *)mass, n, dim, mass_dt, scratch);
         else if (vel_f32_logical)
-            hipLaunchKernelGGL((kinetic_kernel<double, true>), dim3(blocks), dim3(NB_BLOCK), 0, st, (const double *)vel, (const double *)mass, n, dim, scratch);
+            hipLaunchKernelGGL((kinetic_kernel<double, true>), dim3(blocks), dim3(NB_BLOCK), 0, st, (const double *)vel, (const double *)mass, n, dim, mass_dt, scratch);
         else
-            hipLaunchKernelGGL((kinetic_kernel<double, false>), dim3(blocks), dim3(NB_BLOCK), 0, st, (const double *)vel, (const double *)mass, n, dim, scratch);
+            hipLaunchKernelGGL((kinetic_kernel<double, false>), dim3(blocks), dim3(NB_BLOCK), 0, st, (const double *)vel, (const double *)mass, n, dim, mass_dt, scratch);
     } else if (half_pa == NB_F16) {
-        hipLaunchKernelGGL((kinetic_kernel<float, true, NB_F16>), dim3(blocks), dim3(NB_BLOCK), 0, st, (const float *)vel, (const float *)mass, n, dim, scratch);
+        hipLaunchKernelGGL((kinetic_kernel<float, true, NB_F16>), dim3(blocks), dim3(NB_BLOCK), 0, st, (const float *)vel, (const float *)mass, n, dim, mass_dt, scratch);
     } else if (half_pa == NB_BF16) {
-        hipLaunchKernelGGL((kinetic_kernel<float, true, NB_BF16>), dim3(blocks), dim3(NB_BLOCK), 0, st, (const float *)vel, (const float *)mass, n, dim, scratch);
+        hipLaunchKernelGGL((kinetic_kernel<float, true, NB_BF16>), dim3(blocks), dim3(NB_BLOCK), 0, st, (const float *)vel, (const float *)mass, n, dim, mass_dt, scratch);
     } else {
-        hipLaunchKernelGGL((kinetic_kernel<float, true>), dim3(blocks), dim3(NB_BLOCK), 0, st, (const float *)vel, (const float *)mass, n, dim, scratch);
+        hipLaunchKernelGGL((kinetic_kernel<float, true>), dim3(blocks), dim3(NB_BLOCK), 0, st, (const float *)vel, (const float *)mass, n, dim, mass_dt, scratch);
     }
     hipLaunchKernelGGL(final_sum_kernel, dim3(1), dim3(NB_BLOCK), 0, st, scratch, blocks, out);
     return hipGetLastError();

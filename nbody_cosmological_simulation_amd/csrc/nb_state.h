@@ -129,6 +129,12 @@ struct nb_sim {
     double mass_value = 0.0;
     const char *last_kernel = "none";
     char pe_kernel[96] = "none";         // variant the last potential-energy evaluation launched (nb_pe_kernel_name)
+    // where the leapfrog kicks of the last nb_step / nb_kick_drift / nb_kick ran (nb_step_path_name): host-side notes
+    // taken where the launches are issued
+    std::string path_part[3];            // opening kick + drift of the first step, interior steps, closing kick of the last
+    std::string step_path = "none";
+    bool path_open_kd = false;           // the note of the opening part came from nb_kick_drift (nb_kick keeps it)
+    char kick_site[64] = "";             // force_eval -> step_run: the launch that applied this evaluation's kick(s)
     ForceGeom geom{};
     // pair-symmetric path (nb_force_sym.hip): device mirror of the host plan (nb_plan.h)
     struct SymPlan {
@@ -212,6 +218,14 @@ void compute_geometry(nb_sim *s);
 // opening launch) when this evaluation cannot fuse it into its reduction.
 int force_eval(nb_sim *s, bool do_kick, bool packed_ready = false, bool *defer_kick = nullptr,
                bool *open_next = nullptr);
+// step-path notes (nb_step_path_name): `where` 0 opening kick + drift of the first step, 1 interior steps, 2 closing
+// kick of the last step; a site already noted for the same part is not repeated
+void path_clear(nb_sim *s);
+void path_note(nb_sim *s, int where, const char *site);
+const char *path_name(nb_sim *s);
+// v += a dt/2 (drift: then x += v dt) in a launch of its own, typed like torch types it for the handle's logical
+// dtypes; call BEFORE promoting them.  *site: "kick_drift" / "axpy", or "kick_a32" for the mixed-dtype variant
+int launch_plain_kick(nb_sim *s, bool drift, const char **site);
 int step_run(nb_sim *s, int nsteps);                                   // simulation.py:120-143, nsteps times
 int energy_eval(nb_sim *s, double *kinetic, double *potential);        // simulation.py:170-192
 int bin_sums_eval(nb_sim *s, int which, int64_t *sum_k, int64_t *sum_kw, double info[8]);

@@ -62,6 +62,54 @@ ForceGeom onesided_geometry(const nb_config &c, const NbKnobs &knobs)
 
 void compute_geometry(nb_sim *s) { s->geom = onesided_geometry(s->cfg, s->knobs); }
 
+void path_clear(nb_sim *s)
+{
+    for (std::string &p : s->path_part) p.clear();
+    s->path_open_kd = false;
+}
+
+void path_note(nb_sim *s, int where, const char *site)
+{
+    if (!site || !*site) return;
+    std::string &p = s->path_part[where];
+    // the interior steps of a long call repeat one site: a comparison with the last token, no allocation
+    const size_t len = strlen(site);
+    if (p.size() >= len && p.compare(p.size() - len, len, site) == 0 && (p.size() == len || p[p.size() - len - 1] == '+')) return;
+    // whole-token match: "reduce_sym:3" is not contained in "reduce_sym:3|4"
+    const std::string tok = std::string("+") + site + "+";
+    if (("+" + p + "+").find(tok) == std::string::npos) p += (p.empty() ? "" : "+") + std::string(site);
+}
+
+// the reported string is put together only when it is asked for
+const char *path_name(nb_sim *s)
+{
+    static const char *const key[3] = {"open=", "mid=", "close="};
+    s->step_path.clear();
+    for (int k = 0; k < 3; ++k)
+        if (!s->path_part[k].empty()) s->step_path += (s->step_path.empty() ? "" : " ") + (key[k] + s->path_part[k]);
+    if (s->step_path.empty()) s->step_path = "none";
+    return s->step_path.c_str();
+}
+
+int launch_plain_kick(nb_sim *s, bool drift, const char **site)
+{
+    const nb_config &c = s->cfg;
+    if (s->is_f64 && s->logical[3] == NB_F32) {
+        // fp32-typed accelerations on fp64 storage: the dtype-faithful variant (never the hot, uniform paths)
+        const int v64 = promote(s->logical[1], NB_F32) == NB_F64;
+        HIPCHK(nb_launch_kick_a32(s->pos, s->vel, s->acc, c.dt / 2, c.dt, nd(s), v64, s->logical[0] == NB_F64, drift ? 1 : 0,
+                                  s->stream));
+        *site = "kick_a32";
+    } else if (drift) {
+        HIPCHK(nb_launch_kick_drift(s->pos, s->vel, s->acc, c.dt / 2, c.dt, nd(s), s->is_f64, s->stream));
+        *site = "kick_drift";
+    } else {
+        HIPCHK(nb_launch_axpy(s->vel, s->acc, c.dt / 2, nd(s), s->is_f64, s->stream));
+        *site = "axpy";
+    }
+    return NB_OK;
+}
+
 int acc_logical_dtype(const nb_sim *s)
 {
     // promote(promote(Q, M), P) with Q = hook output dtype (quantization.py:43-71)
@@ -72,6 +120,13 @@ int acc_logical_dtype(const nb_sim *s)
 }
 
 namespace {
+
+// the launch that applied the kick(s) of this evaluation: "<site>:<mode>" (+ "|4": opening kick applied on read)
+void site_set(nb_sim *s, const char *site, int mode, const char *tags = "")
+{
+    if (!(mode & 3)) { s->kick_site[0] = 0; return; }
+    snprintf(s->kick_site, sizeof s->kick_site, "%s:%d%s%s", site, mode & 3, (mode & 4) ? "|4" : "", tags);
+}
 
 int prof_begin(nb_sim *s, int *slot, bool record = true)
 {
@@ -160,9 +215,13 @@ int force_eval_generic(nb_sim *s, bool do_kick, bool *defer_kick, bool *open_nex
         }
     }
     if (open_next) *open_next = false;
+    s->kick_site[0] = 0;
     if (do_kick) {
         if (defer_kick) *defer_kick = true;
-        else HIPCHK(nb_launch_axpy(s->vel, s->acc, c.dt / 2, cnt, s->is_f64, s->stream));
+        else {
+            HIPCHK(nb_launch_axpy(s->vel, s->acc, c.dt / 2, cnt, s->is_f64, s->stream));
+            snprintf(s->kick_site, sizeof s->kick_site, "axpy");
+        }
     }
     s->logical[3] = A;
     s->have_acc = true;
@@ -194,6 +253,7 @@ int force_eval(nb_sim *s, bool do_kick, bool packed_ready, bool *defer_kick, boo
         return force_eval_generic(s, do_kick, defer_kick, open_next);
     }
     s->last_generic = false;
+    s->kick_site[0] = 0;
     int slot;
     bool used_sym = false, sym_uniform = false;
 
@@ -362,6 +422,7 @@ int force_eval(nb_sim *s, bool do_kick, bool packed_ready, bool *defer_kick, boo
                                     sp.tile_b, c.n, sp.np, c.dim, s->is_f64, scale, red_out, s->vel, half_dt,
                                     kmode, s->pos, sp.packed, c.dt, s->stream, 0, -1, sums64,
                                     red_mm ? s->scalars + 8 : nullptr, s->pos_alt));
+        site_set(s, "reduce_sym", kmode);
         if (spec) { s->spec_open = true; s->spec_kind = 2; s->spec_dt = c.dt; }
         x64_scale = scale;
         opened = open;
@@ -372,6 +433,7 @@ int force_eval(nb_sim *s, bool do_kick, bool packed_ready, bool *defer_kick, boo
         const bool open = fuse_kick && want_open;
         HIPCHK(nb_launch_reduce(s->partial, s->geom.nchunks, cnt, red_out, s->is_f64, s->vel, half_dt,
                                 open ? 2 : (fuse_kick ? 1 : 0), s->pos, c.dt, s->stream));
+        site_set(s, "reduce", open ? 2 : (fuse_kick ? 1 : 0));
         opened = open;
     }
     bool kicked = fuse_kick;
@@ -391,6 +453,7 @@ int force_eval(nb_sim *s, bool do_kick, bool packed_ready, bool *defer_kick, boo
             opened = open;
         }
         HIPCHK(nb_p2p_allreduce(s->acc, (size_t)cnt, s->is_f64 || x64, p2p_step_timeout_s(), s->stream, &kk));
+        if (kk.mode) site_set(s, "p2p", kk.mode, x64 ? ",x64" : "");
         s->used_p2p = true;
     } else if (multi && x64) {
         if (int rc = comm_allreduce_sum(s, s->sums64, (size_t)cnt, true)) return rc;
@@ -399,6 +462,7 @@ int force_eval(nb_sim *s, bool do_kick, bool packed_ready, bool *defer_kick, boo
         HIPCHK(nb_launch_finish_sums64(s->sums64, x64_scale, (float *)s->acc, (float *)s->vel, (float *)s->pos,
                                        (float *)s->sym.packed, c.n, s->sym.np, c.dim, fin_kick ? (open ? 2 : 1) : 0,
                                        half_dt, c.dt, s->stream));
+        site_set(s, "sums64", fin_kick ? (open ? 2 : 1) : 0);
         if (fin_kick) { kicked = true; opened = open; }
     } else if (multi) {
         if (int rc = comm_allreduce_sum(s, s->acc, (size_t)cnt, s->is_f64)) return rc;
@@ -416,13 +480,20 @@ int force_eval(nb_sim *s, bool do_kick, bool packed_ready, bool *defer_kick, boo
         HIPCHK(nb_launch_force_quant_step((float *)s->acc, cnt, mode_levels(c), s->scalars, s->scalars + 8, s->fbins,
                                           (float *)s->vel, (float *)s->pos, half_dt, c.dt, do_kick ? (open ? 2 : 1) : 0,
                                           used_sym ? (float *)s->sym.packed : nullptr, s->sym.np, c.dim, s->stream));
+        {
+            const int km = do_kick ? (open ? 2 : 1) : 0;
+            site_set(s, "fq_finish", km, (km == 2 && used_sym) ? (red_mm ? ",packed,red_mm" : ",packed") : (red_mm ? ",red_mm" : ""));
+        }
         kicked = do_kick;
         opened = open;
     }
     if (open_next) *open_next = opened;
     if (do_kick && !kicked) {
         if (defer_kick) *defer_kick = true;
-        else HIPCHK(nb_launch_axpy(s->vel, s->acc, half_dt, cnt, s->is_f64, s->stream));
+        else {
+            HIPCHK(nb_launch_axpy(s->vel, s->acc, half_dt, cnt, s->is_f64, s->stream));
+            snprintf(s->kick_site, sizeof s->kick_site, "axpy");
+        }
     }
     s->logical[3] = acc_logical_dtype(s);
     s->have_acc = true;
@@ -473,7 +544,7 @@ int small_grid_tables(nb_sim *s)
 }
 
 // the remaining `nsteps` steps of an nb_step call; `opened`: this step's opening kick + drift was already applied
-int step_small(nb_sim *s, int nsteps, bool opened)
+int step_small(nb_sim *s, int nsteps, bool opened, bool first)
 {
     const nb_config &c = s->cfg;
     const size_t el = s->is_f64 ? 8 : 4;
@@ -493,8 +564,10 @@ int step_small(nb_sim *s, int nsteps, bool opened)
         if (speculate && s->spec_open && s->spec_kind == 1 && s->spec_dt == c.dt) {
             std::swap(s->pos, s->pos_alt);
             open_on_read = true;
+            path_note(s, first ? 0 : 1, "spec_read");
         } else {
             HIPCHK(nb_launch_kick_drift(s->pos, s->vel, s->acc, c.dt / 2, c.dt, nd(s), s->is_f64, s->stream));
+            path_note(s, first ? 0 : 1, "kick_drift");
         }
     }
     s->spec_open = false;
@@ -510,6 +583,8 @@ int step_small(nb_sim *s, int nsteps, bool opened)
                                     c.softening_sq, c.dt / 2, c.dt, kick, lanes, s->stream, grid ? s->tab : nullptr,
                                     fq ? s->small_part : nullptr));
         if (int rc = prof_end(s, slot)) return rc;
+        site_set(s, fq ? "fq_finish" : "small", fq ? (last ? 1 : 2) : kick, fq ? ",small" : "");
+        path_note(s, last ? 2 : 1, s->kick_site);
         if (fq)      // one min / max pair per workgroup of the force launch
             HIPCHK(nb_launch_force_quant_finish((float *)s->acc, nd(s), mode_levels(c), s->small_part,
                                                 (c.n + nb_small_block(c.n) / lanes - 1) / (nb_small_block(c.n) / lanes), s->scalars, s->fbins,
@@ -532,15 +607,17 @@ int step_run(nb_sim *s, int nsteps)
     bool opened = false;            // the previous step's reduction already did this step's opening kick + drift
     bool packed_by_prev = false;    // ... and repacked the positions for the symmetric kernel
     bool open_on_read = false;      // this call starts from the previous call's speculative positions (tiled path)
+    path_clear(s);
     for (int t = 0; t < nsteps; ++t) {
         // small systems with settled dtypes: one launch per step
-        if (!pending_close && small_ok(s)) return step_small(s, nsteps - t, opened);
+        if (!pending_close && small_ok(s)) return step_small(s, nsteps - t, opened, t == 0);
         if (t == 0 && s->spec_open && s->spec_kind == 2 && s->spec_dt == s->cfg.dt && s->sym.enabled && !comm_active(s) &&
             !force_quant_mode(s->cfg) && !grid_mode(s->cfg.mode) && s->pos_alt) {
             const int sd = s->is_f64 ? NB_F64 : NB_F32;
             if (s->logical[0] == sd && s->logical[1] == sd && s->logical[3] == sd) {
                 std::swap(s->pos, s->pos_alt);        // positions after this step's drift; `packed` holds them as well
                 opened = packed_by_prev = open_on_read = true;
+                path_note(s, 0, "spec_read");
             }
         }
         s->spec_open = false;
@@ -555,9 +632,15 @@ int step_run(nb_sim *s, int nsteps)
             HIPCHK(nb_launch_pack(s->pos, s->vel, s->acc, s->mass, s->sym.packed, s->cfg.n, s->sym.np, s->cfg.dim,
                                   s->is_f64, pending_close ? 2 : 1, s->cfg.dt / 2, s->cfg.dt,
                                   s->is_f64 ? s->cfg.G : (double)(float)s->cfg.G, 0, s->stream));
+            path_note(s, t == 0 ? 0 : 1, pending_close ? "pack:2" : "pack:1");
         } else {
-            if (pending_close) HIPCHK(nb_launch_axpy(s->vel, s->acc, s->cfg.dt / 2, nd(s), s->is_f64, s->stream));
-            HIPCHK(nb_launch_kick_drift(s->pos, s->vel, s->acc, s->cfg.dt / 2, s->cfg.dt, nd(s), s->is_f64, s->stream));
+            const char *site = "";
+            if (pending_close) {
+                if (int rc = launch_plain_kick(s, false, &site)) return rc;
+                path_note(s, 1, site);
+            }
+            if (int rc = launch_plain_kick(s, true, &site)) return rc;
+            path_note(s, t == 0 ? 0 : 1, site);
         }
         // packed positions are current when this step's pack launch wrote them, or when the previous evaluation
         // opened this step on the symmetric path (its reduction / quantisation repacked them)
@@ -574,6 +657,7 @@ int step_run(nb_sim *s, int nsteps)
         const int rc_eval = force_eval(s, true, packed_ready, may_defer ? &pending_close : nullptr, &opened);
         s->req_open_on_read = s->req_spec_next = false;
         if (rc_eval) return rc_eval;
+        path_note(s, t + 1 < nsteps ? 1 : 2, s->kick_site);      // (nothing when the closing kick was deferred)
         packed_by_prev = opened && s->sym.enabled;
         s->logical[1] = promote(s->logical[1], s->logical[3]);
     }
@@ -599,7 +683,7 @@ int energy_eval(nb_sim *s, double *kinetic, double *potential)
     const int hp_x = is_half(s->logical[0]) ? s->logical[0] : -1;
     if (kinetic) {
         if (!s->have_vel || !s->have_mass) return fail(NB_ERR_INVALID, "velocities/masses not set");
-        HIPCHK(nb_launch_kinetic(s->vel, s->mass, c.n, c.dim, s->is_f64, s->logical[1] != NB_F64, hp_v, s->scratch,
+        HIPCHK(nb_launch_kinetic(s->vel, s->mass, c.n, c.dim, s->is_f64, s->logical[1] != NB_F64, hp_v, s->logical[2], s->scratch,
                                  s->scalars + 2, s->stream));
     }
     if (potential) {

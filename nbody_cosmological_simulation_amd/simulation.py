@@ -424,6 +424,11 @@ class GalaxySimulation:
         the first)."""
         return N.lib().nb_pe_kernel_name(self._handle).decode()
 
+    def step_path_name(self) -> str:
+        """Where the kicks of the last step() / run() ran: "open=<site> mid=<sites> close=<site>" with the kick mode of
+        each launch (include/nbody_amd.h nb_step_path_name); "none" before the first step."""
+        return N.lib().nb_step_path_name(self._handle).decode()
+
     def quant_debug(self, bins: bool = False):
         """Grid internals of the last force evaluation (INT8/INT4/CUSTOM modes)."""
         import numpy as np

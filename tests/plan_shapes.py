@@ -6,6 +6,8 @@ One place for three things:
   COVERED               the shape keys tests/test_gpu_plan_shapes.py runs against the oracle on the GPU;
   pe_variant()          the potential-energy kernel variant energy_eval (nb_step.cpp) picks for a plan and a dtype
                         chain -- tests/test_gpu_energy_shapes.py asserts it against nb_pe_kernel_name on the GPU.
+  step_path()           the sites of the leapfrog kicks step_run (nb_step.cpp) picks for a call -- tests/test_gpu_kick_paths.py
+                        asserts it against nb_step_path_name on the GPU before it checks the recurrence bit for bit.
 tests/test_distributed_cpu.py sweeps the planner over sizes, modes and rank counts and fails on a CPU machine when
 it emits a key (or a PE variant) that no GPU case covers: a retune that creates a new shape needs a GPU case for it.
 """
@@ -56,6 +58,133 @@ def pe_variant(p, dim, storage_f64, pos_dt, mass_dt, uniform, no_pe_sym=False):
     narrow = not pa_f32 and mass_dt != DT_F64
     return (f"potential_kernel<{T},{dim},pa_f32={int(pa_f32)},hp={_DT_NAME[pos_dt] if hp else 'none'}"
             f"{',mass=' + _DT_NAME[mass_dt] if narrow else ''}>")
+
+
+INT4, CUSTOM = 5, 6
+SMALL_MAX_F64, SMALL_MAX_F32, LUT_MIN, MAX_LUT, RED_MM_MAX_BLOCKS = 4096, 3072, 256, 4096, 1024
+
+
+def _promote(a, b):
+    return a if a == b else (DT_F64 if DT_F64 in (a, b) else DT_F32)
+
+
+def mode_levels(mode, levels=0):
+    return {INT8: 256, INT4: 16}.get(mode, levels if levels > 0 else 64)
+
+
+def acc_dtype(mode, pos_dt, mass_dt):
+    """promote(promote(promote(Q, M), fp32), P), Q the hook's output dtype (nb_step.cpp acc_logical_dtype)."""
+    q = DT_F64 if mode == FLOAT64 else (DT_F32 if mode <= FLOAT16 else pos_dt)
+    return _promote(_promote(_promote(q, mass_dt), DT_F32), pos_dt)
+
+
+def step_path(p, n, mode, storage_f64, dts, nsteps, spec=0, env=(), levels=0):
+    """The string nb_step_path_name reports after nb_step(nsteps) on ONE GPU, the speculation state the call leaves
+    (0 none, 1 small-system kernel, 2 reduce_sym_kernel) and the logical dtypes after it.  `p`: the rank's plan (only
+    enabled is read); dts: logical dtypes [positions, velocities, masses, accelerations] before the call; spec: the
+    state the previous call left (0 after any write of state or dt); env: the knobs of the case.  A line-by-line
+    mirror of step_run / step_small / force_eval's choice of the launch that applies each kick."""
+    P, V, M, A = dts
+    sdt = DT_F64 if storage_f64 else DT_F32
+    grid, fq = mode >= INT8, mode in (INT8, INT4)
+    L = mode_levels(mode, levels)
+    no_spec, no_smalln = "NB_NO_SPEC" in env, "NB_NO_SMALLN" in env
+    parts = [[], [], []]
+
+    def note(where, site):
+        if site and site not in parts[where]:
+            parts[where].append(site)
+
+    def finish(spec_out):
+        name = " ".join(k + "+".join(v) for k, v in zip(("open=", "mid=", "close="), parts) if v)
+        return name or "none", spec_out, [P, V, M, A]
+
+    def uniform():
+        return P == sdt and V == sdt and A == sdt
+
+    def small_ok():
+        if no_smalln or n > (SMALL_MAX_F64 if storage_f64 else SMALL_MAX_F32):
+            return False
+        if grid and (storage_f64 or L > LUT_MIN or L < 2):
+            return False
+        if storage_f64 != (mode == FLOAT64):
+            return False
+        return uniform() and (M == sdt or (storage_f64 and M == DT_F32))
+
+    def generic():
+        if grid and L > MAX_LUT:
+            return True
+        if storage_f64:
+            return False if mode == FLOAT64 else (True if grid else P != DT_F64)
+        return grid and P in (DT_F16, DT_BF16)
+
+    def plain(drift):
+        return "kick_a32" if storage_f64 and A == DT_F32 else ("kick_drift" if drift else "axpy")
+
+    pending = opened = open_on_read = False
+    for t in range(nsteps):
+        if not pending and small_ok():
+            rest = nsteps - t
+            speculate = not grid and not fq and not no_spec
+            on_read = False
+            if not opened:
+                on_read = speculate and spec == 1
+                note(0 if t == 0 else 1, "spec_read" if on_read else "kick_drift")
+            for u in range(rest):
+                last = u + 1 == rest
+                if fq:
+                    site = "fq_finish:%d,small" % (1 if last else 2)
+                else:
+                    site = "small:%d%s" % ((3 if speculate else 1) if last else 2, "|4" if (u == 0 and on_read) else "")
+                note(2 if last else 1, site)
+            return finish(1 if speculate else 0)
+        if t == 0 and spec == 2 and p["enabled"] and not fq and not grid and uniform():
+            opened = open_on_read = True
+            note(0, "spec_read")
+        fuse_pack = p["enabled"] and uniform() and not grid
+        uni = uniform()
+        if opened:
+            pass
+        elif fuse_pack:
+            note(0 if t == 0 else 1, "pack:2" if pending else "pack:1")
+        else:
+            if pending:
+                note(1, plain(False))
+            note(0 if t == 0 else 1, plain(True))
+        pending = False
+        V = _promote(V, A)
+        P = _promote(P, V)
+        inner = t + 1 < nsteps
+        may_defer = inner and fuse_pack
+        want_open = inner and uni
+        spec_next = (not inner) and uni and p["enabled"] and not no_spec
+        site, opened = "", False
+        if generic():
+            if may_defer:
+                pending = True
+            else:
+                site = "axpy"
+        else:
+            if storage_f64:
+                used_sym = p["enabled"] and mode == FLOAT64 and (P == DT_F64 or (P == DT_F32 and p["r"] in (2, 4)))
+            else:
+                used_sym = p["enabled"] and P == DT_F32
+            if fq:
+                red_mm = used_sym and not storage_f64 and (n + 63) // 64 <= RED_MM_MAX_BLOCKS and "NB_NO_RED_MM" not in env
+                k = 2 if want_open else 1
+                tags = (",packed" if (k == 2 and used_sym) else "") + (",red_mm" if red_mm else "")
+                site, opened = "fq_finish:%d%s" % (k, tags), want_open
+            elif used_sym:
+                spec_now = (not want_open) and spec_next and not grid
+                k = 2 if want_open else (3 if spec_now else 1)
+                site = "reduce_sym:%d%s" % (k, "|4" if (t == 0 and open_on_read) else "")
+                opened = want_open
+            else:
+                site, opened = "reduce:%d" % (2 if want_open else 1), want_open
+        note(1 if inner else 2, site)
+        A = acc_dtype(mode, P, M)
+        V = _promote(V, A)
+    return finish(2 if parts[2] and parts[2][-1].startswith("reduce_sym:3") else 0)
 
 
 def pieces(p):

@@ -343,3 +343,56 @@ def test_every_pe_variant_has_a_gpu_case(monkeypatch):
                             if v not in covered:
                                 missing.setdefault(v, (n, world, mode, pos_dt, mass_dt))
     assert not missing, "PE variants without a GPU case (variant: first N, ranks, mode, dtypes): " + repr(missing)
+
+
+def test_every_step_path_has_a_gpu_case(monkeypatch):
+    """Coverage contract of tests/test_gpu_kick_paths.py: every site / kick-mode string the step-path mirror
+    (plan_shapes.step_path, asserted against nb_step_path_name on the GPU) emits over modes x N x dims x dtype chains x
+    position in the call must be one a GPU case of that module runs through the bit-for-bit recurrence; so must the
+    multi-rank sites (the kicks inside the direct all-reduce, p2p:1 / p2p:2, and the closing kick deferred into the next
+    pack launch, pack:2), which the traces of tests/tools/multirank_worker.py cover.  The one site a one-GPU run does
+    not reach is the finish launch after an RCCL exchange of fp64 sums (nb_launch_finish_sums64: the two-GPU test;
+    its own kick modes are never selected)."""
+    import plan_shapes as S
+    import test_gpu_kick_paths as K
+
+    def tokens(name):
+        return {(part.split("=")[0], site) for part in name.split() for site in part.split("=")[1].split("+")}
+
+    covered = set()
+    for case in K.CASES:
+        with monkeypatch.context() as mp:
+            for k, v in case[6].items():
+                mp.setenv(k, v)
+            for name in K.sites_of(case, K.case_plan(case)):
+                covered |= tokens(name)
+    covered |= K.multirank_sites()
+    multi = {("close", "p2p:1"), ("mid", "p2p:2"), ("mid", "pack:2"), ("close", "axpy"), ("mid", "fq_finish:2,packed")}
+    assert multi <= K.multirank_sites(), multi - K.multirank_sites()
+    F16, BF16, F32, F64 = S.DT_F16, S.DT_BF16, S.DT_F32, S.DT_F64
+    # (fp64 storage, mode, [positions, velocities, masses]) -- the chains of the GPU module
+    chains = [(True, S.FLOAT64, [F64, F64, F64]), (True, S.FLOAT64, [F32, F32, F32]), (True, S.FLOAT64, [F16, F16, F16]),
+              (False, S.FLOAT32, [F32, F32, F32]), (False, S.FLOAT16, [F32, F32, F32]), (False, S.INT8, [F32, F32, F32]),
+              (False, S.INT4, [F32, F32, F32]), (False, S.CUSTOM, [F32, F32, F32]), (True, S.INT8, [F64, F64, F64])]
+    for mode in (S.FLOAT32, S.INT8):
+        chains += [(False, mode, [F16, F16, F16]), (False, mode, [BF16, BF16, BF16]), (True, mode, [F32, F32, F64]),
+                   (True, mode, [F32, F64, F32]), (True, mode, [F16, F64, F16]), (True, mode, [BF16, F64, BF16]),
+                   (False, mode, [F16, F16, F32])]
+    sizes = sorted(set(np.geomspace(64, 1 << 20, 60).astype(int).tolist()) | {1 << k for k in range(6, 21)})
+    missing = {}
+    for n in sizes:
+        for dim in (2, 3):
+            for f64, mode, dts3 in chains:
+                p = S.plan(n, dim, 0, 1, f64, mode, work=False)
+                for env in ((), ("NB_NO_SPEC",)):
+                    dts = dts3 + [S.acc_dtype(mode, dts3[0], dts3[2])]
+                    names = []
+                    spec, d = 0, list(dts)
+                    for _ in range(3):                       # a step() loop ...
+                        name, spec, d = S.step_path(p, n, mode, f64, d, 1, spec, env)
+                        names.append(name)
+                    names += [S.step_path(p, n, mode, f64, list(dts), k, 0, env)[0] for k in (2, 5)]    # ... and run(k)
+                    for name in names:
+                        for tok in tokens(name) - covered:
+                            missing.setdefault(tok, (n, dim, f64, mode, dts3))
+    assert not missing, "kick sites without a GPU case (part, site: first N, dim, fp64 storage, mode, dtypes): " + repr(missing)

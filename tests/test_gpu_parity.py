@@ -1982,6 +1982,7 @@ dist.init_process_group("nccl", device_id=torch.device("cuda", lr))
 import nbody_cosmological_simulation_amd as nb
 from nbody_cosmological_simulation_amd import runtime, galaxy
 out = {}
+trace = {}
 for name, n, mode in (("f64", 9000, nb.PrecisionMode.FLOAT64), ("f32", 9000, nb.PrecisionMode.FLOAT32),
                       ("int4", 3000, nb.PrecisionMode.INT4_SIM), ("int4_big", 9000, nb.PrecisionMode.INT4_SIM)):
     pos, vel, mass = galaxy.create_disk_galaxy(n, seed=5, device="cpu")
@@ -1996,6 +1997,24 @@ for name, n, mode in (("f64", 9000, nb.PrecisionMode.FLOAT64), ("f32", 9000, nb.
                  "energy": [single.get_total_energy(), multi.get_total_energy()],
                  "hash": hashlib.sha256(multi.positions.cpu().numpy().tobytes()).hexdigest()}
     single.close(); multi.close()
+    if name in ("f64", "int4_big"):
+        # a step() loop and run(3) of the RCCL step, state read after every step (tests/test_gpu_kick_paths.py): the
+        # deferred closing kick; INT4: the exchange of fp64 sums, nb_launch_finish_sums64, then the finish launch
+        code = {torch.float32: 2, torch.float64: 3}
+        def grab(sim, key):
+            cs = []
+            for part, t in (("x", sim.positions), ("v", sim.velocities), ("a", sim.accelerations)):
+                trace[f"{key}/{part}"] = t.detach().cpu().double().numpy()
+                cs.append(code[t.dtype])
+            return cs
+        mk = lambda: nb.GalaxySimulation(pos, vel * 1e-3, mass, precision_mode=mode, device=torch.device("cuda", lr))
+        sim = mk()
+        codes, paths = [grab(sim, f"{name}/0")], []
+        for i in range(3):
+            sim.step(); paths.append(sim.step_path_name()); codes.append(grab(sim, f"{name}/{i + 1}"))
+        sim.close()
+        sim = mk(); sim.run(3); paths.append(sim.step_path_name()); codes.append(grab(sim, f"{name}/run")); sim.close()
+        out[name]["trace"] = {"codes": codes, "paths": paths, "dt": sim.dt}
 gathered = [None] * dist.get_world_size()
 dist.all_gather_object(gathered, out)
 runtime.shutdown()
@@ -2003,6 +2022,7 @@ dist.barrier()
 dist.destroy_process_group()
 if rank == 0:
     json.dump(gathered, open(os.environ["NB_OUT"], "w"))
+    np.savez(os.environ["NB_OUT"] + ".trace.npz", **trace)
 '''
     with tempfile.TemporaryDirectory() as tmp:
         path = os.path.join(tmp, "two_rank.py")
@@ -2018,6 +2038,7 @@ if rank == 0:
                              capture_output=True, text=True, timeout=600)
         assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
         ranks = json.load(open(outp))
+        arrays = dict(np.load(outp + ".trace.npz"))
     assert len(ranks) == nproc
     for name in ("f64", "f32", "int4", "int4_big"):
         a, b = ranks[0][name], ranks[-1][name]
@@ -2025,6 +2046,9 @@ if rank == 0:
         tol = 1e-12 if name == "f64" else (2e-6 if name == "f32" else 1e-4)
         assert a["relerr"] < tol, (name, a["relerr"])
         assert abs(a["energy"][0] - a["energy"][1]) <= max(tol, 1e-12) * abs(a["energy"][0]) * (1 if name != "int4" and name != "int4_big" else 100)
+    # the kick sites of the RCCL step bit for bit, the launch after the exchange of fp64 sums included
+    import test_gpu_kick_paths as K
+    K.check_multirank_trace(ranks[0], arrays, "rccl", K.RCCL_PATHS)
 
 
 def test_direct_allreduce_virtual_ranks():
@@ -2132,6 +2156,10 @@ def test_multi_rank_product_path_on_one_gpu(nb, world, variant, tmp_path):
     assert ranks[0]["int8_big"]["relerr_x"] < 1e-7 and ranks[0]["int8_big"]["relerr_v"] < 1e-6, ranks[0]["int8_big"]
     assert ranks[0]["f64"]["kernel"].startswith("force_sym_kernel<double")
     assert ranks[0]["f64_onesided"]["kernel"].startswith("force_f64")
+    # the kick sites of the multi-rank step, bit for bit (tests/test_gpu_kick_paths.py): the leapfrog recurrence of a
+    # step() loop given the engine's own accelerations, run(k) against that loop, and the site each call reports
+    import test_gpu_kick_paths as K
+    K.check_multirank_trace(ranks[0], np.load(outp + ".trace.npz"), variant, K.MULTIRANK_PATHS[variant])
 
 
 def test_direct_allreduce_dead_peer_drains_within_its_timeout(nb):

@@ -638,3 +638,44 @@ def test_oracle_prequant_forces_at_config3_size_vs_reference_ops():
         r = int(g["rows"][idx])
         got, _ = O.accelerations_rows(pos, mass, "int8_sim", r, r + 1)
         assert np.abs(got[0].astype(np.float64) - g["int8_sim/pre_rows"][idx]).max() <= 2e-6 * scale
+
+
+
+def _pin_dtypes():
+    import torch
+    return [(O.F16, torch.float16), (O.BF16, torch.bfloat16), (O.F32, torch.float32), (O.F64, torch.float64)]
+
+
+def test_axpy_and_one_term_kinetic_energy_match_torch_for_all_dtype_pairs():
+    """The exact references of tests/test_gpu_kick_paths.py and tests/test_gpu_kinetic_dtypes.py, pinned against torch
+    itself: nbo_axpy == `a + b * s` (result dtype and every value, 4096 elements, three scalars that are not fp32
+    numbers) and nbo_kinetic_energy == `(0.5 * masses * (velocities ** 2).sum(dim=-1)).sum()` on inputs with a single
+    nonzero mass (one term: no summation order), for all 16 dtype pairs of {f16, bf16, f32, f64}, 2-D and 3-D."""
+    import torch
+    dts = _pin_dtypes()
+    code_of = {t: c for c, t in dts}
+    rng = np.random.default_rng(11)
+    n = 4096
+    for ca, ta in dts:
+        for cb, tb in dts:
+            a = torch.from_numpy(rng.standard_normal(n) * 0.05).to(ta)
+            b = torch.from_numpy(rng.standard_normal(n) * 3.0).to(tb)
+            a64, b64 = O.as_f64(a.double().numpy()), O.as_f64(b.double().numpy())
+            for s in (0.005, 0.0123, 0.01 / 3):
+                want = a + b * s
+                out = np.empty(n)
+                code = O.lib().nbo_axpy(n, ca, O._dp(a64), cb, O._dp(b64), s, O._dp(out))
+                assert code == code_of[want.dtype], (ta, tb, code, want.dtype)
+                assert np.array_equal(out, want.double().numpy()), (ta, tb, s, int((out != want.double().numpy()).sum()))
+            # kinetic energy: velocities typed `ta`, masses typed `tb`
+            for d in (2, 3):
+                nk = 300
+                vel = torch.from_numpy(rng.standard_normal((nk, d)) * 0.3).to(ta)
+                v64 = O.as_f64(vel.double().numpy())
+                for k in (0, 17, nk - 1):
+                    m = np.zeros(nk)
+                    m[k] = 0.5 + rng.random()
+                    mass = torch.from_numpy(m).to(tb)
+                    want = (0.5 * mass * (vel ** 2).sum(dim=-1)).sum().item()
+                    got = O.lib().nbo_kinetic_energy(nk, d, ca, O._dp(v64), cb, O._dp(O.as_f64(mass.double().numpy())))
+                    assert got == want, (ta, tb, d, k, got, want)

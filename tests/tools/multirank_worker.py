@@ -21,6 +21,34 @@ from nbody_cosmological_simulation_amd import _native as N, galaxy, runtime
 
 dev = torch.device("cuda", 0)
 out = {}
+trace = {}                     # rank 0: per-step x, v, a of a step() loop and of run(k) (tests/test_gpu_kick_paths.py)
+TRACE_CASES, TRACE_STEPS = ("f64", "f32", "int8_big", "f64_onesided"), 3
+_CODE = {torch.float16: 0, torch.bfloat16: 1, torch.float32: 2, torch.float64: 3}
+
+
+def grab(sim, key):
+    codes = []
+    for part, t in (("x", sim.positions), ("v", sim.velocities), ("a", sim.accelerations)):
+        trace[f"{key}/{part}"] = t.detach().cpu().double().numpy()
+        codes.append(_CODE[t.dtype])
+    return codes
+
+
+def step_trace(name, make):
+    """A step() loop with the state read after every step, then run(k) from the same start: what rank 0 saw."""
+    sim = make()
+    codes, paths = [grab(sim, f"{name}/0")], []
+    for i in range(TRACE_STEPS):
+        sim.step()
+        paths.append(sim.step_path_name())
+        codes.append(grab(sim, f"{name}/{i + 1}"))
+    sim.close()
+    sim = make()
+    sim.run(TRACE_STEPS)
+    paths.append(sim.step_path_name())
+    codes.append(grab(sim, f"{name}/run"))
+    sim.close()
+    return {"codes": codes, "paths": paths, "dt": sim.dt}
 cases = (("f64", 9000, nb.PrecisionMode.FLOAT64), ("f32", 9000, nb.PrecisionMode.FLOAT32),
          ("f16", 9000, nb.PrecisionMode.FLOAT16), ("int4", 3000, nb.PrecisionMode.INT4_SIM),
          ("int8_big", 9000, nb.PrecisionMode.INT8_SIM), ("f64_onesided", 3000, nb.PrecisionMode.FLOAT64))
@@ -51,6 +79,9 @@ for name, n, mode in cases:
                                    np.array_equal(single.velocities.cpu().numpy(), multi.velocities.cpu().numpy())),
                  "hash": hashlib.sha256(multi.positions.cpu().numpy().tobytes() + multi.velocities.cpu().numpy().tobytes()).hexdigest()}
     single.close(); multi.close()
+    if name in TRACE_CASES:
+        # slow stars: the kick a dt/2 must be of the size of v, or an FMA kick could not be told from a two-rounding one
+        out[name]["trace"] = step_trace(name, lambda: nb.GalaxySimulation(pos, vel * 1e-3, mass, precision_mode=mode, device=dev))
 assert N.lib().nb_comm_ready() == world and N.lib().nb_comm_p2p_state() == 2
 label = runtime.allreduce_label()
 gathered = [None] * world
@@ -60,4 +91,5 @@ dist.barrier()
 dist.destroy_process_group()
 if rank == 0:
     json.dump({"ranks": gathered, "label": label}, open(os.environ["NB_OUT"], "w"))
+    np.savez(os.environ["NB_OUT"] + ".trace.npz", **trace)
     print("MULTIRANK-OK", world)
