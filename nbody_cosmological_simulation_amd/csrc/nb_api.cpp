@@ -478,7 +478,7 @@ int nb_compute_accelerations(nb_sim *s)
     if (!s) return fail(NB_ERR_INVALID, "null handle");
     s->spec_open = false;          // state / parameters change: the speculative next positions are void
     DeviceGuard guard(s->cfg.device);
-    return force_eval(s, false);
+    return force_eval(s, EvalRequest{});
 }
 
 int nb_kick_drift(nb_sim *s)

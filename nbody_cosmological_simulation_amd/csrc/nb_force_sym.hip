@@ -34,7 +34,7 @@ template <> __device__ __forceinline__ float axpy_rn<float>(float a, float b, fl
 
 // x, y, (z), mass factor as padded component arrays; with KICK the opening half of a step rides
 // along: v += a*(dt/2); x += v*dt (simulation.py:132,135, separate mul/add roundings like torch).
-// KICK = 2 additionally applies the closing half kick of the PREVIOUS step first (simulation.py:141),
+// KICK = NB_PACK_CLOSE_OPEN additionally applies the closing half kick of the PREVIOUS step first (simulation.py:141),
 // which the multi-GPU / force-quantising paths cannot fuse into their reduction.
 // spread != 0 (potential energy with uniform masses, where no mass factor silences the padding): padding particle
 // number k sits at pad * (1 + k) along x, so pad-pad pairs are as far apart as pad-real ones.
@@ -52,7 +52,7 @@ pack_kernel(T *__restrict__ pos, T *__restrict__ vel, const T *__restrict__ acc,
             T x = pos[idx];
             if (KICK) {
                 T v = vel[idx];
-                if (KICK == 2) v = axpy_rn<T>(v, acc[idx], half_dt);
+                if (KICK == NB_PACK_CLOSE_OPEN) v = axpy_rn<T>(v, acc[idx], half_dt);
                 v = axpy_rn<T>(v, acc[idx], half_dt);
                 x = axpy_rn<T>(x, v, dt);
                 vel[idx] = v;
@@ -129,23 +129,23 @@ reduce_sym_kernel(const double *__restrict__ rowslab, const T *__restrict__ cols
                 continue;
             }
             const T a = (T)(t * scale);            // scale = mass factor of the uniform kernel, else 1
-            // do_kick bit 2: the velocities hold the previous step's CLOSING state and the positions were taken from its
+            // NB_KICK_OPEN_ON_READ: the velocities hold the previous step's CLOSING state and the positions were taken from its
             // speculative drift -- this step's opening kick is applied here, with the accelerations being replaced
-            const T a_prev = (do_kick & 4) ? acc[idx] : (T)0;
+            const T a_prev = (do_kick & NB_KICK_OPEN_ON_READ) ? acc[idx] : (T)0;
             acc[idx] = a;
             if (mm_part) {
                 const double ad = (double)a;
                 mm_lo = (ad != ad || mm_lo != mm_lo) ? __builtin_nan("") : (ad < mm_lo ? ad : mm_lo);
                 mm_hi = (ad != ad || mm_hi != mm_hi) ? __builtin_nan("") : (ad > mm_hi ? ad : mm_hi);
             }
-            const int kmode = do_kick & 3;
-            if (kmode != 0) {
+            const int kmode = do_kick & NB_KICK_MODE_MASK;
+            if (kmode != NB_KICK_NONE) {
                 T v = vel[idx];
-                if (do_kick & 4) v = axpy_rn<T>(v, a_prev, half_dt);
+                if (do_kick & NB_KICK_OPEN_ON_READ) v = axpy_rn<T>(v, a_prev, half_dt);
                 v = axpy_rn<T>(v, a, half_dt);                                   // closing kick
-                if (kmode == 1) {
+                if (kmode == NB_KICK_CLOSE) {
                     vel[idx] = v;
-                } else if (kmode == 2) {
+                } else if (kmode == NB_KICK_CLOSE_OPEN) {
                     // ... then the next step's opening kick + drift and its repack (what pack_kernel<KICK=1>
                     // would do in a launch of its own; mass factors and padding in `packed` do not change)
                     v = axpy_rn<T>(v, a, half_dt);
@@ -178,24 +178,10 @@ reduce_sym_kernel(const double *__restrict__ rowslab, const T *__restrict__ cols
 }
 
 __global__ void __launch_bounds__(NB_BLOCK)
-finish_sums64_kernel(const double *__restrict__ sums64, double scale, float *__restrict__ acc, float *__restrict__ vel,
-                     float *__restrict__ pos, float *__restrict__ packed, long long count, int np, int dim, int mode,
-                     float half_dt, float dt)
+finish_sums64_kernel(const double *__restrict__ sums64, double scale, float *__restrict__ acc, long long count)
 {
     const long long e = (long long)blockIdx.x * NB_BLOCK + threadIdx.x;
-    if (e >= count) return;
-    const float a = (float)(sums64[e] * scale);
-    acc[e] = a;
-    if (mode == 1) {
-        vel[e] = axpy_rn<float>(vel[e], a, half_dt);
-    } else if (mode == 2) {
-        float v = axpy_rn<float>(vel[e], a, half_dt);
-        v = axpy_rn<float>(v, a, half_dt);
-        const float x = axpy_rn<float>(pos[e], v, dt);
-        vel[e] = v;
-        pos[e] = x;
-        if (packed) packed[(size_t)(e % dim) * np + e / dim] = x;
-    }
+    if (e < count) acc[e] = (float)(sums64[e] * scale);
 }
 
 // Potential energy over the same tile-pair work list: sum over unordered pairs of
@@ -394,7 +380,7 @@ hipError_t nb_launch_pack(void *pos, void *vel, const void *acc, const void *mas
     hipLaunchKernelGGL((pack_kernel<TT, DD, KK>), dim3(grid), dim3(NB_BLOCK), 0, st, (TT *)pos, (TT *)vel, \
                        (const TT *)acc, (const TT *)mass, (TT *)packed, n, np, (TT)half_dt, (TT)dt, (TT)gfac, (TT)pad, \
                        p_begin, p_end, spread_pad)
-#define NB_PACK_K(TT, DD) do { if (kick == 2) NB_PACK(TT, DD, 2); else if (kick == 1) NB_PACK(TT, DD, 1); else NB_PACK(TT, DD, 0); } while (0)
+#define NB_PACK_K(TT, DD) do { if (kick == NB_PACK_CLOSE_OPEN) NB_PACK(TT, DD, 2); else if (kick == NB_PACK_OPEN) NB_PACK(TT, DD, 1); else NB_PACK(TT, DD, 0); } while (0)
     if (dim != 2 && dim != 3) return hipErrorInvalidValue;
     if (is_f64) { if (dim == 2) NB_PACK_K(double, 2); else NB_PACK_K(double, 3); }
     else        { if (dim == 2) NB_PACK_K(float, 2); else NB_PACK_K(float, 3); }
@@ -480,12 +466,10 @@ hipError_t nb_launch_potential_sym(const void *packed, const SymWork *work, int 
     return hipGetLastError();
 }
 
-hipError_t nb_launch_finish_sums64(const double *sums64, double scale, float *acc, float *vel, float *pos, float *packed,
-                                   int n, int np, int dim, int mode, double half_dt, double dt, hipStream_t st)
+hipError_t nb_launch_finish_sums64(const double *sums64, double scale, float *acc, int64_t count, hipStream_t st)
 {
-    const long long count = (long long)n * dim;
     hipLaunchKernelGGL(finish_sums64_kernel, dim3((unsigned)((count + NB_BLOCK - 1) / NB_BLOCK)), dim3(NB_BLOCK), 0, st, sums64,
-                       scale, acc, vel, pos, packed, count, np, dim, mode, (float)half_dt, (float)dt);
+                       scale, acc, (long long)count);
     return hipGetLastError();
 }
 
@@ -495,7 +479,7 @@ hipError_t nb_launch_reduce_sym(const double *rowslab, const void *colslab, cons
                                 int do_kick, void *pos, void *packed, double dt, hipStream_t st, int p_begin, int p_end,
                                 double *sums64, double *mm_part, void *pos_next)
 {
-    if ((do_kick & 3) == 3 && !pos_next) return hipErrorInvalidValue;
+    if ((do_kick & NB_KICK_MODE_MASK) == NB_KICK_CLOSE_SPEC && !pos_next) return hipErrorInvalidValue;
     if (p_end < 0 || p_end > n) p_end = n;
     if (p_end <= p_begin) return hipSuccess;
     const int blk0 = p_begin / 64;                  // chunk boundaries are tile boundaries (multiples of 64)

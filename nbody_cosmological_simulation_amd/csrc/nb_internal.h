@@ -106,16 +106,31 @@ struct SymWork {
     int s_count;       // rotation steps to run (64 = a full tile-vs-tile sweep)
 };
 
-// pack positions + mass factors into padded component arrays; kick != 0 fuses the opening
+// Leapfrog work a launch fuses behind the accelerations `a` it has just finished (simulation.py:132-141; separate multiply
+// and add roundings like torch).  The step-path strings print the numbers ("reduce_sym:3|4").
+enum NbKick {
+    NB_KICK_NONE = 0,        // accelerations only
+    NB_KICK_CLOSE = 1,       // closing half kick of this step: v += a dt/2
+    NB_KICK_CLOSE_OPEN = 2,  // ... then the next step's opening kick + drift: v += a dt/2; x += v dt (+ repack of x)
+    NB_KICK_CLOSE_SPEC = 3   // closing kick; the positions the next step WOULD drift to go to a second buffer (+ `packed`)
+};
+constexpr int NB_KICK_MODE_MASK = 3;
+// flag beside a mode: the positions came from such a speculative drift and the velocities still hold the previous closing
+// state -- this step's opening kick (with the accelerations being replaced) comes first.  Only reduce_sym and the
+// one-launch small-system step take NB_KICK_CLOSE_SPEC and the flag.
+constexpr int NB_KICK_OPEN_ON_READ = 4;
+// nb_launch_pack, before it packs: nothing, this step's opening kick + drift, or the previous step's closing kick first
+enum NbPackKick { NB_PACK_NONE = 0, NB_PACK_OPEN = 1, NB_PACK_CLOSE_OPEN = 2 };
+
 // Optional timing events of a launch: attached to the dispatch itself (hipExtLaunchKernelGGL), so the
 // kernel's own start / end timestamps are taken without barrier packets around it on the stream.
 struct NbKernelEvents {
     hipEvent_t start = nullptr, stop = nullptr;
 };
 
-// kick + drift of a step (simulation.py:132,135)
+// pack positions + mass factors into padded component arrays
 hipError_t nb_launch_pack(void *pos, void *vel, const void *acc, const void *mass, void *packed, int n, int np,
-                          int dim, int is_f64, int kick, double half_dt, double dt, double gfac, int f32_pairs,
+                          int dim, int is_f64, int kick /* NbPackKick */, double half_dt, double dt, double gfac, int f32_pairs,
                           hipStream_t st, int p_begin = 0, int p_end = -1 /* packed entries [p_begin, p_end); -1 = np */,
                           int spread_pad = 0 /* padding particles at distinct far positions (uniform-mass potential energy) */);
 hipError_t nb_launch_force_sym_f64(const double *packed, const SymWork *work, int nwork, double *rowslab,
@@ -132,16 +147,14 @@ hipError_t nb_launch_final_sum(const double *part, int count, double *out, hipSt
 hipError_t nb_launch_reduce_sym(const double *rowslab, const void *colslab, const int *row_slot0,
                                 const int *row_nslots, const int *col_upto, int tile_b, int n,
                                 int np, int dim, int is_f64, double scale, void *acc, void *vel, double half_dt,
-                                int do_kick /* 1: closing kick, 2: + next opening kick + drift + repack, 3: closing kick + the next step's positions speculatively into pos_next / packed; | 4: this step's opening kick on read */,
+                                int do_kick /* NbKick | NB_KICK_OPEN_ON_READ */,
                                 void *pos, void *packed, double dt, hipStream_t st,
                                 int p_begin = 0, int p_end = -1 /* particles [p_begin, p_end); -1 = n */,
                                 double *sums64 = nullptr /* instead of acc / kicks: the unscaled, unrounded fp64 sums */,
                                 double *mm_part = nullptr /* per-workgroup {min, max} of the forces written (whole-range launches) */,
-                                void *pos_next = nullptr /* do_kick mode 3 */);
-// fp32 state, multi-GPU: acc = (float)(sums64 * scale) after the ranks' fp64 sums were added, + the kicks of mode
-// (0 none, 1 closing, 2 closing + next opening + drift + repack) -- the tail of reduce_sym_kernel, after the exchange
-hipError_t nb_launch_finish_sums64(const double *sums64, double scale, float *acc, float *vel, float *pos, float *packed,
-                                   int n, int np, int dim, int mode, double half_dt, double dt, hipStream_t st);
+                                void *pos_next = nullptr /* NB_KICK_CLOSE_SPEC */);
+// fp32 state, multi-GPU: acc = (float)(sums64 * scale) after the ranks' fp64 sums were added (force quantisation follows)
+hipError_t nb_launch_finish_sums64(const double *sums64, double scale, float *acc, int64_t count, hipStream_t st);
 
 // ---- kernel launchers (implemented in the .hip files) --------------------------------------
 // T = storage/accumulation type of the state (float or double); pa_f32 != 0 selects fp32
@@ -188,7 +201,7 @@ hipError_t nb_launch_d2bins(const float *pos, int n, int dim, float eps2, const 
 
 // reduce the S partial slabs in fixed order; optionally fuse the closing half kick
 hipError_t nb_launch_reduce(const double *partial, int nchunks, int64_t count, void *acc, int is_f64,
-                            void *vel, double half_dt, int do_kick /* 1: closing kick, 2: + next opening kick + drift */,
+                            void *vel, double half_dt, int do_kick /* NB_KICK_NONE / CLOSE / CLOSE_OPEN */,
                             void *pos, double dt, hipStream_t st);
 hipError_t nb_launch_axpy(void *y, const void *x, double scalar, int64_t count, int is_f64, hipStream_t st);
 hipError_t nb_launch_kick_drift(void *pos, void *vel, const void *acc, double half_dt, double dt,
@@ -201,7 +214,7 @@ hipError_t nb_launch_convert(const void *in, int in_dt, void *out, int out_dt, i
 // linear force grid (quantization.py:74-88) applied in place inside the step, fp32, with bin output
 hipError_t nb_launch_force_quant_step(float *acc, int64_t count, int levels, double *mn_mx, double *partials,
                                       int16_t *bins, float *vel, float *pos, double half_dt, double dt,
-                                      int kick /* 0 none, 1 closing kick, 2 + next opening kick + drift */,
+                                      int kick /* NB_KICK_NONE / CLOSE / CLOSE_OPEN */,
                                       float *packed /* symmetric path: also repack the new positions, else null */,
                                       int np, int dim, hipStream_t st);
 hipError_t nb_launch_force_quant_bins(const float *in, float *out, int64_t count, int levels, const double *mn_mx,
@@ -259,9 +272,9 @@ size_t nb_p2p_capacity();           // bytes of the shared input buffer (0: not 
 void *nb_p2p_data();                // this rank's shared input buffer (device pointer)
 int nb_p2p_nranks();
 int nb_p2p_device();
-// leapfrog work fused behind the sum: mode 1 closing half kick, 2 + the next step's opening kick + drift (+ repack)
+// leapfrog work fused behind the sum
 struct NbP2PKick {
-    int mode, dim, np;
+    int mode /* NB_KICK_NONE / CLOSE / CLOSE_OPEN */, dim, np;
     int f64_to_f32;                // the vector holds fp64 sums, the result (and vel / pos / packed) is fp32:
     double scale;                  //   result = (float)(sum * scale)
     void *vel, *pos, *packed;      // storage type of the force vector; packed may be null (one-sided kernels)
@@ -290,7 +303,7 @@ int nb_small_lanes(int n);
 int nb_small_block(int n);          // threads per workgroup of the one-launch step at this size (256 or 512)
 hipError_t nb_launch_small_step(const void *pos_in, void *pos_out, void *vel, void *acc, const void *mass, int n, int dim,
                                 int is_f64, int hook, double G, double eps2, double half_dt, double dt,
-                                int do_kick /* 0 force only, 1 + closing kick, 2 + next opening kick + drift into pos_out, 3 closing kick + speculative next positions into pos_out; | 4 opening kick on read */,
+                                int do_kick /* NbKick | NB_KICK_OPEN_ON_READ */,
                                 int lanes /* 16 / 32 / 64 lanes per target */, hipStream_t st,
                                 const GridTables *tab = nullptr /* HOOK_GRID: this evaluation's tables */,
                                 double *part = nullptr /* INT8 / INT4: 2 n doubles, per-target min / max of the forces */,
@@ -298,4 +311,4 @@ hipError_t nb_launch_small_step(const void *pos_in, void *pos_out, void *vel, vo
 // second half of nb_launch_force_quant_step with caller-provided min / max partials (nblocks pairs of doubles)
 hipError_t nb_launch_force_quant_finish(float *acc, int64_t count, int levels, const double *partials, int nblocks,
                                         double *mn_mx, int16_t *bins, float *vel, float *pos, double half_dt, double dt,
-                                        int kick, hipStream_t st, float *packed = nullptr, int np = 0, int dim = 1);
+                                        int kick /* as above */, hipStream_t st, float *packed = nullptr, int np = 0, int dim = 1);

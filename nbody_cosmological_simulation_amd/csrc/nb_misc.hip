@@ -34,9 +34,9 @@ reduce_kernel(const double *__restrict__ partial, int nchunks, int64_t count, T 
         for (int c = 1; c < nchunks; ++c) s += partial[(size_t)c * count + idx];
         const T a = (T)s;
         acc[idx] = a;
-        if (do_kick == 1) {
+        if (do_kick == NB_KICK_CLOSE) {
             vel[idx] = axpy1(vel[idx], a, half_dt);
-        } else if (do_kick == 2) {
+        } else if (do_kick == NB_KICK_CLOSE_OPEN) {
             // closing kick of this step and the opening kick + drift of the next one (simulation.py:141,
             // then :132,:135 of the following step()): the same operations the separate launches perform
             T v = axpy1(vel[idx], a, half_dt);
@@ -279,9 +279,9 @@ force_quant_finish_kernel(float *__restrict__ acc, int64_t count, int levels, co
         if (!passthrough) a = lin_quant<float>(a, mn, range, lm1, &b);
         acc[idx] = a;
         if (bins) bins[idx] = (int16_t)b;
-        if (kick) {
+        if (kick != NB_KICK_NONE) {
             float v = axpy1(vel[idx], a, half_dt);
-            if (kick == 2) {
+            if (kick == NB_KICK_CLOSE_OPEN) {
                 v = axpy1(v, a, half_dt);
                 const float x = axpy1(pos[idx], v, dt);
                 pos[idx] = x;

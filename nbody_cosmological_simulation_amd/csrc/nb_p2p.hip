@@ -57,8 +57,7 @@ struct P2PArgs {
     long long units;            // 8-byte units (one double / two floats)
     long long timeout_ticks;    // of wall_clock64()
     size_t data_off, out_off;
-    // leapfrog work fused behind the sum (what reduce_sym_kernel fuses on one GPU): 0 none, 1 closing half kick,
-    // 2 closing kick + the next step's opening kick + drift (+ repack of the pair-symmetric kernel's positions)
+    // leapfrog work fused behind the sum (what reduce_sym_kernel fuses on one GPU): NB_KICK_NONE / CLOSE / CLOSE_OPEN
     int kick, dim, np;
     void *vel, *pos, *packed;
     double half_dt, dt;
@@ -156,7 +155,7 @@ __device__ __forceinline__ void p2p_leapfrog(const P2PArgs &a, long long e, T f)
     const T h = (T)a.half_dt;
     if (sizeof(T) == 8) v = (T)__dadd_rn((double)v, __dmul_rn((double)f, (double)h));
     else v = (T)__fadd_rn((float)v, __fmul_rn((float)f, (float)h));
-    if (a.kick == 2) {
+    if (a.kick == NB_KICK_CLOSE_OPEN) {
         T *pos = (T *)a.pos;
         T x;
         if (sizeof(T) == 8) {
@@ -178,11 +177,11 @@ __device__ __forceinline__ void p2p_finish(const P2PArgs &a, u64 *__restrict__ d
     if (F64 && a.f64_to_f32) {
         const float f = (float)(__longlong_as_double((long long)s) * a.scale);
         ((float *)dst)[u] = f;
-        if (a.kick) p2p_leapfrog<float>(a, u, f);
+        if (a.kick != NB_KICK_NONE) p2p_leapfrog<float>(a, u, f);
         return;
     }
     dst[u] = s;
-    if (a.kick) {
+    if (a.kick != NB_KICK_NONE) {
         if (F64) {
             p2p_leapfrog<double>(a, u, __longlong_as_double((long long)s));
         } else {
@@ -336,11 +335,11 @@ size_t nb_p2p_handle_bytes() { return sizeof(hipIpcMemHandle_t); }
 
 static void p2p_set_kick(P2PArgs &a, const NbP2PKick *k)
 {
-    a.kick = 0; a.dim = 1; a.np = 0; a.vel = a.pos = a.packed = nullptr; a.half_dt = a.dt = 0.0;
+    a.kick = NB_KICK_NONE; a.dim = 1; a.np = 0; a.vel = a.pos = a.packed = nullptr; a.half_dt = a.dt = 0.0;
     a.f64_to_f32 = 0; a.scale = 1.0;
     if (k) {
         a.f64_to_f32 = k->f64_to_f32; a.scale = k->scale;
-        if (k->mode) {
+        if (k->mode != NB_KICK_NONE) {
             a.kick = k->mode; a.dim = k->dim; a.np = k->np; a.vel = k->vel; a.pos = k->pos; a.packed = k->packed;
             a.half_dt = k->half_dt; a.dt = k->dt;
         }

@@ -1,6 +1,7 @@
 // nb_state.h -- host-side state shared by the translation units behind the C-ABI (include/nbody_amd.h):
 //   nb_api.cpp    entry points of a simulation handle + argument checks, state upload / download
 //   nb_step.cpp   kernel selection and the sequencing of one force evaluation / leapfrog step / energy evaluation
+//                 (EvalRequest in, EvalResult out: the handle below holds only what outlives a call)
 //   nb_comm.cpp   process communicator: RCCL (resolved with dlopen) and the direct xGMI all-reduce (nb_p2p.hip)
 //   nb_hooks.cpp  handle-less tensor-level hooks (quantization.py module functions) and diagnostics on caller tensors
 // Host orchestration only: no arithmetic of the hot path runs on the host; without a HIP device every entry fails.
@@ -134,7 +135,6 @@ struct nb_sim {
     std::string path_part[3];            // opening kick + drift of the first step, interior steps, closing kick of the last
     std::string step_path = "none";
     bool path_open_kd = false;           // the note of the opening part came from nb_kick_drift (nb_kick keeps it)
-    char kick_site[64] = "";             // force_eval -> step_run: the launch that applied this evaluation's kick(s)
     ForceGeom geom{};
     // pair-symmetric path (nb_force_sym.hip): device mirror of the host plan (nb_plan.h)
     struct SymPlan {
@@ -150,8 +150,6 @@ struct nb_sim {
     bool spec_open = false;              // ... pos_alt holds the positions the NEXT step drifts to (computed with spec_dt by
     double spec_dt = 0.0;                //     the last step of the previous nb_step); dropped by every entry that writes state
     int spec_kind = 0;                   //     1: left by the small-system kernel, 2: by reduce_sym_kernel (sym.packed holds them too)
-    bool req_spec_next = false;          // step_run -> force_eval: last step of a call, leave the next step's positions
-    bool req_open_on_read = false;       // step_run -> force_eval: this step started from speculative positions
     double *small_part = nullptr;        // ... INT8 / INT4: per-target min / max of the forces (2 n doubles)
     void *gen_scalars = nullptr;         // generic (dtype-faithful) path: device scalars of one evaluation
     bool last_generic = false;           // the last force evaluation ran on the generic path (no threshold tables)
@@ -160,7 +158,6 @@ struct nb_sim {
     void *metrics_scratch = nullptr;     // nb_metrics work arrays (allocated on first use)
     size_t metrics_cap = 0;
     unsigned long long *bin_out = nullptr;   // nb_quant_bin_sums: {s1[n], s2[n], counters[2]} while a read-out runs
-    bool bins_active = false;            // force_eval launches the BINS instantiations of the grid-mode kernels
     NbKnobs knobs;                       // environment knobs, read once in nb_create
     ncclComm_t comm = nullptr;
     unsigned comm_generation = 0;        // ProcComm::generation this handle attached to
@@ -193,6 +190,17 @@ inline bool force_quant_mode(const nb_config &c)
     return c.mode == NB_INT8_SIM || c.mode == NB_INT4_SIM ||
            (c.mode == NB_CUSTOM && (c.flags & NB_FLAG_CUSTOM_FORCEQ));
 }
+// hook the pair loop compiles in for a precision mode (quantization.py:21-71)
+inline int mode_hook(int mode)
+{
+    return mode == NB_BFLOAT16 ? HOOK_BF16 : mode == NB_FLOAT16 ? HOOK_F16 : grid_mode(mode) ? HOOK_GRID : HOOK_NONE;
+}
+// positions, velocities and accelerations are typed like the storage (every step after the first few promotions)
+inline bool settled(const nb_sim *s)
+{
+    const int sdt = s->is_f64 ? NB_F64 : NB_F32;
+    return s->logical[0] == sdt && s->logical[1] == sdt && s->logical[3] == sdt;
+}
 int acc_logical_dtype(const nb_sim *s);
 
 // ---- nb_comm.cpp ---------------------------------------------------------------------------------------------------
@@ -213,11 +221,22 @@ int onesided_r(int n, const NbKnobs &knobs);
 // source chunks of the one-sided kernels (force, potential energy, generic) for this rank's j-range
 ForceGeom onesided_geometry(const nb_config &c, const NbKnobs &knobs);
 void compute_geometry(nb_sim *s);
-// one evaluation of simulation.py:74-118; optionally followed by the closing half kick (:141)
-// defer_kick: the caller will apply the closing half kick itself (fused into the next step's
-// opening launch) when this evaluation cannot fuse it into its reduction.
-int force_eval(nb_sim *s, bool do_kick, bool packed_ready = false, bool *defer_kick = nullptr,
-               bool *open_next = nullptr);
+// one evaluation of simulation.py:74-118 and the leapfrog work its launches can carry
+struct EvalRequest {
+    bool kick = false;          // follow the evaluation with the closing half kick (:141)
+    bool packed_ready = false;  // sym.packed already holds the current positions (no pack launch)
+    bool may_defer = false;     // a closing kick no launch here can carry may be left to the caller's next opening launch
+    bool open_next = false;     // with the kick: also the next step's opening kick + drift, where a launch can carry it
+    bool spec_next = false;     // last step of a call: leave the next step's positions speculatively (NB_KICK_CLOSE_SPEC)
+    bool open_on_read = false;  // this step started from such positions: its opening kick is still to be applied
+    bool bins = false;          // nb_quant_bin_sums: the BINS instantiations of the grid-mode kernels
+};
+struct EvalResult {
+    bool deferred = false;      // the closing kick is left to the caller
+    bool opened = false;        // the next step's opening kick + drift is done (pair-symmetric path: repacked as well)
+    char site[64] = "";         // the launch that applied the kick(s), as the step path prints it; empty: none
+};
+int force_eval(nb_sim *s, EvalRequest rq, EvalResult *result = nullptr);
 // step-path notes (nb_step_path_name): `where` 0 opening kick + drift of the first step, 1 interior steps, 2 closing
 // kick of the last step; a site already noted for the same part is not repeated
 void path_clear(nb_sim *s);

@@ -1,5 +1,8 @@
 // nb_step.cpp -- kernel selection and sequencing of the hot path behind the C-ABI (include/nbody_amd.h):
-//   force_eval   one evaluation of GalaxySimulation._compute_accelerations (reference simulation.py:74-118)
+//   force_eval   one evaluation of GalaxySimulation._compute_accelerations (reference simulation.py:74-118), in phases:
+//                resolve_eval (dtypes, kernel, carriers: decided once), grid_prepare, launch_pairs, reduce_and_exchange,
+//                force_quant_finish, fall-back kick; force_eval_generic for the dtype-faithful kernel.  Asked for with
+//                an EvalRequest, answers with an EvalResult (nb_state.h); kicks are named by NbKick (nb_internal.h)
 //   step_run     kick-drift-kick leapfrog steps (simulation.py:120-143), launches fused as far as each path allows
 //   energy_eval  kinetic / potential energy (simulation.py:170-192)
 //   bin_sums_eval  the quant-bin read-out of the production grid-mode pair loops (nb_quant_bin_sums)
@@ -121,11 +124,14 @@ int acc_logical_dtype(const nb_sim *s)
 
 namespace {
 
-// the launch that applied the kick(s) of this evaluation: "<site>:<mode>" (+ "|4": opening kick applied on read)
-void site_set(nb_sim *s, const char *site, int mode, const char *tags = "")
+inline int kick_mode(bool kick, bool open) { return kick ? (open ? NB_KICK_CLOSE_OPEN : NB_KICK_CLOSE) : NB_KICK_NONE; }
+inline int allow_fast(const nb_sim *s) { return s->knobs.no_grid_fast ? 0 : 1; }
+
+// the launch that applied the kick(s) of an evaluation: "<site>:<mode>" (+ "|4": opening kick applied on read)
+void site_set(EvalResult *res, const char *site, int mode, const char *tags = "")
 {
-    if (!(mode & 3)) { s->kick_site[0] = 0; return; }
-    snprintf(s->kick_site, sizeof s->kick_site, "%s:%d%s%s", site, mode & 3, (mode & 4) ? "|4" : "", tags);
+    if (!(mode & NB_KICK_MODE_MASK)) { res->site[0] = 0; return; }
+    snprintf(res->site, sizeof res->site, "%s:%d%s%s", site, mode & NB_KICK_MODE_MASK, (mode & NB_KICK_OPEN_ON_READ) ? "|4" : "", tags);
 }
 
 int prof_begin(nb_sim *s, int *slot, bool record = true)
@@ -180,14 +186,67 @@ bool use_generic(const nb_sim *s)
     return grid_mode(c.mode) && is_half(s->logical[0]);                      // grid over a half tensor
 }
 
-int force_eval_generic(nb_sim *s, bool do_kick, bool *defer_kick, bool *open_next)
+// ---- one force evaluation: what resolve_eval decides once, and the two things its phases hand on ----------------
+struct Eval {
+    bool shard = false;        // NB_FLAG_NO_COMM shard of a larger run: no collective, no force quantisation, cannot step
+    bool fq = false;           // quantize_force follows the sum
+    bool multi = false;        // the sum goes through a collective (comm_active)
+    bool generic = false;      // use_generic: everything below is for the tuned kernels only
+    int hook = HOOK_NONE;      // hook of the pair loop; fp64 storage: -1 unless a cast mode rounds fp64 positions
+    int pair_dt = NB_F32;      // fp32 storage: NB_F32, or the half type of half-typed positions (first evaluation);
+                               // fp64 storage: -1 for fp64 pairs, else the narrower type the positions still have
+    float eps2 = 0.0f;         // softening rounded to the pair dtype
+    bool used_sym = false, sym_uniform = false;   // pair-symmetric kernel; its uniform-mass variant (mass factor in `scale`)
+    bool red_mm = false, x64 = false;   // the reduction hands quantize_force its min / max partials; the ranks exchange fp64 sums
+    double scale = 1.0;        // launch_reduce: factor applied to the finished sums
+    bool kicked = false;       // ... and by whoever applied it: the closing kick is done
+};
+
+Eval resolve_eval(const nb_sim *s)
+{
+    const nb_config &c = s->cfg;
+    Eval e;
+    e.shard = (c.flags & NB_FLAG_NO_COMM) && c.nranks > 1;
+    e.fq = force_quant_mode(c) && !e.shard;
+    e.multi = comm_active(s);
+    e.generic = use_generic(s);
+    if (e.generic) return e;
+    if (s->is_f64) {
+        // (grid modes on fp64 storage and cast modes before the positions are promoted take the generic path)
+        e.hook = (c.mode == NB_FLOAT64) ? -1 : mode_hook(c.mode);
+        e.pair_dt = (e.hook < 0 && s->logical[0] != NB_F64) ? s->logical[0] : -1;   // NB_F32 / F16 / BF16
+        const bool sym_default_shape = s->sym.r == 4 || s->sym.r == 2;   // HOOK_F32PAIR instantiations
+        e.used_sym = s->sym.enabled && e.hook < 0 && (e.pair_dt < 0 || (e.pair_dt == NB_F32 && sym_default_shape));
+        e.sym_uniform = s->mass_uniform;
+    } else {
+        e.hook = mode_hook(c.mode);
+        e.pair_dt = is_half(s->logical[0]) ? s->logical[0] : NB_F32;
+        e.used_sym = s->sym.enabled && e.pair_dt == NB_F32;
+        // grid LUT already carries G and the uniform grid kernel applies the common mass itself (reduce scale stays 1)
+        e.sym_uniform = s->mass_uniform && e.hook != HOOK_GRID;
+    }
+    e.eps2 = (float)round_dt(e.pair_dt >= 0 ? e.pair_dt : NB_F32, c.softening_sq);
+    // INT8 / INT4 on one GPU, pair-symmetric path: the reduction hands quantize_force its min / max partials (one pair
+    // per workgroup of 64 particles), saving the min/max launch (4.6 of 50 us per step at N = 6000; NbTuning: up to 65 536)
+    e.red_mm = e.fq && e.used_sym && !e.multi && !s->is_f64 && (c.n + 63) / 64 <= g_tune.red_mm_max_blocks && !s->knobs.no_red_mm;
+    // multi-GPU INT8 / INT4 on the pair-symmetric path: the ranks exchange the UNROUNDED fp64 sums and round once,
+    // (float)(sum * scale), exactly where the single-GPU reduction rounds, so the all-reduce itself adds no fp32
+    // rounding of its own before quantize_force snaps the forces to their grid (a last-bit difference there is what
+    // flips a force bin: measured against the single-GPU run after five steps at N = 9000 INT8, two ranks: positions
+    // 1.2e-8 with the fp64 exchange, 1.2e-6 -- a flipped bin -- with fp32 partials).  Twice the bytes, so only where a
+    // grid follows: the other fp32 modes differ across rank counts at the 1e-7 of their in-kernel fp32 running sums
+    // either way (measured: identical with both exchanges).
+    e.x64 = e.multi && e.used_sym && !s->is_f64 && e.fq && !s->knobs.no_x64;
+    return e;
+}
+
+int force_eval_generic(nb_sim *s, const EvalRequest &rq, const Eval &e, EvalResult *res)
 {
     const nb_config &c = s->cfg;
     const int64_t cnt = nd(s);
-    const bool no_comm = (c.flags & NB_FLAG_NO_COMM) != 0;
-    const bool multi = comm_active(s);
-    if (multi && !s->comm) return fail(NB_ERR_COMM, "nranks > 1 but nb_comm_init was not called");
-    const bool fq = force_quant_mode(c) && !(no_comm && c.nranks > 1);
+    if (rq.open_on_read) return fail(NB_ERR_INVALID, "internal: speculative positions on the generic path");
+    // a call defers only with settled dtypes outside the grid modes, and neither takes the generic path
+    if (rq.may_defer) return fail(NB_ERR_INVALID, "internal: a deferred kick on the generic path");
     const int L = mode_levels(c);
     if (grid_mode(c.mode) && L < 2) return fail(NB_ERR_INVALID, "grid levels must be >= 2 (got %d)", L);
     const int A = acc_logical_dtype(s);
@@ -198,9 +257,9 @@ int force_eval_generic(nb_sim *s, bool do_kick, bool *defer_kick, bool *open_nex
                                    L, c.G, c.softening_sq, s->gen_scalars, s->acc, A, s->stream));
     s->last_kernel = "generic_force_kernel";
     s->last_generic = true;
-    if (multi)
+    if (e.multi)
         if (int rc = comm_allreduce_sum(s, s->acc, (size_t)cnt, s->is_f64)) return rc;
-    if (fq) {
+    if (e.fq) {
         // quantize_force on a tensor of dtype A (quantization.py:74-88): linear grid over its global min / max
         const bool a64 = (A == NB_F64);
         if (a64 == s->is_f64) {
@@ -214,285 +273,237 @@ int force_eval_generic(nb_sim *s, bool do_kick, bool *defer_kick, bool *open_nex
             HIPCHK(nb_launch_convert(s->staging, NB_F32, s->acc, NB_F64, cnt, s->stream));
         }
     }
-    if (open_next) *open_next = false;
-    s->kick_site[0] = 0;
-    if (do_kick) {
-        if (defer_kick) *defer_kick = true;
-        else {
-            HIPCHK(nb_launch_axpy(s->vel, s->acc, c.dt / 2, cnt, s->is_f64, s->stream));
-            snprintf(s->kick_site, sizeof s->kick_site, "axpy");
-        }
+    if (rq.kick) {
+        HIPCHK(nb_launch_axpy(s->vel, s->acc, c.dt / 2, cnt, s->is_f64, s->stream));
+        snprintf(res->site, sizeof res->site, "axpy");
     }
     s->logical[3] = A;
     s->have_acc = true;
     return NB_OK;
 }
 
-}  // namespace
-
-// one evaluation of simulation.py:74-118; optionally followed by the closing half kick (:141)
-// defer_kick: the caller will apply the closing half kick itself (fused into the next step's
-// opening launch) when this evaluation cannot fuse it into its reduction.
-int force_eval(nb_sim *s, bool do_kick, bool packed_ready, bool *defer_kick, bool *open_next)
+// This evaluation's grid (fp32 storage, HOOK_GRID): the maximum of r2 over all pairs, then the threshold / factor tables.
+// tab->r2max_bits is 0 here: zeroed at creation, put back by grid_tables_kernel after each use.
+//   tracked   after a seeding evaluation: the farthest pair of the predecessor gives the lower bound, so two launches
+//             (filter, scan + tables) replace the search (exact either way, nb_force.hip).  Single GPU or every rank
+//             redundantly; not for comm-less shards, whose first evaluation is their only one.
+//   small     the one-launch step's all-pairs pass; up to small_fuse_tables_max_n the same launch builds the tables
+//             (measured, INT4: N = 1024 22.5 -> 18.6 us per step; N = 3000 30.8 vs 31.7: there the fused kernel's
+//             arrival counter and longer source chunks cost more than the launch)
+//   seeding   the pruned search (six launches, O(N) + candidates^2, no collective), else all pairs + max over the ranks
+//             (the small step's evaluations above the fused size as well: one GPU, so its own block is every source)
+int grid_prepare(nb_sim *s, const Eval &e, bool small)
 {
-    if (!s->have_pos || !s->have_mass) return fail(NB_ERR_INVALID, "positions and masses must be set first");
+    const nb_config &c = s->cfg;
+    const int L = mode_levels(c);
+    const float G = (float)c.G, min_val = 0.01f;
+    if (L > NB_MAX_LUT || L < 2) return fail(NB_ERR_UNSUPPORTED, "grid levels must be in [2, %d] on the fused path (got %d)", NB_MAX_LUT, L);
+    const bool track = !s->knobs.no_prune && !s->knobs.no_track && c.n > g_tune.track_min_n && !e.shard;
+    if (track && s->prune_seeded) {
+        HIPCHK(nb_launch_r2max_tracked((const float *)s->pos, c.n, c.dim, e.eps2, s->prune_cand, s->prune_idx, s->prune_state,
+                                       s->tab, L, G, min_val, allow_fast(s), s->stream));
+        if (L > NB_LUT_MIN)      // multi-block tables: the scan left the maximum in tab->r2max_bits
+            HIPCHK(nb_launch_grid_tables(s->tab, L, G, e.eps2, min_val, nullptr, s->stream, allow_fast(s)));
+        return NB_OK;
+    }
+    if (small && L <= NB_LUT_MIN && c.n <= g_tune.small_fuse_tables_max_n && !s->knobs.no_small_fuse) {
+        HIPCHK(nb_launch_r2max_tables((const float *)s->pos, s->geom, c.dim, e.eps2, s->tab, L, G, min_val, allow_fast(s),
+                                      s->stream));
+        return NB_OK;
+    }
+    const bool prune = !small && !s->knobs.no_prune && (c.n > g_tune.prune_min_n || track);
+    if (prune) {
+        HIPCHK(nb_launch_r2max_pruned((const float *)s->pos, c.n, c.dim, e.eps2, s->prune_cand, s->prune_rho, s->prune_state,
+                                      s->tab, s->stream));
+    } else {
+        ForceGeom gmax = s->geom;
+        const bool scan_all = e.shard || (e.multi && g_pc.direct_only);
+        if (scan_all) {   // a comm-less shard (and a rank without RCCL's max) scans every source itself
+            gmax.j_begin = 0;
+            gmax.j_end = c.n;
+            gmax.nchunks = (c.n + gmax.chunk_len - 1) / gmax.chunk_len;
+        }
+        HIPCHK(nb_launch_r2max((const float *)s->pos, gmax, c.dim, e.eps2, s->tab, s->stream));
+        if (e.multi && !scan_all)
+            if (int rc = comm_allreduce_max_u32(s, &s->tab->r2max_bits)) return rc;
+    }
+    HIPCHK(nb_launch_grid_tables(s->tab, L, G, e.eps2, min_val, prune ? s->prune_state : nullptr, s->stream, allow_fast(s)));
+    s->prune_seeded = prune;     // grid_tables_kernel seeded the tracked search from the pruned one's far pair
+    return NB_OK;
+}
+
+// the pair sweep: partial sums into the slabs of the pair-symmetric plan, or into the one-sided kernels' source chunks
+int launch_pairs(nb_sim *s, const EvalRequest &rq, const Eval &e)
+{
+    const nb_config &c = s->cfg;
+    const auto &sp = s->sym;
+    const bool grid = e.hook == HOOK_GRID;
+    const int L = grid ? mode_levels(c) : 0;
+    unsigned long long *bin_out = (rq.bins && grid) ? s->bin_out : nullptr;    // nb_quant_bin_sums: the same kernels, BINS = true
+    int slot;
+    if (!e.used_sym) {
+        if (int rc = prof_begin(s, &slot)) return rc;
+        if (s->is_f64)
+            HIPCHK(nb_launch_force_f64((const double *)s->pos, (const double *)s->mass, s->partial, s->geom, c.dim, e.pair_dt,
+                                       e.hook, c.G, c.softening_sq, e.eps2, s->stream));
+        else
+            HIPCHK(nb_launch_force_f32((const float *)s->pos, (const float *)s->mass, s->partial, s->geom, c.dim, e.hook,
+                                       e.pair_dt, (float)c.G, e.eps2, s->tab, L, s->stream, bin_out));
+        s->last_kernel = s->is_f64 ? "force_f64_kernel" : "force_f32_kernel";
+        return prof_end(s, slot);
+    }
+    const int pa_f32 = s->is_f64 && e.pair_dt == NB_F32;
+    if (!rq.packed_ready) {
+        // the packed mass factor carries G, except in grid modes, whose table already does (simulation.py:101)
+        const double gfac = s->is_f64 ? c.G : (grid ? 1.0 : (double)(float)c.G);
+        HIPCHK(nb_launch_pack(s->pos, s->vel, s->acc, s->mass, sp.packed, c.n, sp.np, c.dim, s->is_f64, NB_PACK_NONE, 0.0, 0.0,
+                              gfac, pa_f32, s->stream));
+    }
+    if (int rc = prof_begin(s, &slot, false)) return rc;
+    if (s->is_f64) {
+        HIPCHK(nb_launch_force_sym_f64((const double *)sp.packed, sp.work, sp.nwork, sp.rowslab, (double *)sp.colslab, sp.np,
+                                       c.dim, sp.r, s->mass_uniform, pa_f32, c.softening_sq, s->stream, prof_events(s, slot),
+                                       sp.rowsplit ? 1 : 0));
+        s->last_kernel = "force_sym_kernel<double";
+        return NB_OK;
+    }
+    // grid modes on the R = 2 tiling (N < 20 480: a few hundred short work items, one wave per SIMD): a step is bound by
+    // the LATENCY of a sweep, and the general-mass kernel's four independent scalar pairs per rotation step hide the
+    // log / exp chains better than the packed uniform kernel does (measured INT8 / INT4 us per step, uniform vs general:
+    // N = 6000 61.7 / 55.1 vs 48.3 / 47.6, N = 12 000 100 vs 88; N = 20 000 equal; N = 65 536 0.83 vs 1.24 ms)
+    const bool uniform = grid ? (s->mass_uniform && sp.r != 2) : e.sym_uniform;
+    if (bin_out)
+        HIPCHK(nb_launch_force_sym_f32_bins((const float *)sp.packed, sp.work, sp.nwork, sp.rowslab, (float *)sp.colslab, sp.np,
+                                            c.dim, sp.r, uniform, e.eps2, s->tab, (float)c.G, (float)s->mass_value, L, bin_out,
+                                            c.n, s->stream));
+    else
+        HIPCHK(nb_launch_force_sym_f32((const float *)sp.packed, sp.work, sp.nwork, sp.rowslab, (float *)sp.colslab, sp.np,
+                                       c.dim, sp.r, uniform, e.hook, e.eps2, s->tab, (float)c.G, (float)s->mass_value, L,
+                                       s->stream, prof_events(s, slot)));
+    s->last_kernel = "force_sym_kernel<float";
+    return NB_OK;
+}
+
+// the reduction of the partial sums with every kick it can carry (none before a collective), then the sum over the
+// ranks through one of three carriers: the direct xGMI all-reduce (the reduction writes the buffer the peers read), the
+// exchange of fp64 sums (Eval::x64), or the in-place RCCL all-reduce of `acc`
+int reduce_and_exchange(nb_sim *s, const EvalRequest &rq, Eval &e, EvalResult *res)
+{
     const nb_config &c = s->cfg;
     const int64_t cnt = nd(s);
-    const double half_dt = c.dt / 2;
-    const bool fq = force_quant_mode(c) && !((c.flags & NB_FLAG_NO_COMM) && c.nranks > 1);
-    const bool no_comm = (c.flags & NB_FLAG_NO_COMM) != 0;
-    // collectives run whenever a communicator exists (a 1-rank communicator exercises the same
-    // RCCL calls on a single GPU) and must exist when the sources are really sharded
-    const bool multi = (c.nranks > 1 && !no_comm) || s->comm != nullptr;
-    if (multi && !s->comm) return fail(NB_ERR_COMM, "nranks > 1 but nb_comm_init was not called");
-    if (multi)
-        if (int rc = comm_check(s)) return rc;
-    if (no_comm && c.nranks > 1 && do_kick) return fail(NB_ERR_INVALID, "NB_FLAG_NO_COMM handles cannot step");
-    if (use_generic(s)) {
-        if (s->req_open_on_read) return fail(NB_ERR_INVALID, "internal: speculative positions on the generic path");
-        return force_eval_generic(s, do_kick, defer_kick, open_next);
-    }
-    s->last_generic = false;
-    s->kick_site[0] = 0;
-    int slot;
-    bool used_sym = false, sym_uniform = false;
-
-    if (s->is_f64) {
-        // (grid modes on fp64 storage and cast modes before the positions are promoted took the generic path above)
-        int qhook = -1;                      // fp64 positions under a cast mode: hook output is fp32
-        if (c.mode == NB_FLOAT32) qhook = HOOK_NONE;
-        else if (c.mode == NB_BFLOAT16) qhook = HOOK_BF16;
-        else if (c.mode == NB_FLOAT16) qhook = HOOK_F16;
-        const int pair_dt = (qhook < 0 && s->logical[0] != NB_F64) ? s->logical[0] : -1;   // NB_F32 / F16 / BF16
-        const int pa_f32 = (pair_dt == NB_F32);
-        const bool sym_default_shape = s->sym.r == 4 || s->sym.r == 2;   // HOOK_F32PAIR instantiations
-        used_sym = s->sym.enabled && qhook < 0 && (pair_dt < 0 || (pa_f32 && sym_default_shape));
-        sym_uniform = s->mass_uniform;
-        if (used_sym) {
-            const auto &sp = s->sym;
-            if (!packed_ready)
-                HIPCHK(nb_launch_pack(s->pos, s->vel, s->acc, s->mass, sp.packed, c.n, sp.np, c.dim, 1, 0, 0.0, 0.0,
-                                      c.G, pa_f32, s->stream));
-            if (int rc = prof_begin(s, &slot, false)) return rc;
-            HIPCHK(nb_launch_force_sym_f64((const double *)sp.packed, sp.work, sp.nwork, sp.rowslab,
-                                           (double *)sp.colslab, sp.np, c.dim, sp.r, s->mass_uniform, pa_f32,
-                                           c.softening_sq, s->stream, prof_events(s, slot), sp.rowsplit ? 1 : 0));
-            s->last_kernel = "force_sym_kernel<double";
-        } else {
-            if (int rc = prof_begin(s, &slot)) return rc;
-            HIPCHK(nb_launch_force_f64((const double *)s->pos, (const double *)s->mass, s->partial, s->geom, c.dim,
-                                       pair_dt, qhook, c.G, c.softening_sq,
-                                       (float)round_dt(pair_dt >= 0 ? pair_dt : NB_F32, c.softening_sq), s->stream));
-            s->last_kernel = "force_f64_kernel";
-            if (int rc = prof_end(s, slot)) return rc;
-        }
-    } else {
-        int hook = HOOK_NONE;
-        if (c.mode == NB_BFLOAT16) hook = HOOK_BF16;
-        else if (c.mode == NB_FLOAT16) hook = HOOK_F16;
-        else if (grid_mode(c.mode)) hook = HOOK_GRID;
-        const int pa = is_half(s->logical[0]) ? s->logical[0] : NB_F32;   // half-typed positions (first evaluation)
-        const float eps2 = (float)round_dt(pa, c.softening_sq);
-        if (hook == HOOK_GRID) {
-            const int L = mode_levels(c);
-            if (L > NB_MAX_LUT || L < 2)
-                return fail(NB_ERR_UNSUPPORTED, "grid levels must be in [2, %d] on the fused path (got %d)",
-                            NB_MAX_LUT, L);
-            // tab->r2max_bits is 0 here: zeroed at creation, put back by grid_tables_kernel after each use.
-            // Small systems scan all pairs in one launch; the pruned search (six launches, O(N) + candidates^2)
-            // pays off above that.
-            // Tracked search: the farthest pair of the previous evaluation gives this one's lower bound, so two launches
-            // (filter, scan + tables) replace six + one (round 3; exact either way, nb_force.hip).  Single GPU or every rank
-            // redundantly; not for comm-less shards, whose first evaluation is their only one.
-            const bool track = !s->knobs.no_prune && !s->knobs.no_track && c.n > g_tune.track_min_n && !(no_comm && c.nranks > 1);
-            const bool prune = !s->knobs.no_prune && (c.n > g_tune.prune_min_n || track);
-            if (track && s->prune_seeded) {
-                HIPCHK(nb_launch_r2max_tracked((const float *)s->pos, c.n, c.dim, eps2, s->prune_cand, s->prune_idx, s->prune_state,
-                                               s->tab, L, (float)c.G, 0.01f, s->knobs.no_grid_fast ? 0 : 1, s->stream));
-                if (L > NB_LUT_MIN)      // multi-block tables: the scan left the maximum in tab->r2max_bits
-                    HIPCHK(nb_launch_grid_tables(s->tab, L, (float)c.G, eps2, 0.01f, nullptr, s->stream,
-                                                 s->knobs.no_grid_fast ? 0 : 1));
-            } else {
-            if (prune) {
-                // every rank finds the global maximum itself: O(N) + (outer candidates)^2, no collective
-                HIPCHK(nb_launch_r2max_pruned((const float *)s->pos, c.n, c.dim, eps2, s->prune_cand, s->prune_rho,
-                                              s->prune_state, s->tab, s->stream));
-            } else {
-                ForceGeom gmax = s->geom;
-                const bool scan_all = (no_comm && c.nranks > 1) || (multi && g_pc.direct_only);
-                if (scan_all) {   // a comm-less shard (and a rank without RCCL's max) scans every source itself
-                    gmax.j_begin = 0;
-                    gmax.j_end = c.n;
-                    gmax.nchunks = (c.n + gmax.chunk_len - 1) / gmax.chunk_len;
-                }
-                HIPCHK(nb_launch_r2max((const float *)s->pos, gmax, c.dim, eps2, s->tab, s->stream));
-                if (multi && !scan_all)   // NB_FLAG_NO_COMM shards see only their own block's maximum
-                    if (int rc = comm_allreduce_max_u32(s, &s->tab->r2max_bits)) return rc;
-            }
-            HIPCHK(nb_launch_grid_tables(s->tab, L, (float)c.G, eps2, 0.01f, prune ? s->prune_state : nullptr,
-                                         s->stream, s->knobs.no_grid_fast ? 0 : 1));
-            s->prune_seeded = prune;     // grid_tables_kernel seeded the tracked search from the pruned one's far pair
-            }
-        }
-        used_sym = s->sym.enabled && pa == NB_F32;
-        if (used_sym) {
-            const auto &sp = s->sym;
-            // grid LUT already carries G (simulation.py:101), so the packed factor is the bare mass there
-            sym_uniform = s->mass_uniform && hook != HOOK_GRID;
-            const double gfac = (hook == HOOK_GRID) ? 1.0 : (double)(float)c.G;
-            if (!packed_ready)
-                HIPCHK(nb_launch_pack(s->pos, s->vel, s->acc, s->mass, sp.packed, c.n, sp.np, c.dim, 0, 0, 0.0, 0.0,
-                                      gfac, 0, s->stream));
-            if (int rc = prof_begin(s, &slot, false)) return rc;
-            // grid modes: the uniform kernel applies the common mass itself (reduce scale stays 1).  On the R = 2 tiling
-            // (N < 20 480: a few hundred short work items, one wave per SIMD) a step is bound by the LATENCY of a sweep,
-            // and the general-mass kernel's four independent scalar pairs per rotation step hide the log / exp chains
-            // better than the packed uniform kernel does (measured INT8 / INT4 us per step, uniform vs general:
-            // N = 6000 61.7 / 55.1 vs 48.3 / 47.6, N = 12 000 100 vs 88; N = 20 000 equal; N = 65 536 0.83 vs 1.24 ms)
-            const bool grid_uniform = s->mass_uniform && sp.r != 2;
-            if (s->bins_active && hook == HOOK_GRID)     // nb_quant_bin_sums: the same kernels, BINS = true
-                HIPCHK(nb_launch_force_sym_f32_bins((const float *)sp.packed, sp.work, sp.nwork, sp.rowslab,
-                                                    (float *)sp.colslab, sp.np, c.dim, sp.r, grid_uniform, eps2, s->tab,
-                                                    (float)c.G, (float)s->mass_value, mode_levels(c), s->bin_out, c.n,
-                                                    s->stream));
-            else
-            HIPCHK(nb_launch_force_sym_f32((const float *)sp.packed, sp.work, sp.nwork, sp.rowslab,
-                                           (float *)sp.colslab, sp.np, c.dim, sp.r,
-                                           hook == HOOK_GRID ? grid_uniform : sym_uniform, hook, eps2, s->tab,
-                                           (float)c.G, (float)s->mass_value, hook == HOOK_GRID ? mode_levels(c) : 0,
-                                           s->stream, prof_events(s, slot)));
-            s->last_kernel = "force_sym_kernel<float";
-        } else {
-            if (int rc = prof_begin(s, &slot)) return rc;
-            HIPCHK(nb_launch_force_f32((const float *)s->pos, (const float *)s->mass, s->partial, s->geom, c.dim, hook,
-                                       pa, (float)c.G, eps2, s->tab, hook == HOOK_GRID ? mode_levels(c) : 0, s->stream,
-                                       (s->bins_active && hook == HOOK_GRID) ? s->bin_out : nullptr));
-            s->last_kernel = "force_f32_kernel";
-            if (int rc = prof_end(s, slot)) return rc;
-        }
-    }
-
-    const bool fuse_kick = do_kick && !multi && !fq;
-    const bool want_open = do_kick && open_next && *open_next;   // nb_step asks: may this evaluation open the next step?
-    bool opened = false;
-    double x64_scale = 1.0;
-    // INT8 / INT4 on one GPU, pair-symmetric path: the reduction hands quantize_force its min / max partials (one pair
-    // per workgroup of 64 particles), saving the min/max launch (4.6 of 50 us per step at N = 6000)
-    const int red_blocks = (c.n + 63) / 64;
-    // (up to N = 32 768: beyond, every workgroup of the finish launch would fold thousands of partials -- measured
-    // neutral to slightly negative at N = 65 536, where the launch it saves is 0.5 % of the step anyway)
-    const bool red_mm = fq && used_sym && !multi && !s->is_f64 && red_blocks <= g_tune.red_mm_max_blocks && !s->knobs.no_red_mm;
-    // multi-GPU: the rank's partial force vector goes straight into the buffer the peers read (direct xGMI
-    // all-reduce), or into `acc` for the in-place RCCL all-reduce
-    // multi-GPU INT8 / INT4 on the pair-symmetric path: the ranks exchange the UNROUNDED fp64 sums and round once,
-    // (float)(sum * scale), exactly where the single-GPU reduction rounds, so the all-reduce itself adds no fp32
-    // rounding of its own before quantize_force snaps the forces to their grid (a last-bit difference there is what
-    // flips a force bin: measured against the single-GPU run after five steps at N = 9000 INT8, two ranks: positions
-    // 1.2e-8 with the fp64 exchange, 1.2e-6 -- a flipped bin -- with fp32 partials).  Twice the bytes, so only where a
-    // grid follows: the other fp32 modes differ across rank counts at the 1e-7 of their in-kernel fp32 running sums
-    // either way (measured: identical with both exchanges).
-    const bool x64 = multi && used_sym && !s->is_f64 && fq && !s->knobs.no_x64;
-    bool p2p = multi && (x64 ? p2p_use_x64(s, cnt) : p2p_use(s, cnt));
+    const bool p2p = e.multi && (e.x64 ? p2p_use_x64(s, cnt) : p2p_use(s, cnt));
     void *red_out = p2p ? nb_p2p_data() : s->acc;
-    if (x64 && !p2p && !s->sums64) HIPCHK(hipMalloc((void **)&s->sums64, (size_t)cnt * sizeof(double)));
-    double *sums64 = x64 ? (p2p ? (double *)nb_p2p_data() : s->sums64) : nullptr;
+    if (e.x64 && !p2p && !s->sums64) HIPCHK(hipMalloc((void **)&s->sums64, (size_t)cnt * sizeof(double)));
+    double *sums64 = e.x64 ? (p2p ? (double *)nb_p2p_data() : s->sums64) : nullptr;
     if (p2p)
         if (int rc = p2p_claim_buffer(s)) return rc;
-    if (used_sym) {
+    const bool fuse_kick = rq.kick && !e.multi && !e.fq;
+    // inside nb_step the reduction also opens the next step (one launch fewer per step, which is what small systems
+    // are bound by) and, on the pair-symmetric path, repacks its positions
+    int kmode = kick_mode(fuse_kick, rq.open_next);
+    if (rq.open_on_read && !(fuse_kick && e.used_sym))
+        return fail(NB_ERR_INVALID, "internal: a step started from speculative positions needs the kick-fusing pair-symmetric reduction");
+    if (!e.used_sym) {
+        HIPCHK(nb_launch_reduce(s->partial, s->geom.nchunks, cnt, red_out, s->is_f64, s->vel, c.dt / 2, kmode, s->pos, c.dt,
+                                s->stream));
+        site_set(res, "reduce", kmode);
+    } else {
         const auto &sp = s->sym;
         // uniform-mass kernels leave out the mass factor: G*m in T arithmetic (fp32: (float)G * m)
-        double scale = 1.0;
-        if (sym_uniform) scale = s->is_f64 ? c.G * s->mass_value : (double)((float)c.G * (float)s->mass_value);
-        // inside nb_step the reduction also opens the next step and repacks its positions
-        const bool open = fuse_kick && want_open;
-        int kmode = open ? 2 : (fuse_kick ? 1 : 0);
-        // the last step of a native call leaves the NEXT step's drifted positions in pos_alt and `packed` (mode 3); a
-        // call that starts from them applies its opening kick on read (bit 2) -- a Python loop of step() then costs
-        // force + reduction per tick, no pack launch (see step_run)
-        const bool spec = fuse_kick && !open && s->req_spec_next && !grid_mode(c.mode);
+        if (e.sym_uniform) e.scale = s->is_f64 ? c.G * s->mass_value : (double)((float)c.G * (float)s->mass_value);
+        // the last step of a native call leaves the NEXT step's drifted positions in pos_alt and `packed`; a call that
+        // starts from them applies its opening kick on read -- a Python loop of step() then costs force + reduction
+        // per tick, no pack launch (see step_run)
+        const bool spec = kmode == NB_KICK_CLOSE && rq.spec_next && !grid_mode(c.mode);
         if (spec) {
             if (!s->pos_alt) HIPCHK(hipMalloc(&s->pos_alt, (size_t)cnt * (s->is_f64 ? 8 : 4)));
-            kmode = 3;
+            kmode = NB_KICK_CLOSE_SPEC;
         }
-        if (s->req_open_on_read) {
-            if (!fuse_kick) return fail(NB_ERR_INVALID, "internal: a step started from speculative positions cannot fuse its kicks");
-            kmode |= 4;
-        }
-        HIPCHK(nb_launch_reduce_sym(sp.rowslab, sp.colslab, sp.row_slot0, sp.row_nslots, sp.col_upto,
-                                    sp.tile_b, c.n, sp.np, c.dim, s->is_f64, scale, red_out, s->vel, half_dt,
-                                    kmode, s->pos, sp.packed, c.dt, s->stream, 0, -1, sums64,
-                                    red_mm ? s->scalars + 8 : nullptr, s->pos_alt));
-        site_set(s, "reduce_sym", kmode);
+        if (rq.open_on_read) kmode |= NB_KICK_OPEN_ON_READ;
+        HIPCHK(nb_launch_reduce_sym(sp.rowslab, sp.colslab, sp.row_slot0, sp.row_nslots, sp.col_upto, sp.tile_b, c.n, sp.np,
+                                    c.dim, s->is_f64, e.scale, red_out, s->vel, c.dt / 2, kmode, s->pos, sp.packed, c.dt,
+                                    s->stream, 0, -1, sums64, e.red_mm ? s->scalars + 8 : nullptr, s->pos_alt));
+        site_set(res, "reduce_sym", kmode);
         if (spec) { s->spec_open = true; s->spec_kind = 2; s->spec_dt = c.dt; }
-        x64_scale = scale;
-        opened = open;
-    } else {
-        if (s->req_open_on_read) return fail(NB_ERR_INVALID, "internal: speculative positions on the one-sided path");
-        // one-sided path inside nb_step: the reduction can also open the next step (one launch fewer per step,
-        // which is what small systems are bound by)
-        const bool open = fuse_kick && want_open;
-        HIPCHK(nb_launch_reduce(s->partial, s->geom.nchunks, cnt, red_out, s->is_f64, s->vel, half_dt,
-                                open ? 2 : (fuse_kick ? 1 : 0), s->pos, c.dt, s->stream));
-        site_set(s, "reduce", open ? 2 : (fuse_kick ? 1 : 0));
-        opened = open;
     }
-    bool kicked = fuse_kick;
+    e.kicked = fuse_kick;
+    res->opened = (kmode & NB_KICK_MODE_MASK) == NB_KICK_CLOSE_OPEN;
     if (p2p) {
         // every rank holds every summed element inside this kernel: the kicks (and, inside nb_step, the next step's
         // opening kick + drift + repack) ride along as they do in the single-GPU reduction -- no pack launch
         NbP2PKick kk{};
-        kk.f64_to_f32 = x64 ? 1 : 0;
-        kk.scale = x64_scale;
-        if (do_kick && !fq && !s->knobs.no_p2p_kick) {
-            const bool open = want_open;
-            kk.mode = open ? 2 : 1;
-            kk.dim = c.dim; kk.np = used_sym ? s->sym.np : 0;
-            kk.vel = s->vel; kk.pos = s->pos; kk.packed = used_sym ? (void *)s->sym.packed : nullptr;
-            kk.half_dt = half_dt; kk.dt = c.dt;
-            kicked = true;
-            opened = open;
+        kk.scale = e.scale;
+        if (e.x64) kk.f64_to_f32 = 1;     // (force quantisation follows: its finish launch carries the kicks)
+        else if (rq.kick && !e.fq && !s->knobs.no_p2p_kick) {
+            kk.mode = kick_mode(true, rq.open_next);
+            kk.dim = c.dim; kk.np = e.used_sym ? s->sym.np : 0;
+            kk.vel = s->vel; kk.pos = s->pos; kk.packed = e.used_sym ? (void *)s->sym.packed : nullptr;
+            kk.half_dt = c.dt / 2; kk.dt = c.dt;
+            e.kicked = true;
+            res->opened = rq.open_next;
         }
-        HIPCHK(nb_p2p_allreduce(s->acc, (size_t)cnt, s->is_f64 || x64, p2p_step_timeout_s(), s->stream, &kk));
-        if (kk.mode) site_set(s, "p2p", kk.mode, x64 ? ",x64" : "");
+        HIPCHK(nb_p2p_allreduce(s->acc, (size_t)cnt, s->is_f64 || e.x64, p2p_step_timeout_s(), s->stream, &kk));
+        if (kk.mode != NB_KICK_NONE) site_set(res, "p2p", kk.mode);
         s->used_p2p = true;
-    } else if (multi && x64) {
+    } else if (e.x64) {
         if (int rc = comm_allreduce_sum(s, s->sums64, (size_t)cnt, true)) return rc;
-        const bool fin_kick = do_kick && !fq;
-        const bool open = fin_kick && want_open;
-        HIPCHK(nb_launch_finish_sums64(s->sums64, x64_scale, (float *)s->acc, (float *)s->vel, (float *)s->pos,
-                                       (float *)s->sym.packed, c.n, s->sym.np, c.dim, fin_kick ? (open ? 2 : 1) : 0,
-                                       half_dt, c.dt, s->stream));
-        site_set(s, "sums64", fin_kick ? (open ? 2 : 1) : 0);
-        if (fin_kick) { kicked = true; opened = open; }
-    } else if (multi) {
+        HIPCHK(nb_launch_finish_sums64(s->sums64, e.scale, (float *)s->acc, cnt, s->stream));
+    } else if (e.multi) {
         if (int rc = comm_allreduce_sum(s, s->acc, (size_t)cnt, s->is_f64)) return rc;
     }
-    if (fq) {
-        // min/max of the summed forces, then quantisation with the closing kick (and, inside nb_step, the next
-        // step's opening kick + drift) in the same launch
-        const bool open = want_open;
-        if (red_mm)
-            HIPCHK(nb_launch_force_quant_finish((float *)s->acc, cnt, mode_levels(c), s->scalars + 8, red_blocks, s->scalars,
-                                                s->fbins, (float *)s->vel, (float *)s->pos, half_dt, c.dt,
-                                                do_kick ? (open ? 2 : 1) : 0, s->stream, (float *)s->sym.packed, s->sym.np,
-                                                c.dim));
-        else
-        HIPCHK(nb_launch_force_quant_step((float *)s->acc, cnt, mode_levels(c), s->scalars, s->scalars + 8, s->fbins,
-                                          (float *)s->vel, (float *)s->pos, half_dt, c.dt, do_kick ? (open ? 2 : 1) : 0,
-                                          used_sym ? (float *)s->sym.packed : nullptr, s->sym.np, c.dim, s->stream));
-        {
-            const int km = do_kick ? (open ? 2 : 1) : 0;
-            site_set(s, "fq_finish", km, (km == 2 && used_sym) ? (red_mm ? ",packed,red_mm" : ",packed") : (red_mm ? ",red_mm" : ""));
-        }
-        kicked = do_kick;
-        opened = open;
-    }
-    if (open_next) *open_next = opened;
-    if (do_kick && !kicked) {
-        if (defer_kick) *defer_kick = true;
+    return NB_OK;
+}
+
+// min / max of the summed forces, then quantisation with the closing kick (and, inside nb_step, the next step's
+// opening kick + drift) in the same launch
+int force_quant_finish(nb_sim *s, const EvalRequest &rq, Eval &e, EvalResult *res)
+{
+    const nb_config &c = s->cfg;
+    const int km = kick_mode(rq.kick, rq.open_next);
+    if (e.red_mm)
+        HIPCHK(nb_launch_force_quant_finish((float *)s->acc, nd(s), mode_levels(c), s->scalars + 8, (c.n + 63) / 64, s->scalars,
+                                            s->fbins, (float *)s->vel, (float *)s->pos, c.dt / 2, c.dt, km, s->stream,
+                                            (float *)s->sym.packed, s->sym.np, c.dim));
+    else
+        HIPCHK(nb_launch_force_quant_step((float *)s->acc, nd(s), mode_levels(c), s->scalars, s->scalars + 8, s->fbins,
+                                          (float *)s->vel, (float *)s->pos, c.dt / 2, c.dt, km,
+                                          e.used_sym ? (float *)s->sym.packed : nullptr, s->sym.np, c.dim, s->stream));
+    const bool packed = km == NB_KICK_CLOSE_OPEN && e.used_sym;
+    site_set(res, "fq_finish", km, packed ? (e.red_mm ? ",packed,red_mm" : ",packed") : (e.red_mm ? ",red_mm" : ""));
+    e.kicked = rq.kick;
+    res->opened = rq.open_next;
+    return NB_OK;
+}
+
+}  // namespace
+
+// one evaluation of simulation.py:74-118 and the leapfrog work the request asks for (EvalRequest / EvalResult, nb_state.h)
+int force_eval(nb_sim *s, EvalRequest rq, EvalResult *result)
+{
+    if (!s->have_pos || !s->have_mass) return fail(NB_ERR_INVALID, "positions and masses must be set first");
+    rq.open_next = rq.kick && rq.open_next;      // the next step is opened by the launch that closes this one
+    EvalResult unread;
+    EvalResult *res = result ? result : &unread;
+    *res = EvalResult{};
+    Eval e = resolve_eval(s);
+    if (e.multi && !s->comm) return fail(NB_ERR_COMM, "nranks > 1 but nb_comm_init was not called");
+    if (e.multi)
+        if (int rc = comm_check(s)) return rc;
+    if (e.shard && rq.kick) return fail(NB_ERR_INVALID, "NB_FLAG_NO_COMM handles cannot step");
+    if (e.generic) return force_eval_generic(s, rq, e, res);
+    s->last_generic = false;
+    if (e.hook == HOOK_GRID)
+        if (int rc = grid_prepare(s, e, false)) return rc;
+    if (int rc = launch_pairs(s, rq, e)) return rc;
+    if (int rc = reduce_and_exchange(s, rq, e, res)) return rc;
+    if (e.fq)
+        if (int rc = force_quant_finish(s, rq, e, res)) return rc;
+    if (rq.kick && !e.kicked) {
+        // no launch could carry the closing kick (RCCL all-reduce in between)
+        if (rq.may_defer) res->deferred = true;
         else {
-            HIPCHK(nb_launch_axpy(s->vel, s->acc, half_dt, cnt, s->is_f64, s->stream));
-            snprintf(s->kick_site, sizeof s->kick_site, "axpy");
+            HIPCHK(nb_launch_axpy(s->vel, s->acc, s->cfg.dt / 2, nd(s), s->is_f64, s->stream));
+            snprintf(res->site, sizeof res->site, "axpy");
         }
     }
     s->logical[3] = acc_logical_dtype(s);
@@ -518,29 +529,7 @@ bool small_ok(const nb_sim *s)
     // masses: fp32-typed masses in an fp64 run enter the fp64 product exactly (no rounding of their own); half-typed
     // masses round the product to the half type and stay on the tuned kernels
     const bool mass_ok = s->logical[2] == sdt || (s->is_f64 && s->logical[2] == NB_F32);
-    return s->logical[0] == sdt && s->logical[1] == sdt && mass_ok && s->logical[3] == sdt;
-}
-
-// this evaluation's grid on a small system: all-pairs max of r2 and the threshold / factor tables -- one launch for
-// both up to N = 2048 (measured, INT4: N = 1024 22.5 -> 18.6 us per step; N = 3000 30.8 vs 31.7: there the fused
-// kernel's arrival counter and longer source chunks cost more than the launch)
-int small_grid_tables(nb_sim *s)
-{
-    const nb_config &c = s->cfg;
-    const float eps2f = (float)c.softening_sq;
-    if (s->prune_seeded && !s->knobs.no_prune && !s->knobs.no_track && c.n > g_tune.track_min_n) {
-        // the first evaluation (tiled path) seeded the tracked search: filter + scan (+ tables) instead of an all-pairs pass
-        HIPCHK(nb_launch_r2max_tracked((const float *)s->pos, c.n, c.dim, eps2f, s->prune_cand, s->prune_idx, s->prune_state,
-                                       s->tab, mode_levels(c), (float)c.G, 0.01f, s->knobs.no_grid_fast ? 0 : 1, s->stream));
-    } else if (mode_levels(c) <= NB_LUT_MIN && c.n <= g_tune.small_fuse_tables_max_n && !s->knobs.no_small_fuse) {
-        HIPCHK(nb_launch_r2max_tables((const float *)s->pos, s->geom, c.dim, eps2f, s->tab, mode_levels(c), (float)c.G, 0.01f,
-                                      s->knobs.no_grid_fast ? 0 : 1, s->stream));
-    } else {
-        HIPCHK(nb_launch_r2max((const float *)s->pos, s->geom, c.dim, eps2f, s->tab, s->stream));
-        HIPCHK(nb_launch_grid_tables(s->tab, mode_levels(c), (float)c.G, eps2f, 0.01f, nullptr, s->stream,
-                                     s->knobs.no_grid_fast ? 0 : 1));
-    }
-    return NB_OK;
+    return settled(s) && mass_ok;
 }
 
 // the remaining `nsteps` steps of an nb_step call; `opened`: this step's opening kick + drift was already applied
@@ -549,13 +538,14 @@ int step_small(nb_sim *s, int nsteps, bool opened, bool first)
     const nb_config &c = s->cfg;
     const size_t el = s->is_f64 ? 8 : 4;
     const bool grid = grid_mode(c.mode);
-    const bool fq = force_quant_mode(c);
+    const Eval e = resolve_eval(s);
+    const bool fq = e.fq;
     if (!s->pos_alt) HIPCHK(hipMalloc(&s->pos_alt, (size_t)nd(s) * el));
     if (fq && !s->small_part) HIPCHK(hipMalloc((void **)&s->small_part, 2 * (size_t)c.n * sizeof(double)));
-    const int hook = grid ? HOOK_GRID : (c.mode == NB_BFLOAT16 ? HOOK_BF16 : (c.mode == NB_FLOAT16 ? HOOK_F16 : HOOK_NONE));
+    const int hook = mode_hook(c.mode);
     const int lanes = s->knobs.small_lanes ? s->knobs.small_lanes : nb_small_lanes(c.n);
     // A step() loop driven from Python is one nb_step(1) per tick: the last step of a call leaves the next step's
-    // drifted positions in pos_alt (kick mode 3); if nothing wrote state or dt since, this call takes them and applies
+    // drifted positions in pos_alt (NB_KICK_CLOSE_SPEC); if nothing wrote state or dt since, this call takes them and applies
     // its opening kick on read -- one launch per tick instead of two (FLOAT32 us per step() call: N = 1024 9.9 -> 5.6, N = 3000 12.6 -> 10.8;
     // profiles/r03_python_step_overhead.txt)
     const bool speculate = !grid && !fq && !s->knobs.no_spec;
@@ -571,24 +561,27 @@ int step_small(nb_sim *s, int nsteps, bool opened, bool first)
         }
     }
     s->spec_open = false;
+    EvalResult note;
     for (int t = 0; t < nsteps; ++t) {
         const bool last = (t + 1 == nsteps);
         if (grid)
-            if (int rc = small_grid_tables(s)) return rc;
+            if (int rc = grid_prepare(s, e, true)) return rc;
         // INT8 / INT4: the forces are snapped to their grid (and the kicks applied) by the finish launch
-        const int kick = fq ? 0 : ((last ? (speculate ? 3 : 1) : 2) | ((t == 0 && open_on_read) ? 4 : 0));
+        const int closing = kick_mode(true, !last);
+        const int kick = fq ? NB_KICK_NONE : ((last && speculate ? NB_KICK_CLOSE_SPEC : closing) |
+                                              ((t == 0 && open_on_read) ? NB_KICK_OPEN_ON_READ : 0));
         int slot;
         if (int rc = prof_begin(s, &slot)) return rc;
         HIPCHK(nb_launch_small_step(s->pos, s->pos_alt, s->vel, s->acc, s->mass, c.n, c.dim, s->is_f64, hook, c.G,
                                     c.softening_sq, c.dt / 2, c.dt, kick, lanes, s->stream, grid ? s->tab : nullptr,
                                     fq ? s->small_part : nullptr));
         if (int rc = prof_end(s, slot)) return rc;
-        site_set(s, fq ? "fq_finish" : "small", fq ? (last ? 1 : 2) : kick, fq ? ",small" : "");
-        path_note(s, last ? 2 : 1, s->kick_site);
+        site_set(&note, fq ? "fq_finish" : "small", fq ? closing : kick, fq ? ",small" : "");
+        path_note(s, last ? 2 : 1, note.site);
         if (fq)      // one min / max pair per workgroup of the force launch
             HIPCHK(nb_launch_force_quant_finish((float *)s->acc, nd(s), mode_levels(c), s->small_part,
                                                 (c.n + nb_small_block(c.n) / lanes - 1) / (nb_small_block(c.n) / lanes), s->scalars, s->fbins,
-                                                (float *)s->vel, (float *)s->pos, c.dt / 2, c.dt, last ? 1 : 2, s->stream));
+                                                (float *)s->vel, (float *)s->pos, c.dt / 2, c.dt, closing, s->stream));
         else if (!last)
             std::swap(s->pos, s->pos_alt);
     }
@@ -603,39 +596,33 @@ int step_small(nb_sim *s, int nsteps, bool opened, bool first)
 // `nsteps` leapfrog steps (simulation.py:120-143): v += a dt/2; x += v dt; a = force(x); v += a dt/2.
 int step_run(nb_sim *s, int nsteps)
 {
-    bool pending_close = false;     // closing kick of the previous step still to be applied
-    bool opened = false;            // the previous step's reduction already did this step's opening kick + drift
-    bool packed_by_prev = false;    // ... and repacked the positions for the symmetric kernel
+    EvalResult prev;                // what the previous step's evaluation left: .deferred, its closing kick; .opened: it did
+                                    // this step's opening kick + drift (and, on the symmetric path, the repack)
     bool open_on_read = false;      // this call starts from the previous call's speculative positions (tiled path)
     path_clear(s);
     for (int t = 0; t < nsteps; ++t) {
         // small systems with settled dtypes: one launch per step
-        if (!pending_close && small_ok(s)) return step_small(s, nsteps - t, opened, t == 0);
+        if (!prev.deferred && small_ok(s)) return step_small(s, nsteps - t, prev.opened, t == 0);
         if (t == 0 && s->spec_open && s->spec_kind == 2 && s->spec_dt == s->cfg.dt && s->sym.enabled && !comm_active(s) &&
-            !force_quant_mode(s->cfg) && !grid_mode(s->cfg.mode) && s->pos_alt) {
-            const int sd = s->is_f64 ? NB_F64 : NB_F32;
-            if (s->logical[0] == sd && s->logical[1] == sd && s->logical[3] == sd) {
-                std::swap(s->pos, s->pos_alt);        // positions after this step's drift; `packed` holds them as well
-                opened = packed_by_prev = open_on_read = true;
-                path_note(s, 0, "spec_read");
-            }
+            !force_quant_mode(s->cfg) && !grid_mode(s->cfg.mode) && s->pos_alt && settled(s)) {
+            std::swap(s->pos, s->pos_alt);        // positions after this step's drift; `packed` holds them as well
+            prev.opened = open_on_read = true;
+            path_note(s, 0, "spec_read");
         }
         s->spec_open = false;
         // opening kick + drift; on the pair-symmetric path the repack rides in the same launch
-        const int sdt = s->is_f64 ? NB_F64 : NB_F32;
-        const bool fuse_pack = s->sym.enabled && s->logical[0] == sdt && s->logical[1] == sdt &&
-                               s->logical[3] == sdt && !grid_mode(s->cfg.mode);
-        const bool uniform_dt = s->logical[0] == sdt && s->logical[1] == sdt && s->logical[3] == sdt;
-        if (opened) {
+        const bool uniform_dt = settled(s);
+        const bool fuse_pack = s->sym.enabled && uniform_dt && !grid_mode(s->cfg.mode);
+        if (prev.opened) {
             // nothing to launch: positions and velocities were advanced by the previous reduction
         } else if (fuse_pack) {
             HIPCHK(nb_launch_pack(s->pos, s->vel, s->acc, s->mass, s->sym.packed, s->cfg.n, s->sym.np, s->cfg.dim,
-                                  s->is_f64, pending_close ? 2 : 1, s->cfg.dt / 2, s->cfg.dt,
+                                  s->is_f64, prev.deferred ? NB_PACK_CLOSE_OPEN : NB_PACK_OPEN, s->cfg.dt / 2, s->cfg.dt,
                                   s->is_f64 ? s->cfg.G : (double)(float)s->cfg.G, 0, s->stream));
-            path_note(s, t == 0 ? 0 : 1, pending_close ? "pack:2" : "pack:1");
+            path_note(s, t == 0 ? 0 : 1, prev.deferred ? "pack:2" : "pack:1");
         } else {
             const char *site = "";
-            if (pending_close) {
+            if (prev.deferred) {
                 if (int rc = launch_plain_kick(s, false, &site)) return rc;
                 path_note(s, 1, site);
             }
@@ -644,21 +631,18 @@ int step_run(nb_sim *s, int nsteps)
         }
         // packed positions are current when this step's pack launch wrote them, or when the previous evaluation
         // opened this step on the symmetric path (its reduction / quantisation repacked them)
-        const bool packed_ready = opened ? packed_by_prev : fuse_pack;
-        pending_close = false;
+        EvalRequest rq;
+        rq.kick = true;
+        rq.packed_ready = prev.opened ? s->sym.enabled : fuse_pack;
         s->logical[1] = promote(s->logical[1], s->logical[3]);
         s->logical[0] = promote(s->logical[0], s->logical[1]);
-        // a closing kick that cannot ride in the reduction (RCCL all-reduce / force quantisation in
-        // between) is folded into the next step's opening launch when there is one
-        const bool may_defer = (t + 1 < nsteps) && fuse_pack;
-        opened = (t + 1 < nsteps) && uniform_dt;      // request; force_eval answers
-        s->req_open_on_read = (t == 0) && open_on_read;
-        s->req_spec_next = (t + 1 == nsteps) && uniform_dt && s->sym.enabled && !s->knobs.no_spec;
-        const int rc_eval = force_eval(s, true, packed_ready, may_defer ? &pending_close : nullptr, &opened);
-        s->req_open_on_read = s->req_spec_next = false;
-        if (rc_eval) return rc_eval;
-        path_note(s, t + 1 < nsteps ? 1 : 2, s->kick_site);      // (nothing when the closing kick was deferred)
-        packed_by_prev = opened && s->sym.enabled;
+        // a closing kick no launch of the evaluation can carry is folded into the next step's opening launch, if there is one
+        rq.may_defer = (t + 1 < nsteps) && fuse_pack;
+        rq.open_next = (t + 1 < nsteps) && uniform_dt;
+        rq.open_on_read = (t == 0) && open_on_read;
+        rq.spec_next = (t + 1 == nsteps) && uniform_dt && s->sym.enabled && !s->knobs.no_spec;
+        if (int rc = force_eval(s, rq, &prev)) return rc;
+        path_note(s, t + 1 < nsteps ? 1 : 2, prev.site);      // (nothing when the closing kick was deferred)
         s->logical[1] = promote(s->logical[1], s->logical[3]);
     }
     return NB_OK;
@@ -723,7 +707,7 @@ int energy_eval(nb_sim *s, double *kinetic, double *potential)
                      s->is_f64 ? "double" : "float", c.dim, pa_f32 ? 1 : 0, hp_x >= 0 ? dtype_name(hp_x) : "none",
                      narrow_mass ? ",mass=" : "", narrow_mass ? dtype_name(s->logical[2]) : "");
         }
-        if ((c.nranks > 1 && !(c.flags & NB_FLAG_NO_COMM)) || s->comm) {
+        if (comm_active(s)) {
             if (!s->comm) return fail(NB_ERR_COMM, "nranks > 1 but nb_comm_init was not called");
             if (int rc = comm_allreduce_sum(s, s->scalars + 3, 1, true)) return rc;
         }
@@ -774,16 +758,15 @@ int bin_sums_eval(nb_sim *s, int which, int64_t *sum_k, int64_t *sum_kw, double 
         // what step_small launches for one step, force only (do_kick = 0), forces into the staging buffer
         const int lanes = s->knobs.small_lanes ? s->knobs.small_lanes : nb_small_lanes(c.n);
         if (!s->pos_alt) HIPCHK(hipMalloc(&s->pos_alt, (size_t)nd(s) * 4));
-        if (int rc = small_grid_tables(s)) return rc;
+        if (int rc = grid_prepare(s, resolve_eval(s), true)) return rc;
         HIPCHK(nb_launch_small_step(s->pos, s->pos_alt, s->vel, s->staging, s->mass, c.n, c.dim, 0, HOOK_GRID, c.G, c.softening_sq,
-                                    c.dt / 2, c.dt, 0, lanes, s->stream, s->tab, nullptr, s->bin_out));
+                                    c.dt / 2, c.dt, NB_KICK_NONE, lanes, s->stream, s->tab, nullptr, s->bin_out));
         path = 3;
         shape = lanes;
     } else {
-        s->bins_active = true;
-        const int rc = force_eval(s, false);
-        s->bins_active = false;
-        if (rc) return rc;
+        EvalRequest rq;
+        rq.bins = true;
+        if (int rc = force_eval(s, rq)) return rc;
         const bool sym = strncmp(s->last_kernel, "force_sym_kernel", 16) == 0;
         path = sym ? 1 : 2;
         shape = sym ? s->sym.r : 0;

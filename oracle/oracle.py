@@ -7,6 +7,7 @@ __graft_entry__.smoke() and bench.py's cpu_baseline leg; never by the product pa
 arrays with the reference's dtype state machine (SURVEY.md section 8a "Facts").
 """
 import ctypes as C
+import fcntl
 import os
 import subprocess
 
@@ -24,8 +25,12 @@ _CODE = {np.dtype(np.float16): F16, np.dtype(np.float32): F32, np.dtype(np.float
 
 def build(force=False):
     src = os.path.join(_HERE, "nbody_oracle.c")
-    if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < os.path.getmtime(src):
-        subprocess.check_call(["make", "-C", _HERE, "-s"])
+    # one process at a time: the workers a test spawns arrive together, and a library that another process is still
+    # linking already exists, looks fresh and is too short to load
+    with open(src, "rb") as guard:
+        fcntl.flock(guard, fcntl.LOCK_EX)
+        if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < os.path.getmtime(src):
+            subprocess.check_call(["make", "-C", _HERE, "-s"])
     return _SO
 
 

@@ -160,10 +160,7 @@ def step_path(p, n, mode, storage_f64, dts, nsteps, spec=0, env=(), levels=0):
         spec_next = (not inner) and uni and p["enabled"] and not no_spec
         site, opened = "", False
         if generic():
-            if may_defer:
-                pending = True
-            else:
-                site = "axpy"
+            site = "axpy"
         else:
             if storage_f64:
                 used_sym = p["enabled"] and mode == FLOAT64 and (P == DT_F64 or (P == DT_F32 and p["r"] in (2, 4)))
