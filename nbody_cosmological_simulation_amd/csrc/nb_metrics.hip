@@ -135,12 +135,14 @@ metrics_finish_sums_kernel(const double *__restrict__ part, int nblocks, int n, 
             edges[threadIdx.x] = edges_in[threadIdx.x];
         } else {
             // torch.linspace(0, max_radius, num_bins + 1) in float32: symmetric formulation of ATen (start + i*step for
-            // the lower half, end - (steps-1-i)*step for the upper half); callers that need the bins of the reference
-            // to the last bit pass the edges they built with torch itself
+            // the lower half, end - (steps-1-i)*step for the upper half).  The upper half is ONE fused multiply-subtract
+            // here because that is what torch's CPU build returns (measured, B = 1..255: its compiler contracts the
+            // expression; ATen's source does not promise it).  Only C callers get this branch: metrics.py passes the
+            // edges torch itself built
             const float end = (float)(max_radius_in >= 0.0 ? max_radius_in : mx);
             const int steps = num_bins + 1, i = threadIdx.x;
             const float step = __fdiv_rn(end, (float)(steps - 1));
-            edges[i] = (i < steps / 2) ? __fmul_rn(step, (float)i) : __fsub_rn(end, __fmul_rn(step, (float)(steps - i - 1)));
+            edges[i] = (i < steps / 2) ? __fmul_rn(step, (float)i) : __fmaf_rn(-step, (float)(steps - i - 1), end);
         }
     }
 }

@@ -679,3 +679,133 @@ def test_axpy_and_one_term_kinetic_energy_match_torch_for_all_dtype_pairs():
                     want = (0.5 * mass * (vel ** 2).sum(dim=-1)).sum().item()
                     got = O.lib().nbo_kinetic_energy(nk, d, ca, O._dp(v64), cb, O._dp(O.as_f64(mass.double().numpy())))
                     assert got == want, (ta, tb, d, k, got, want)
+
+
+# --------------------------------------------------------------------------- the per-star diagnostics oracle
+def _torch_per_star(p, v, m, G, edges):
+    """The reference's formulas (metrics.py:48-143) with torch's CPU ops, every intermediate kept."""
+    import torch
+    positions, velocities, masses = torch.from_numpy(p), torch.from_numpy(v), torch.from_numpy(m)
+    radii = torch.sqrt((positions ** 2).sum(dim=-1))
+    vt = torch.abs(positions[:, 0] * velocities[:, 1] - positions[:, 1] * velocities[:, 0]) / radii.clamp(min=0.1)
+    com = (positions * masses.unsqueeze(-1)).sum(dim=0) / masses.sum()
+    r_com = torch.sqrt(((positions - com) ** 2).sum(dim=-1))
+    order = torch.argsort(r_com, stable=True)
+    enclosed = torch.cumsum(masses[order], dim=0)[torch.argsort(order)]
+    vesc = torch.sqrt(2 * G * enclosed / r_com.clamp(min=0.1))
+    vm = torch.sqrt((velocities ** 2).sum(dim=-1))
+    e = torch.from_numpy(edges)
+    bins = torch.full((len(m),), -1, dtype=torch.int64)
+    for b in range(len(edges) - 1):
+        bins[(radii >= e[b]) & (radii < e[b + 1])] = b
+    return {k: t.numpy() for k, t in dict(r=radii, vt=vt, vm=vm, com=com, r_com=r_com, order=order, enclosed=enclosed,
+                                          vesc=vesc, bound=vm < vesc, bins=bins).items()}
+
+
+def _oracle_per_star(p, v, m, G, edges):
+    from oracle import metrics_oracle as MO
+    rc = MO.com_radii(p, m)
+    return dict(r=MO.radii(p), vt=MO.tangential_speeds(p, v), vm=MO.speeds(v), com=MO.centre_of_mass(p, m), r_com=rc,
+                order=MO.stable_order(rc), enclosed=MO.enclosed_masses(p, m), vesc=MO.escape_speeds(p, m, G),
+                bound=MO.bound_flags(p, v, m, G), bins=MO.bin_indices(MO.radii(p), edges))
+
+
+def _per_star_agree(got, want, keys, tag):
+    """Exact, except through a square root: torch's vectorised CPU sqrt is not correctly rounded (measured in float32:
+    sqrt(115.328125f) comes out 0.5014 ulp from the true root, on the wrong side of a near-tie; float64 likewise),
+    numpy's is -- see test_metrics_oracle_square_root_is_correctly_rounded.  So the roots themselves (r, |v|, r_com)
+    are held to one float of torch's value and what is computed from a root by one more rounded divide (vt) or a
+    divide and a second root (vesc) to two; everything else to equality."""
+    floats = {"r": 1, "vm": 1, "r_com": 1, "vt": 2, "vesc": 2}
+    for k in keys:
+        a, b = got[k], want[k]
+        if k in ("order", "bins", "bound"):
+            assert np.array_equal(a, b), (k,) + tag
+            continue
+        assert a.dtype == b.dtype, (k,) + tag
+        if k in floats:
+            with np.errstate(invalid="ignore"):
+                ok = (a == b) | (np.isnan(a) & np.isnan(b)) | (np.abs(a - b) <= floats[k] * np.spacing(np.abs(b)))
+            assert ok.all(), (k,) + tag
+        else:
+            assert np.array_equal(a, b, equal_nan=True), (k,) + tag
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("n,dim", [(1, 2), (2, 3), (257, 2), (1025, 3), (2049, 2)])
+def test_metrics_oracle_per_star_functions_vs_torch_ops(n, dim, dtype):
+    """Every per-star function of oracle/metrics_oracle.py against torch's CPU result of the reference formula, element
+    by element: all of them on lattice inputs (whose sums are exact in any order, so torch's summation order cannot
+    matter), the element-wise ones (r, vt, |v|, bins) on random inputs with awkward stars as well."""
+    import torch
+    import metrics_cases as MC
+    rng = np.random.default_rng(n + dim)
+    edges = torch.linspace(0, 12.5, 8).numpy()
+    p, m = MC.lattice(n, dim, np.dtype(dtype))
+    v = (rng.standard_normal((n, dim)) * 0.05).astype(dtype)
+    want, got = _torch_per_star(p, v, m, 0.001, edges), _oracle_per_star(p, v, m, 0.001, edges)
+    _per_star_agree(got, want, list(want), (n, dim, dtype))
+    p = (rng.standard_normal((n, dim)) * 4).astype(dtype)
+    p[0] = 0.05
+    if n > 2:
+        p[1, 0], v[2, 1] = np.nan, np.inf
+    want, got = _torch_per_star(p, v, m, 0.001, edges), _oracle_per_star(p, v, m, 0.001, edges)
+    _per_star_agree(got, want, ("r", "vt", "vm", "bins"), (n, dim, dtype))
+
+
+def test_metrics_oracle_square_root_is_correctly_rounded():
+    """The oracle's float32 roots are the correctly rounded ones: equal to the float64 root rounded once (53 >= 2 * 24 + 2
+    bits: the double rounding is harmless for a square root).  The device tests hold the kernels to these."""
+    import metrics_cases as MC
+    from oracle import metrics_oracle as MO
+    p, m = MC.lattice(2049, 3, np.dtype(np.float32))
+    s = (p.astype(np.float64) ** 2).sum(axis=1)                       # exact on the lattice
+    assert np.array_equal(MO.radii(p), np.sqrt(s).astype(np.float32))
+    x = np.float32(115.328125)
+    assert np.sqrt(x) == np.float32(np.sqrt(np.float64(x))) == np.float32(10.739093780517578)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_metrics_lattice_inputs_have_order_independent_sums(dtype):
+    """The precondition of the exact star-by-star device tests, for each lattice case: the sums behind the centre of mass
+    are float32 numbers, and the oracle's enclosed masses and centre of mass do not change under sequential,
+    reversed-within-1024-blocks and pairwise float64 accumulation."""
+    import metrics_cases as MC
+    for n, dim in MC.LATTICE_CASES:
+        p, m = MC.lattice(n, dim, np.dtype(dtype))
+        assert len(np.unique(m)) > 1 or n == 1
+        assert np.abs(p).max() <= 16 and m.min() >= 0.25 and m.max() <= 2
+        assert MC.sums_round_trip_through_float32(p, m), (n, dim)
+        assert MC.order_independent(p, m), (n, dim)
+
+
+def test_metrics_random_mass_case_has_an_order_independent_seed():
+    import metrics_cases as MC
+    seed, p, m = MC.random_mass_case()
+    assert seed is not None and seed <= 20
+    assert MC.order_independent(p, m) and not MC.sums_round_trip_through_float32(p, m)      # it really rounds
+
+
+def test_metrics_oracle_linspace_and_ranks():
+    """MO.linspace_f32 is torch.linspace; the percentile rank where n * p / 100 is within an ulp of an integer."""
+    import torch
+    from oracle import metrics_oracle as MO
+    for B in (1, 2, 7, 20, 255):
+        for R in (1.0, 12.5, float(np.float32(12.3456789)), float(np.float32(0.7071067811865476))):
+            assert np.array_equal(MO.linspace_f32(R, B), torch.linspace(0, R, B + 1).numpy()), (B, R)
+    assert [MO.percentile_rank(300, p) for p in (29, 57, 58, 0, 100, 99.9)] == [87, 171, 174, 0, 299, 299]
+    assert [MO.percentile_rank(1, p) for p in (0, 50, 100)] == [0, 0, 0]
+
+
+def test_metrics_oracle_vs_reference_metric_flow_tick0():
+    """g12: the reference's collect_metrics at tick 0 (float32 state) from the refactored aggregates."""
+    from oracle import metrics_oracle as MO
+    g = load_golden("g12_metric_flow.npz")
+    p, v, m = g["pos"], g["vel"], g["mass"]
+    for mode in ("float64", "int4_sim"):
+        rc = MO.rotation_curve(p, v)
+        assert list(rc["num_stars_per_bin"]) == list(g[f"{mode}/rc_n"][0])
+        assert np.allclose(rc["velocities"], g[f"{mode}/rc_v"][0], rtol=2e-6, equal_nan=True)
+        assert abs(MO.galaxy_radius(p, 90) - g[f"{mode}/galaxy_radius_90"][0]) <= 1e-6 * g[f"{mode}/galaxy_radius_90"][0]
+        assert abs(MO.bound_fraction(p, v, m, 0.001) - g[f"{mode}/bound_fraction"][0]) <= 1e-6
+        assert abs(MO.velocity_dispersion(v) - g[f"{mode}/velocity_dispersion"][0]) <= 2e-6 * g[f"{mode}/velocity_dispersion"][0]
