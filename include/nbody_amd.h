@@ -138,6 +138,52 @@ int nb_kick(nb_sim *s);
 /* get_kinetic_energy / get_potential_energy (simulation.py:170-192); either may be NULL. */
 int nb_energy(nb_sim *s, double *kinetic, double *potential);
 
+/* ---- ensembles: many small systems per launch ------------------------------------------------ */
+
+/* The reference's sweeps (falsification_tests.py:284-356 over softening lengths and time steps,
+ * reproducibility.py:362 over seeds, stability_test.py over modes) are Python loops of independent
+ * GalaxySimulations of a few hundred to a few thousand stars.  An nb_ens holds `members` such systems of the
+ * same n, dim, precision mode and state dtype, each with its own state, G, softening and dt, and advances all
+ * of them one tick per kernel launch.  No arithmetic crosses members; a member's state is bit-identical to
+ * the nb_sim that takes the same steps on the one-launch small-system path.
+ * Limits: modes NB_FLOAT64 .. NB_FLOAT16 (the grid modes need per-member tables: NB_ERR_UNSUPPORTED);
+ * state of the settled dtype only (NB_F64 under NB_FLOAT64, NB_F32 otherwise); n at most the one-launch
+ * step's limit (4096 fp64, 3072 fp32); 1 <= members <= 1024; one device, no communicator.
+ * Arrays are whole (members, n, dim) / (members, n) row-major blocks, host or device as flagged. */
+typedef struct nb_ens nb_ens;
+typedef struct nb_ens_config {
+    int32_t members;       /* B                                                              */
+    int32_t n;             /* stars per member                                               */
+    int32_t dim;           /* 2 or 3                                                         */
+    int32_t mode;          /* nb_mode, NB_FLOAT64 .. NB_FLOAT16                              */
+    int32_t device;        /* HIP device ordinal                                             */
+    int32_t flags;         /* 0                                                              */
+} nb_ens_config;
+
+/* G / softening_sq / dt: `members` doubles each (softening**2 evaluated by the caller, as in nb_config) */
+int nb_ens_create(nb_ens **out, const nb_ens_config *cfg, const double *G, const double *softening_sq,
+                  const double *dt);
+int nb_ens_destroy(nb_ens *e);
+/* any array may be NULL to keep its values; the device copy is updated on the handle's stream */
+int nb_ens_set_params(nb_ens *e, const double *G, const double *softening_sq, const double *dt);
+/* as nb_set_state / nb_get_state / nb_set_accelerations, for all members at once */
+int nb_ens_set_state(nb_ens *e, const void *pos, const void *vel, const void *mass, int dtype, int on_device);
+int nb_ens_get_state(nb_ens *e, void *pos, void *vel, void *acc, void *mass, int on_device);
+int nb_ens_set_accelerations(nb_ens *e, const void *acc, int dtype, int on_device);
+/* every member's forces on its current positions: one launch */
+int nb_ens_compute_accelerations(nb_ens *e);
+/* `nsteps` leapfrog ticks of every member: one elementwise launch (opening kick + drift), then one force
+ * launch per tick that closes the tick and opens the next */
+int nb_ens_step(nb_ens *e, int32_t nsteps);
+/* kinetic / potential: `members` doubles each, either may be NULL; the values nb_energy gives for the
+ * member's state on an nb_sim, bit for bit (off the hot path: evaluated member by member) */
+int nb_ens_energy(nb_ens *e, double *kinetic, double *potential);
+/* members; batched force launches issued since creation (nb_ens_compute_accelerations and one per tick;
+ * the opening kick + drift launch of an nb_ens_step is not counted); name of the last force kernel
+ * ("ens_step_kernel", "none" before the first).  Any output may be NULL. */
+int nb_ens_info(nb_ens *e, int32_t *members, int64_t *force_launches, const char **kernel_name);
+int nb_ens_synchronize(nb_ens *e);
+
 /* ---- precision-hook introspection ---------------------------------------------------- */
 
 /* Grid-mode internals of the LAST force evaluation: info[0..3] = lmin, lmax (log-grid of

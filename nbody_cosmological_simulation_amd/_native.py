@@ -32,6 +32,8 @@ EXPORTS = [
     "nb_comm_shutdown", "nb_comm_quiesce", "nb_comm_p2p_export", "nb_comm_p2p_import", "nb_comm_p2p_selftest",
     "nb_comm_p2p_enable", "nb_comm_p2p_state", "nb_comm_p2p_allreduce", "nb_comm_allreduce_time", "nb_comm_p2p_virtual_test", "nb_plan_debug", "nb_set_hook_stream", "nb_metrics", "nb_metrics_tensors",
     "nb_kernel_time", "nb_force_kernel_name", "nb_pe_kernel_name", "nb_step_path_name", "nb_synchronize", "nb_device_count", "nb_abi_version", "nb_last_error",
+    "nb_ens_create", "nb_ens_destroy", "nb_ens_set_params", "nb_ens_set_state", "nb_ens_get_state", "nb_ens_set_accelerations",
+    "nb_ens_compute_accelerations", "nb_ens_step", "nb_ens_energy", "nb_ens_info", "nb_ens_synchronize",
 ]
 
 
@@ -40,6 +42,13 @@ class NbConfig(C.Structure):
         ("n", C.c_int32), ("dim", C.c_int32), ("mode", C.c_int32), ("levels", C.c_int32),
         ("G", C.c_double), ("softening_sq", C.c_double), ("dt", C.c_double),
         ("device", C.c_int32), ("rank", C.c_int32), ("nranks", C.c_int32), ("flags", C.c_int32),
+    ]
+
+
+class NbEnsConfig(C.Structure):
+    _fields_ = [
+        ("members", C.c_int32), ("n", C.c_int32), ("dim", C.c_int32), ("mode", C.c_int32),
+        ("device", C.c_int32), ("flags", C.c_int32),
     ]
 
 
@@ -114,6 +123,17 @@ def lib():
         "nb_device_count": ([pi32], C.c_int),
         "nb_abi_version": ([], C.c_int),
         "nb_last_error": ([], C.c_char_p),
+        "nb_ens_create": ([C.POINTER(vp), C.POINTER(NbEnsConfig), pdbl, pdbl, pdbl], C.c_int),
+        "nb_ens_destroy": ([vp], C.c_int),
+        "nb_ens_set_params": ([vp, pdbl, pdbl, pdbl], C.c_int),
+        "nb_ens_set_state": ([vp, vp, vp, vp, C.c_int, C.c_int], C.c_int),
+        "nb_ens_get_state": ([vp, vp, vp, vp, vp, C.c_int], C.c_int),
+        "nb_ens_set_accelerations": ([vp, vp, C.c_int, C.c_int], C.c_int),
+        "nb_ens_compute_accelerations": ([vp], C.c_int),
+        "nb_ens_step": ([vp, i32], C.c_int),
+        "nb_ens_energy": ([vp, pdbl, pdbl], C.c_int),
+        "nb_ens_info": ([vp, pi32, C.POINTER(C.c_int64), C.POINTER(C.c_char_p)], C.c_int),
+        "nb_ens_synchronize": ([vp], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -1,0 +1,275 @@
+// nb_ens_api.cpp -- nb_ens handles (include/nbody_amd.h): B independent systems of the same shape, precision mode and
+// state dtype, each with its own G / softening / dt, advanced together -- ONE force launch per tick (nb_ensemble.hip) where
+// a loop of solo handles issues B.  Host orchestration only, as in nb_api.cpp / nb_step.cpp.
+//
+// Layout: contiguous (B, N, D) positions (two buffers: they ping-pong as in the solo step), velocities, accelerations and
+// (B, N) masses in the storage type (fp64 under FLOAT64, else fp32), and a device array of NB_ENS_PARAM_WORDS scalars per
+// member, cast on the host exactly as the solo launch casts them.  A mode that needs more per member (the grid modes:
+// tables, force min / max) adds arrays beside these; nothing here is indexed by anything but the member.
+//
+// Energies are off the hot path and must equal a solo handle's bit for bit, whichever kernel variant the solo engine
+// picks for this shape and these masses: each member's slice is handed (device to device) to one solo handle of the same
+// shape kept for that purpose, and nb_energy runs there.
+#include <cstring>
+
+#include "nb_state.h"
+
+using namespace nbhost;
+
+struct nb_ens {
+    nb_ens_config cfg{};
+    hipStream_t stream = nullptr;
+    bool is_f64 = false;
+    int hook = HOOK_NONE, lanes = 64;
+    std::vector<double> G, eps2, dt;          // per member, as given
+    std::vector<char> prm_host;               // what the device array holds (or is about to)
+    void *prm = nullptr;                      // device: members * NB_ENS_PARAM_WORDS elements of the storage type
+    void *pos = nullptr, *pos_alt = nullptr, *vel = nullptr, *acc = nullptr, *mass = nullptr;
+    bool have_pos = false, have_vel = false, have_mass = false, have_acc = false;
+    int64_t force_launches = 0;               // batched force launches since creation (kick + drift launches not counted)
+    const char *last_kernel = "none";
+    nb_sim *probe = nullptr;                  // solo handle of the members' shape: energies (created on first use)
+};
+
+namespace {
+
+inline size_t el(const nb_ens *e) { return e->is_f64 ? 8 : 4; }
+inline size_t cnt_nd(const nb_ens *e) { return (size_t)e->cfg.members * e->cfg.n * e->cfg.dim; }
+inline size_t cnt_n(const nb_ens *e) { return (size_t)e->cfg.members * e->cfg.n; }
+
+// the casts of nb_launch_small_step / launch_s: fp64 (T)x; fp32 (float)G, (float)eps2, (float)(dt / 2), (float)dt
+int upload_params(nb_ens *e)
+{
+    const int B = e->cfg.members;
+    for (int b = 0; b < B; ++b) {
+        const double half_dt = e->dt[b] / 2;
+        if (e->is_f64) {
+            const double v[NB_ENS_PARAM_WORDS] = {e->G[b], e->eps2[b], half_dt, e->dt[b]};
+            memcpy(e->prm_host.data() + (size_t)b * sizeof v, v, sizeof v);
+        } else {
+            const float v[NB_ENS_PARAM_WORDS] = {(float)e->G[b], (float)e->eps2[b], (float)half_dt, (float)e->dt[b]};
+            memcpy(e->prm_host.data() + (size_t)b * sizeof v, v, sizeof v);
+        }
+    }
+    // on the handle's stream, behind the launches that still read the old values; the wait keeps prm_host free to rewrite
+    HIPCHK(hipMemcpyAsync(e->prm, e->prm_host.data(), e->prm_host.size(), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return NB_OK;
+}
+
+int launch_force(nb_ens *e, int do_kick)
+{
+    const nb_ens_config &c = e->cfg;
+    HIPCHK(nb_launch_ens_step(e->pos, e->pos_alt, e->vel, e->acc, e->mass, c.members, c.n, c.dim, e->is_f64, e->hook, e->prm,
+                              do_kick, e->lanes, e->stream));
+    e->force_launches++;
+    e->last_kernel = "ens_step_kernel";
+    return NB_OK;
+}
+
+int copy_in(nb_ens *e, void *dst, const void *src, size_t count, int on_device)
+{
+    HIPCHK(hipMemcpyAsync(dst, src, count * el(e), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
+    return NB_OK;
+}
+
+int copy_out(nb_ens *e, void *dst, const void *src, size_t count, int on_device)
+{
+    HIPCHK(hipMemcpyAsync(dst, src, count * el(e), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, e->stream));
+    return NB_OK;
+}
+
+void release(nb_ens *e)
+{
+    if (e->probe) (void)nb_destroy(e->probe);
+    for (void *p : {e->prm, e->pos, e->pos_alt, e->vel, e->acc, e->mass})
+        if (p) (void)hipFree(p);
+    if (e->stream) (void)hipStreamDestroy(e->stream);
+    delete e;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nb_ens_create(nb_ens **out, const nb_ens_config *cfg, const double *G, const double *softening_sq, const double *dt)
+{
+    if (!out || !cfg || !G || !softening_sq || !dt) return fail(NB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (cfg->members < 1 || cfg->members > NB_ENS_MAX_MEMBERS)
+        return fail(NB_ERR_INVALID, "members must be in [1, %d] (got %d)", NB_ENS_MAX_MEMBERS, cfg->members);
+    if (cfg->n < 1) return fail(NB_ERR_INVALID, "n must be >= 1 (got %d)", cfg->n);
+    if (cfg->dim != 2 && cfg->dim != 3) return fail(NB_ERR_INVALID, "dim must be 2 or 3 (got %d)", cfg->dim);
+    if (cfg->mode < NB_FLOAT64 || cfg->mode > NB_FLOAT16)
+        return fail(NB_ERR_UNSUPPORTED, "ensembles run the FLOAT64, FLOAT32, BFLOAT16 and FLOAT16 modes (got mode %d): the grid "
+                                        "modes need per-member tables", cfg->mode);
+    const bool f64 = cfg->mode == NB_FLOAT64;
+    if (cfg->n > small_max_n(f64))
+        return fail(NB_ERR_UNSUPPORTED, "n = %d is above the one-launch step's limit of %d for this mode: a single system of "
+                                        "that size fills the chip, step it with nb_sim", cfg->n, small_max_n(f64));
+    int ndev = 0;
+    hipError_t err = hipGetDeviceCount(&ndev);
+    if (err != hipSuccess || ndev == 0)
+        return fail(NB_ERR_NO_DEVICE, "no HIP device available (%s); this library has no CPU fallback",
+                    err == hipSuccess ? "0 devices" : hipGetErrorString(err));
+    if (cfg->device < 0 || cfg->device >= ndev) return fail(NB_ERR_NO_DEVICE, "device %d out of range [0,%d)", cfg->device, ndev);
+    DeviceGuard guard(cfg->device);
+    nb_ens *e = new nb_ens();
+    e->cfg = *cfg;
+    e->is_f64 = f64;
+    e->hook = mode_hook(cfg->mode);
+    const NbKnobs knobs = nb_read_knobs();
+    e->lanes = knobs.small_lanes ? knobs.small_lanes : nb_small_lanes(cfg->n);     // as step_small picks them
+    const int B = cfg->members;
+    e->G.assign(G, G + B);
+    e->eps2.assign(softening_sq, softening_sq + B);
+    e->dt.assign(dt, dt + B);
+    e->prm_host.resize((size_t)B * NB_ENS_PARAM_WORDS * el(e));
+    const size_t nd_bytes = cnt_nd(e) * el(e);
+    hipError_t he = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
+    if (he == hipSuccess) he = hipMalloc(&e->prm, e->prm_host.size());
+    if (he == hipSuccess) he = hipMalloc(&e->pos, nd_bytes);
+    if (he == hipSuccess) he = hipMalloc(&e->pos_alt, nd_bytes);
+    if (he == hipSuccess) he = hipMalloc(&e->vel, nd_bytes);
+    if (he == hipSuccess) he = hipMalloc(&e->acc, nd_bytes);
+    if (he == hipSuccess) he = hipMalloc(&e->mass, cnt_n(e) * el(e));
+    if (he == hipSuccess) he = hipMemsetAsync(e->acc, 0, nd_bytes, e->stream);
+    if (he != hipSuccess) {
+        release(e);
+        return fail(he == hipErrorOutOfMemory ? NB_ERR_OOM : NB_ERR_HIP, "ensemble allocation failed: %s", hipGetErrorString(he));
+    }
+    if (int rc = upload_params(e)) { release(e); return rc; }
+    *out = e;
+    return NB_OK;
+}
+
+int nb_ens_destroy(nb_ens *e)
+{
+    if (!e) return NB_OK;
+    DeviceGuard guard(e->cfg.device);
+    if (e->stream) (void)hipStreamSynchronize(e->stream);
+    release(e);
+    return NB_OK;
+}
+
+int nb_ens_set_params(nb_ens *e, const double *G, const double *softening_sq, const double *dt)
+{
+    if (!e) return fail(NB_ERR_INVALID, "null handle");
+    DeviceGuard guard(e->cfg.device);
+    const int B = e->cfg.members;
+    if (G) e->G.assign(G, G + B);
+    if (softening_sq) e->eps2.assign(softening_sq, softening_sq + B);
+    if (dt) e->dt.assign(dt, dt + B);
+    return upload_params(e);
+}
+
+int nb_ens_set_state(nb_ens *e, const void *pos, const void *vel, const void *mass, int dtype, int on_device)
+{
+    if (!e) return fail(NB_ERR_INVALID, "null handle");
+    if (dtype != (e->is_f64 ? NB_F64 : NB_F32))
+        return fail(NB_ERR_UNSUPPORTED, "ensemble state is %s under this mode (got dtype %d): mixed dtypes and the promotion "
+                                        "timeline are nb_sim's", e->is_f64 ? "fp64" : "fp32", dtype);
+    DeviceGuard guard(e->cfg.device);
+    if (pos) { if (int rc = copy_in(e, e->pos, pos, cnt_nd(e), on_device)) return rc; e->have_pos = true; }
+    if (vel) { if (int rc = copy_in(e, e->vel, vel, cnt_nd(e), on_device)) return rc; e->have_vel = true; }
+    if (mass) { if (int rc = copy_in(e, e->mass, mass, cnt_n(e), on_device)) return rc; e->have_mass = true; }
+    HIPCHK(hipStreamSynchronize(e->stream));      // the copies have consumed the caller's buffers
+    return NB_OK;
+}
+
+int nb_ens_get_state(nb_ens *e, void *pos, void *vel, void *acc, void *mass, int on_device)
+{
+    if (!e) return fail(NB_ERR_INVALID, "null handle");
+    DeviceGuard guard(e->cfg.device);
+    if (pos) if (int rc = copy_out(e, pos, e->pos, cnt_nd(e), on_device)) return rc;
+    if (vel) if (int rc = copy_out(e, vel, e->vel, cnt_nd(e), on_device)) return rc;
+    if (acc) if (int rc = copy_out(e, acc, e->acc, cnt_nd(e), on_device)) return rc;
+    if (mass) if (int rc = copy_out(e, mass, e->mass, cnt_n(e), on_device)) return rc;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return NB_OK;
+}
+
+int nb_ens_set_accelerations(nb_ens *e, const void *acc, int dtype, int on_device)
+{
+    if (!e || !acc) return fail(NB_ERR_INVALID, "null argument");
+    if (dtype != (e->is_f64 ? NB_F64 : NB_F32)) return fail(NB_ERR_UNSUPPORTED, "acceleration dtype %d on %s state", dtype, e->is_f64 ? "fp64" : "fp32");
+    DeviceGuard guard(e->cfg.device);
+    if (int rc = copy_in(e, e->acc, acc, cnt_nd(e), on_device)) return rc;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->have_acc = true;
+    return NB_OK;
+}
+
+int nb_ens_compute_accelerations(nb_ens *e)
+{
+    if (!e) return fail(NB_ERR_INVALID, "null handle");
+    if (!e->have_pos || !e->have_mass) return fail(NB_ERR_INVALID, "positions/masses not set");
+    DeviceGuard guard(e->cfg.device);
+    if (int rc = launch_force(e, NB_KICK_NONE)) return rc;
+    e->have_acc = true;
+    return NB_OK;
+}
+
+// `nsteps` leapfrog ticks of every member (simulation.py:120-143): one elementwise launch for the opening kick + drift,
+// then one force launch per tick that closes the tick and opens the next (the last one only closes)
+int nb_ens_step(nb_ens *e, int32_t nsteps)
+{
+    if (!e) return fail(NB_ERR_INVALID, "null handle");
+    if (!e->have_pos || !e->have_vel || !e->have_mass) return fail(NB_ERR_INVALID, "state incomplete");
+    if (!e->have_acc) return fail(NB_ERR_INVALID, "no accelerations yet: call nb_ens_compute_accelerations first");
+    if (nsteps < 1) return NB_OK;
+    DeviceGuard guard(e->cfg.device);
+    const nb_ens_config &c = e->cfg;
+    HIPCHK(nb_launch_ens_kick_drift(e->pos, e->vel, e->acc, c.members, c.n, c.dim, e->is_f64, e->prm, e->stream));
+    for (int t = 0; t < nsteps; ++t) {
+        const bool last = (t + 1 == nsteps);
+        if (int rc = launch_force(e, last ? NB_KICK_CLOSE : NB_KICK_CLOSE_OPEN)) return rc;
+        if (!last) std::swap(e->pos, e->pos_alt);       // the launch wrote the drifted positions to the second buffer
+    }
+    return NB_OK;
+}
+
+int nb_ens_energy(nb_ens *e, double *kinetic, double *potential)
+{
+    if (!e) return fail(NB_ERR_INVALID, "null handle");
+    if (!kinetic && !potential) return NB_OK;
+    if (!e->have_mass || (kinetic && !e->have_vel) || (potential && !e->have_pos)) return fail(NB_ERR_INVALID, "state incomplete");
+    DeviceGuard guard(e->cfg.device);
+    const nb_ens_config &c = e->cfg;
+    if (!e->probe) {
+        nb_config pc{};
+        pc.n = c.n; pc.dim = c.dim; pc.mode = c.mode; pc.G = e->G[0]; pc.softening_sq = e->eps2[0]; pc.dt = e->dt[0];
+        pc.device = c.device; pc.rank = 0; pc.nranks = 1; pc.flags = 0;
+        if (int rc = nb_create(&e->probe, &pc)) return rc;
+    }
+    HIPCHK(hipStreamSynchronize(e->stream));         // the probe reads the members' slices on a stream of its own
+    const int dtype = e->is_f64 ? NB_F64 : NB_F32;
+    const size_t nd_b = (size_t)c.n * c.dim * el(e), n_b = (size_t)c.n * el(e);
+    for (int b = 0; b < c.members; ++b) {
+        if (int rc = nb_set_params(e->probe, e->G[b], e->eps2[b], e->dt[b])) return rc;
+        if (int rc = nb_set_state(e->probe, (const char *)e->pos + b * nd_b, (const char *)e->vel + b * nd_b,
+                                  (const char *)e->mass + b * n_b, dtype, 1))
+            return rc;
+        if (int rc = nb_energy(e->probe, kinetic ? kinetic + b : nullptr, potential ? potential + b : nullptr)) return rc;
+    }
+    return NB_OK;
+}
+
+int nb_ens_info(nb_ens *e, int32_t *members, int64_t *force_launches, const char **kernel_name)
+{
+    if (!e) return fail(NB_ERR_INVALID, "null handle");
+    if (members) *members = e->cfg.members;
+    if (force_launches) *force_launches = e->force_launches;
+    if (kernel_name) *kernel_name = e->last_kernel;
+    return NB_OK;
+}
+
+int nb_ens_synchronize(nb_ens *e)
+{
+    if (!e) return fail(NB_ERR_INVALID, "null handle");
+    DeviceGuard guard(e->cfg.device);
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return NB_OK;
+}
+
+}  // extern "C"

@@ -308,6 +308,18 @@ hipError_t nb_launch_small_step(const void *pos_in, void *pos_out, void *vel, vo
                                 const GridTables *tab = nullptr /* HOOK_GRID: this evaluation's tables */,
                                 double *part = nullptr /* INT8 / INT4: 2 n doubles, per-target min / max of the forces */,
                                 unsigned long long *bin_out = nullptr /* HOOK_GRID: bin read-out (BINS instantiation) */);
+// ---- many small systems per launch (nb_ensemble.hip; host side nb_ens_api.cpp) -----------------------------------------
+// `members` systems of n particles in contiguous (members, n, dim) / (members, n) buffers of the storage type; prm: device,
+// NB_ENS_PARAM_WORDS elements of the storage type per member = {G, eps2, dt / 2, dt}, cast on the host exactly as
+// nb_launch_small_step casts the solo step's.  The body is the solo step's (nb_small_body.h), picked by
+// nb_small_block(n) and `lanes` as there; do_kick: NB_KICK_NONE / CLOSE / CLOSE_OPEN.
+constexpr int NB_ENS_PARAM_WORDS = 4;
+constexpr int NB_ENS_MAX_MEMBERS = 1024;
+hipError_t nb_launch_ens_step(const void *pos_in, void *pos_out, void *vel, void *acc, const void *mass, int members, int n,
+                              int dim, int is_f64, int hook, const void *prm, int do_kick, int lanes, hipStream_t st);
+// opening kick + drift of every member with its own dt (two roundings per line, like nb_launch_kick_drift)
+hipError_t nb_launch_ens_kick_drift(void *pos, void *vel, const void *acc, int members, int n, int dim, int is_f64,
+                                    const void *prm, hipStream_t st);
 // second half of nb_launch_force_quant_step with caller-provided min / max partials (nblocks pairs of doubles)
 hipError_t nb_launch_force_quant_finish(float *acc, int64_t count, int levels, const double *partials, int nblocks,
                                         double *mn_mx, int16_t *bins, float *vel, float *pos, double half_dt, double dt,

@@ -16,6 +16,7 @@
 // Arithmetic per pair is that of the tuned kernels (fp64: v_rsq_f64 + second-order correction; fp32: reference op
 // order for r2 without fma, cast hooks, v_rsq_f32 + first-order correction, fp32 products summed in fp64).
 #include "nb_device.h"
+#include "nb_small_body.h"
 
 #include <cstdlib>
 
@@ -25,29 +26,8 @@ namespace {
 
 using namespace nbdev;
 
-constexpr int SM_TILE = 1024;     // sources per LDS tile (2048 measured: slower -- fewer workgroups per CU)
-
-__device__ __forceinline__ double inv_r3_d(double q)
-{
-    const double y0 = __builtin_amdgcn_rsq(q);
-    const double y02 = y0 * y0;
-    const double e = __builtin_fma(-q, y02, 1.0);
-    const double v = y0 * y02;
-    const double c = __builtin_fma(e, 1.875, 1.5);
-    return __builtin_fma(v, c * e, v);
-}
-__device__ __forceinline__ float inv_r3_f(float q)
-{
-    const float y0 = __builtin_amdgcn_rsqf(q);
-    const float y02 = y0 * y0;
-    const float e = __builtin_fmaf(-q, y02, 1.0f);
-    const float v = y0 * y02;
-    return __builtin_fmaf(v * e, 1.5f, v);
-}
-
-template <typename T> __device__ __forceinline__ T axpy_sep(T a, T b, T s);      // a + b*s, two roundings like torch
-template <> __device__ __forceinline__ double axpy_sep<double>(double a, double b, double s) { return __dadd_rn(a, __dmul_rn(b, s)); }
-template <> __device__ __forceinline__ float axpy_sep<float>(float a, float b, float s) { return __fadd_rn(a, __fmul_rn(b, s)); }
+// the pair loop, butterfly and kicks of the cast hooks (and SM_TILE, inv_r3_*, axpy_sep): nb_small_body.h, shared with
+// the batched step of nb_ensemble.hip; the grid hook's body (tables, bin read-out) follows here
 
 // do_kick: an NbKick mode, | NB_KICK_OPEN_ON_READ (nb_internal.h); the drifted positions go to pos_out
 // BINS (grid hook only): the same body with the quant-bin read-out -- per-target integer checksums s1 = sum_j k,
@@ -62,17 +42,19 @@ small_step_kernel(const T *__restrict__ pos_in, T *__restrict__ pos_out, T *__re
                   const T *__restrict__ mass, int n, T G, T eps2, T half_dt, T dt, int do_kick,
                   const GridTables *__restrict__ tab, double *__restrict__ part, unsigned long long *__restrict__ bin_out)
 {
-    constexpr bool F64 = sizeof(T) == 8;
-    constexpr int TG = BS / S;                       // targets per workgroup
-    __shared__ T sx[D][SM_TILE];
-    __shared__ T sg[SM_TILE];                        // G * m_j (fp32: the reference's (1/p * G) * m_j order is kept below)
-    // grid hook (INT8 / INT4 / CUSTOM up to 256 levels): the evaluation's tables (nb_force.hip grid_tables_kernel)
-    __shared__ float s_thr[HOOK == HOOK_GRID ? NB_LUT_MIN + 1 : 1], s_lut[HOOK == HOOK_GRID ? NB_LUT_MIN + 1 : 1];
-    const int tid = threadIdx.x;
-    bool g_fast = false, g_est = false, g_deg = false;
-    float est_a = 0.0f, est_b = 0.0f, est_bc = 0.0f, sure_lim = 0.0f, c1 = 0.0f, c0c = 0.0f, kcf = 0.0f;
-    int g_levels = 0, g_tm = 0;
-    if constexpr (HOOK == HOOK_GRID) {
+    if constexpr (HOOK != HOOK_GRID) {
+        small_step_body<T, D, HOOK, S, BS>(blockIdx.x, pos_in, pos_out, vel, acc, mass, n, G, eps2, half_dt, dt, do_kick, part);
+    } else {
+        constexpr bool F64 = sizeof(T) == 8;
+        constexpr int TG = BS / S;                       // targets per workgroup
+        __shared__ T sx[D][SM_TILE];
+        __shared__ T sg[SM_TILE];                        // G * m_j (fp32: the reference's (1/p * G) * m_j order is kept below)
+        // grid hook (INT8 / INT4 / CUSTOM up to 256 levels): the evaluation's tables (nb_force.hip grid_tables_kernel)
+        __shared__ float s_thr[NB_LUT_MIN + 1], s_lut[NB_LUT_MIN + 1];
+        const int tid = threadIdx.x;
+        bool g_fast = false, g_est = false, g_deg = false;
+        float est_a = 0.0f, est_b = 0.0f, est_bc = 0.0f, sure_lim = 0.0f, c1 = 0.0f, c0c = 0.0f, kcf = 0.0f;
+        int g_levels = 0, g_tm = 0;
         g_levels = tab->levels;
         for (int k = tid; k <= NB_LUT_MIN; k += BS) {
             s_thr[k] = (k <= g_levels) ? tab->thr[k] : __builtin_inff();     // thr[levels] = NaN sentinel, +inf padding
@@ -83,41 +65,39 @@ small_step_kernel(const T *__restrict__ pos_in, T *__restrict__ pos_out, T *__re
         g_deg = tab->degenerate != 0;
         est_a = tab->est_a; est_b = tab->est_b; est_bc = tab->est_bc; sure_lim = tab->sure_lim;
         c1 = tab->c1; c0c = tab->c0c; kcf = (float)tab->kc; g_tm = tab->tm;
-    }
-    const int grp = tid / S, l = tid % S;
-    const int i_raw = blockIdx.x * TG + grp;
-    const bool live = i_raw < n;
-    const int i = live ? i_raw : n - 1;
-    T xi[D];
+        const int grp = tid / S, l = tid % S;
+        const int i_raw = blockIdx.x * TG + grp;
+        const bool live = i_raw < n;
+        const int i = live ? i_raw : n - 1;
+        T xi[D];
 #pragma unroll
-    for (int k = 0; k < D; ++k) xi[k] = pos_in[(size_t)i * D + k];
-    double a[D];
+        for (int k = 0; k < D; ++k) xi[k] = pos_in[(size_t)i * D + k];
+        double a[D];
 #pragma unroll
-    for (int k = 0; k < D; ++k) a[k] = 0.0;
-    long long b1 = 0, b2 = 0, bfast = 0, bexact = 0;     // BINS only
+        for (int k = 0; k < D; ++k) a[k] = 0.0;
+        long long b1 = 0, b2 = 0, bfast = 0, bexact = 0;     // BINS only
 
-    for (int j0 = 0; j0 < n; j0 += SM_TILE) {
-        __syncthreads();
-        // entries past the end, up to the pair loop's stride: padding (far away, massless)
-        constexpr int STRIDE = (HOOK == HOOK_GRID) ? 4 * S : S;
-        const int cnt_ld = min(SM_TILE, (min(SM_TILE, n - j0) + STRIDE - 1) / STRIDE * STRIDE);
-        // (a "flat" variant -- consecutive threads reading consecutive elements of the (N, D) array and scattering them
-        // into the component arrays -- measured slower on the same box: 6.8 vs 5.4 us per step at N = 1024 fp64)
-        for (int t = tid; t < cnt_ld; t += BS) {
-            const int j = j0 + t;
-            if (j < n) {
+        for (int j0 = 0; j0 < n; j0 += SM_TILE) {
+            __syncthreads();
+            // entries past the end, up to the pair loop's stride: padding (far away, massless)
+            constexpr int STRIDE = 4 * S;
+            const int cnt_ld = min(SM_TILE, (min(SM_TILE, n - j0) + STRIDE - 1) / STRIDE * STRIDE);
+            // (a "flat" variant -- consecutive threads reading consecutive elements of the (N, D) array and scattering them
+            // into the component arrays -- measured slower on the same box: 6.8 vs 5.4 us per step at N = 1024 fp64)
+            for (int t = tid; t < cnt_ld; t += BS) {
+                const int j = j0 + t;
+                if (j < n) {
 #pragma unroll
-                for (int k = 0; k < D; ++k) sx[k][t] = pos_in[(size_t)j * D + k];
-                sg[t] = F64 ? (T)(G * mass[j]) : mass[j];
-            } else {
+                    for (int k = 0; k < D; ++k) sx[k][t] = pos_in[(size_t)j * D + k];
+                    sg[t] = F64 ? (T)(G * mass[j]) : mass[j];
+                } else {
 #pragma unroll
-                for (int k = 0; k < D; ++k) sx[k][t] = F64 ? (T)1e150 : (T)1e18;
-                sg[t] = (T)0;
+                    for (int k = 0; k < D; ++k) sx[k][t] = F64 ? (T)1e150 : (T)1e18;
+                    sg[t] = (T)0;
+                }
             }
-        }
-        __syncthreads();
-        const int cnt_up = cnt_ld;                   // padding entries are harmless
-        if constexpr (HOOK == HOOK_GRID) {
+            __syncthreads();
+            const int cnt_up = cnt_ld;                   // padding entries are harmless
             // four sources per iteration: independent log / exp chains in flight, ONE edge test for all of them
             constexpr int U = 4;
             for (int jj = l; jj < cnt_up; jj += U * S) {
@@ -192,99 +172,73 @@ small_step_kernel(const T *__restrict__ pos_in, T *__restrict__ pos_out, T *__re
                     for (int k = 0; k < D; ++k) a[k] += (double)__fmul_rn(wm, dd[u][k]);
                 }
             }
-        } else {
-#pragma unroll 4
-        for (int jj = l; jj < cnt_up; jj += S) {
-            T d[D];
-            if constexpr (F64) {
-#pragma unroll
-                for (int k = 0; k < D; ++k) d[k] = sx[k][jj] - xi[k];
-                double q = __builtin_fma(d[D - 1], d[D - 1], eps2);
-#pragma unroll
-                for (int k = D - 2; k >= 0; --k) q = __builtin_fma(d[k], d[k], q);
-                const double w = inv_r3_d(q) * sg[jj];
-#pragma unroll
-                for (int k = 0; k < D; ++k) a[k] = __builtin_fma(w, d[k], a[k]);
-            } else {
-#pragma unroll
-                for (int k = 0; k < D; ++k) d[k] = __fsub_rn(sx[k][jj], xi[k]);
-                float q = r2_f32_exact<D>(d, eps2);
-                if (HOOK == HOOK_BF16) q = round_bf16(q);
-                if (HOOK == HOOK_F16) q = round_f16(q);
-                float w = __fmul_rn(inv_r3_f(q), G);
-                if (HOOK == HOOK_F16) w = (q == __builtin_inff()) ? 0.0f : w;      // pow(inf) = inf -> G / inf = 0 upstream
-                w = __fmul_rn(w, sg[jj]);
-#pragma unroll
-                for (int k = 0; k < D; ++k) a[k] += (double)__fmul_rn(w, d[k]);
-            }
         }
-        }
-    }
-    // the S lanes of a target: fixed butterfly
-#pragma unroll
-    for (int off = S / 2; off >= 1; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < D; ++k) a[k] += __shfl_xor(a[k], off, 64);
-    }
-    if constexpr (BINS) {
+        // the S lanes of a target: fixed butterfly
 #pragma unroll
         for (int off = S / 2; off >= 1; off >>= 1) {
-            b1 += __shfl_xor(b1, off, 64);
-            b2 += __shfl_xor(b2, off, 64);
-            bfast += __shfl_xor(bfast, off, 64);
-            bexact += __shfl_xor(bexact, off, 64);
-        }
-        if (live && l == 0) {
-            bin_out[i] = (unsigned long long)b1;
-            bin_out[(size_t)n + i] = (unsigned long long)b2;
-            atomicAdd(&bin_out[2 * (size_t)n], (unsigned long long)bfast);
-            atomicAdd(&bin_out[2 * (size_t)n + 1], (unsigned long long)bexact);
-        }
-    }
-    __shared__ double s_mm[BS / 16][2];        // INT8 / INT4: min / max of this workgroup's force components
-    double lo = __builtin_inf(), hi = -__builtin_inf();
-    if (live && l == 0) {
 #pragma unroll
-        for (int k = 0; k < D; ++k) {
-            const size_t idx = (size_t)i * D + k;
-            const T ak = (T)a[k];
-            const T a_prev = (do_kick & NB_KICK_OPEN_ON_READ) ? acc[idx] : (T)0;     // (read before this evaluation's force replaces it)
-            acc[idx] = ak;
-            const double av = (double)ak;              // NaN-propagating like torch's min() / max()
-            lo = (av != av || lo != lo) ? __builtin_nan("") : (av < lo ? av : lo);
-            hi = (av != av || hi != hi) ? __builtin_nan("") : (av > hi ? av : hi);
-            const int kmode = do_kick & NB_KICK_MODE_MASK;
-            if (kmode != NB_KICK_NONE) {
-                T v = vel[idx];
-                if (do_kick & NB_KICK_OPEN_ON_READ) v = axpy_sep<T>(v, a_prev, half_dt);     // this step's opening kick, deferred (see below)
-                v = axpy_sep<T>(v, ak, half_dt);                          // closing kick (simulation.py:141)
-                if (kmode == NB_KICK_CLOSE_OPEN) {
-                    v = axpy_sep<T>(v, ak, half_dt);                      // next step's opening kick (:132)
-                    pos_out[idx] = axpy_sep<T>(xi[k], v, dt);             // ... and drift (:135)
-                } else if (kmode == NB_KICK_CLOSE_SPEC) {
-                    // last step of a native call: velocities stay at the closing kick (what a reader must see), but the
-                    // positions the NEXT step would drift to go to pos_out -- if the next nb_step finds the state
-                    // untouched it takes them and applies its opening kick here on read (NB_KICK_OPEN_ON_READ): a Python loop of
-                    // step() costs one launch per step instead of two
-                    const T vo = axpy_sep<T>(v, ak, half_dt);
-                    pos_out[idx] = axpy_sep<T>(xi[k], vo, dt);
-                }
-                vel[idx] = v;
+            for (int k = 0; k < D; ++k) a[k] += __shfl_xor(a[k], off, 64);
+        }
+        if constexpr (BINS) {
+#pragma unroll
+            for (int off = S / 2; off >= 1; off >>= 1) {
+                b1 += __shfl_xor(b1, off, 64);
+                b2 += __shfl_xor(b2, off, 64);
+                bfast += __shfl_xor(bfast, off, 64);
+                bexact += __shfl_xor(bexact, off, 64);
+            }
+            if (live && l == 0) {
+                bin_out[i] = (unsigned long long)b1;
+                bin_out[(size_t)n + i] = (unsigned long long)b2;
+                atomicAdd(&bin_out[2 * (size_t)n], (unsigned long long)bfast);
+                atomicAdd(&bin_out[2 * (size_t)n + 1], (unsigned long long)bexact);
             }
         }
-    }
-    if (part) {                                      // kernel-uniform
-        if (l == 0) { s_mm[grp][0] = lo; s_mm[grp][1] = hi; }    // dead targets hold (+inf, -inf): neutral
-        __syncthreads();
-        if (tid == 0) {
-            double mn = s_mm[0][0], mx = s_mm[0][1];
-            for (int g = 1; g < TG; ++g) {
-                const double a0 = s_mm[g][0], a1 = s_mm[g][1];
-                mn = (a0 != a0 || mn != mn) ? __builtin_nan("") : (a0 < mn ? a0 : mn);
-                mx = (a1 != a1 || mx != mx) ? __builtin_nan("") : (a1 > mx ? a1 : mx);
+        __shared__ double s_mm[BS / 16][2];        // INT8 / INT4: min / max of this workgroup's force components
+        double lo = __builtin_inf(), hi = -__builtin_inf();
+        if (live && l == 0) {
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+                const size_t idx = (size_t)i * D + k;
+                const T ak = (T)a[k];
+                const T a_prev = (do_kick & NB_KICK_OPEN_ON_READ) ? acc[idx] : (T)0;     // (read before this evaluation's force replaces it)
+                acc[idx] = ak;
+                const double av = (double)ak;              // NaN-propagating like torch's min() / max()
+                lo = (av != av || lo != lo) ? __builtin_nan("") : (av < lo ? av : lo);
+                hi = (av != av || hi != hi) ? __builtin_nan("") : (av > hi ? av : hi);
+                const int kmode = do_kick & NB_KICK_MODE_MASK;
+                if (kmode != NB_KICK_NONE) {
+                    T v = vel[idx];
+                    if (do_kick & NB_KICK_OPEN_ON_READ) v = axpy_sep<T>(v, a_prev, half_dt);     // this step's opening kick, deferred (see below)
+                    v = axpy_sep<T>(v, ak, half_dt);                          // closing kick (simulation.py:141)
+                    if (kmode == NB_KICK_CLOSE_OPEN) {
+                        v = axpy_sep<T>(v, ak, half_dt);                      // next step's opening kick (:132)
+                        pos_out[idx] = axpy_sep<T>(xi[k], v, dt);             // ... and drift (:135)
+                    } else if (kmode == NB_KICK_CLOSE_SPEC) {
+                        // last step of a native call: velocities stay at the closing kick (what a reader must see), but the
+                        // positions the NEXT step would drift to go to pos_out -- if the next nb_step finds the state
+                        // untouched it takes them and applies its opening kick here on read (NB_KICK_OPEN_ON_READ): a Python loop of
+                        // step() costs one launch per step instead of two
+                        const T vo = axpy_sep<T>(v, ak, half_dt);
+                        pos_out[idx] = axpy_sep<T>(xi[k], vo, dt);
+                    }
+                    vel[idx] = v;
+                }
             }
-            part[2 * (size_t)blockIdx.x] = mn;
-            part[2 * (size_t)blockIdx.x + 1] = mx;
+        }
+        if (part) {                                      // kernel-uniform
+            if (l == 0) { s_mm[grp][0] = lo; s_mm[grp][1] = hi; }    // dead targets hold (+inf, -inf): neutral
+            __syncthreads();
+            if (tid == 0) {
+                double mn = s_mm[0][0], mx = s_mm[0][1];
+                for (int g = 1; g < TG; ++g) {
+                    const double a0 = s_mm[g][0], a1 = s_mm[g][1];
+                    mn = (a0 != a0 || mn != mn) ? __builtin_nan("") : (a0 < mn ? a0 : mn);
+                    mx = (a1 != a1 || mx != mx) ? __builtin_nan("") : (a1 > mx ? a1 : mx);
+                }
+                part[2 * (size_t)blockIdx.x] = mn;
+                part[2 * (size_t)blockIdx.x + 1] = mx;
+            }
         }
     }
 }

@@ -218,6 +218,8 @@ int p2p_check(nb_sim *s);
 // ---- nb_step.cpp ---------------------------------------------------------------------------------------------------
 // targets per thread of the one-sided fp64 kernel (FLOAT64 pairs; the cast / half-typed variants always take 2)
 int onesided_r(int n, const NbKnobs &knobs);
+// largest N of the one-launch small-system step for this storage type (also the member size limit of nb_ens)
+int small_max_n(bool is_f64);
 // source chunks of the one-sided kernels (force, potential energy, generic) for this rank's j-range
 ForceGeom onesided_geometry(const nb_config &c, const NbKnobs &knobs);
 void compute_geometry(nb_sim *s);

@@ -33,6 +33,8 @@ struct NbTuning {
 };
 static const NbTuning g_tune{};
 
+int small_max_n(bool is_f64) { return is_f64 ? g_tune.small_max_f64 : g_tune.small_max_f32; }
+
 // targets per thread of the one-sided fp64 kernel.  Small systems are parallelism-bound, not
 // throughput-bound: R = 1 doubles the workgroups (N = 1024: 27.8 -> 17.6 us per step, N = 4096:
 // 32.5 -> 22.6 us)

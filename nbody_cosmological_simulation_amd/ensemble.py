@@ -1,0 +1,262 @@
+"""Many small systems stepped together: `GalaxyEnsemble`.
+
+The reference's sweeps (falsification_tests.py:284-356 over softening lengths and time steps,
+reproducibility.py:362 over seeds, stability_test.py over precision modes, sensitivity_test.py and
+jitter_test.py over one parameter) are Python loops of independent `GalaxySimulation`s with a few hundred to
+a few thousand stars.  One such system is a single latency-bound kernel launch per tick that leaves most of
+the chip idle.  A `GalaxyEnsemble` holds B of them -- same N, D, precision mode and state dtype; own
+positions, velocities, masses, G, softening and dt -- and advances all of them one tick per launch
+(include/nbody_amd.h nb_ens_*, csrc/nb_ensemble.hip).  No arithmetic crosses members, and every member's
+state is bit-identical to the `GalaxySimulation` that takes the same steps.
+
+Unlike `GalaxySimulation`, the array attributes are SNAPSHOTS: `positions`, `velocities`, `masses` and
+`accelerations` return fresh (B, ...) tensors at every read, and in-place edits of them are not tracked.
+Writes go through `set_state`, `set_accelerations` and `set_params`.
+
+First version: FLOAT64 / FLOAT32 / BFLOAT16 / FLOAT16 modes; state already in its settled dtype (fp64
+tensors under FLOAT64, fp32 under the others); N up to the one-launch step's limit (4096 fp64, 3072 fp32) --
+above it a single system already fills the chip; B up to 1024; one device.  Not covered: the grid modes
+(INT8 / INT4 / CUSTOM), per-member tick counts, mixed dtypes and the fp32 -> fp64 promotion timeline,
+subclass overrides, metrics, checkpoints, multi-GPU.
+"""
+import ctypes as C
+import numbers
+from typing import Callable
+
+import torch
+
+from . import _native as N
+from . import runtime
+from .quantization import PrecisionMode, mode_code, _TORCH_TO_NB
+
+MAX_MEMBERS = 1024
+MAX_STARS = {torch.float64: 4096, torch.float32: 3072}     # the solo one-launch step's limits (csrc/nb_step.cpp)
+_MODES = (PrecisionMode.FLOAT64, PrecisionMode.FLOAT32, PrecisionMode.BFLOAT16, PrecisionMode.FLOAT16)
+
+
+def state_dtype(precision_mode) -> torch.dtype:
+    """The settled state dtype of a mode: what positions, velocities, masses and accelerations all have."""
+    return torch.float64 if precision_mode == PrecisionMode.FLOAT64 else torch.float32
+
+
+def _param_list(name, value, members):
+    """A float, or a sequence of `members` floats -> list of floats (members None: any length)."""
+    if isinstance(value, torch.Tensor):
+        value = value.tolist()
+    if isinstance(value, (list, tuple)):
+        out = [float(v) for v in value]
+        if members is not None and len(out) != members:
+            raise ValueError(f"{name} has {len(out)} entries for {members} members")
+        return out
+    if isinstance(value, bool) or not isinstance(value, numbers.Real):
+        raise TypeError(f"{name} must be a float or a sequence of floats, got {type(value).__name__}")
+    return None if members is None else [float(value)] * members
+
+
+def check_arguments(positions, velocities, masses, precision_mode=PrecisionMode.FLOAT64, G=0.001, softening=0.1, dt=0.01):
+    """Validate constructor arguments without touching a device.  Returns (positions, velocities, masses, G, softening,
+    dt) with the tensors shaped (B, N, D) / (B, N) and the parameters as length-B lists; raises ValueError / TypeError."""
+    if not isinstance(precision_mode, PrecisionMode):
+        raise TypeError(f"precision_mode must be a PrecisionMode, got {type(precision_mode).__name__}")
+    if precision_mode not in _MODES:
+        raise ValueError(f"GalaxyEnsemble runs the FLOAT64, FLOAT32, BFLOAT16 and FLOAT16 modes; {precision_mode.name} needs "
+                         "per-member quantisation tables (use GalaxySimulation)")
+    for name, t in (("positions", positions), ("velocities", velocities), ("masses", masses)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+    if positions.dim() == 2 and masses.dim() == 1:
+        # one galaxy under a parameter sweep: as many members as the longest parameter list
+        lens = [len(p) for p in (_param_list("G", G, None), _param_list("softening", softening, None),
+                                 _param_list("dt", dt, None)) if p is not None]
+        members = max(lens) if lens else 1
+        if velocities.dim() != 2:
+            raise ValueError(f"velocities must be (N, D) like positions, got {tuple(velocities.shape)}")
+        positions, velocities, masses = (t.unsqueeze(0).expand(members, *t.shape) for t in (positions, velocities, masses))
+    if positions.dim() != 3 or masses.dim() != 2:
+        raise ValueError(f"positions must be (B, N, D) with (B, N) masses, or (N, D) with (N,) masses; got "
+                         f"{tuple(positions.shape)} and {tuple(masses.shape)}")
+    B, n, d = (int(v) for v in positions.shape)
+    if d not in (2, 3):
+        raise ValueError(f"D must be 2 or 3, got {d}")
+    if tuple(velocities.shape) != (B, n, d) or tuple(masses.shape) != (B, n):
+        raise ValueError(f"positions {tuple(positions.shape)}, velocities {tuple(velocities.shape)} and masses "
+                         f"{tuple(masses.shape)} disagree on (B, N, D)")
+    if not 1 <= B <= MAX_MEMBERS:
+        raise ValueError(f"B must be in [1, {MAX_MEMBERS}], got {B}")
+    want = state_dtype(precision_mode)
+    for name, t in (("positions", positions), ("velocities", velocities), ("masses", masses)):
+        if t.dtype != want:
+            raise TypeError(f"{name} must be {want} under {precision_mode.name} (got {t.dtype}): an ensemble holds settled "
+                            "state only; mixed dtypes and the promotion timeline are GalaxySimulation's")
+    if not 1 <= n <= MAX_STARS[want]:
+        raise ValueError(f"N must be in [1, {MAX_STARS[want]}] for {want} state, got {n}: above it a single system fills the "
+                         "chip (use GalaxySimulation)")
+    return (positions, velocities, masses, _param_list("G", G, B), _param_list("softening", softening, B),
+            _param_list("dt", dt, B))
+
+
+def _doubles(values):
+    return (C.c_double * len(values))(*values)
+
+
+class GalaxyEnsemble:
+    """B independent N-body systems advanced one tick per kernel launch (see the module docstring)."""
+
+    def __init__(self, positions, velocities, masses, precision_mode=PrecisionMode.FLOAT64,
+                 G=0.001, softening=0.1, dt=0.01, device=None):
+        self._handle = C.c_void_p()
+        positions, velocities, masses, self.G, self.softening, self.dt = check_arguments(
+            positions, velocities, masses, precision_mode, G, softening, dt)
+        self.device = torch.device(device) if device is not None else positions.device
+        self.precision_mode = precision_mode
+        self.num_members, self.num_stars, self._dim = (int(v) for v in positions.shape)
+        self._dtype = state_dtype(precision_mode)
+        self.tick = 0
+        if self.device.type == "cuda":
+            dev = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        else:
+            dev = runtime.default_hip_device()
+        cfg = N.NbEnsConfig(members=self.num_members, n=self.num_stars, dim=self._dim, mode=mode_code(precision_mode),
+                            device=int(dev), flags=0)
+        N.check(N.lib().nb_ens_create(C.byref(self._handle), C.byref(cfg), _doubles(self.G),
+                                      _doubles([s ** 2 for s in self.softening]), _doubles(self.dt)))
+        self.set_state(positions=positions, velocities=velocities, masses=masses)
+        N.check(N.lib().nb_ens_compute_accelerations(self._handle))
+
+    # ------------------------------------------------------------------ native plumbing
+    def close(self):
+        """Release the native handle (device buffers, stream) now instead of at garbage collection."""
+        h = getattr(self, "_handle", None)
+        if h is not None and h.value:
+            try:
+                N.lib().nb_ens_destroy(h)
+            except Exception:
+                pass
+            h.value = None
+
+    def __del__(self):
+        self.close()
+
+    def _shape(self, name):
+        return (self.num_members, self.num_stars) if name == "masses" else (self.num_members, self.num_stars, self._dim)
+
+    def _pointer(self, name, t):
+        """(contiguous tensor kept alive by the caller, pointer, on_device) of an upload; shape and dtype checked."""
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+        if tuple(t.shape) != self._shape(name):
+            raise ValueError(f"{name} must have shape {self._shape(name)}, got {tuple(t.shape)}")
+        if t.dtype != self._dtype:
+            raise TypeError(f"{name} must be {self._dtype}, got {t.dtype}")
+        t = t.detach().contiguous()
+        on_device = t.device.type == "cuda"
+        if on_device:
+            torch.cuda.current_stream(t.device).synchronize()
+        return t, C.c_void_p(t.data_ptr()), on_device
+
+    def _download(self, name):
+        out = torch.empty(self._shape(name), dtype=self._dtype, device=self.device)
+        args = [None, None, None, None]
+        args[{"positions": 0, "velocities": 1, "accelerations": 2, "masses": 3}[name]] = C.c_void_p(out.data_ptr())
+        N.check(N.lib().nb_ens_get_state(self._handle, args[0], args[1], args[2], args[3], int(out.device.type == "cuda")))
+        return out
+
+    positions = property(lambda s: s._download("positions"))
+    velocities = property(lambda s: s._download("velocities"))
+    masses = property(lambda s: s._download("masses"))
+    accelerations = property(lambda s: s._download("accelerations"))
+
+    # ------------------------------------------------------------------ writes
+    def set_state(self, positions=None, velocities=None, masses=None):
+        """Replace whole (B, N, D) / (B, N) arrays of the state; the accelerations are NOT recomputed (as assigning
+        `sim.positions` on a GalaxySimulation leaves them)."""
+        given = [(n, t) for n, t in (("positions", positions), ("velocities", velocities), ("masses", masses)) if t is not None]
+        if not given:
+            return
+        held = [self._pointer(n, t) for n, t in given]
+        for on_device in sorted({h[2] for h in held}):
+            ptr = {n: h[1] for (n, _), h in zip(given, held) if h[2] == on_device}
+            N.check(N.lib().nb_ens_set_state(self._handle, ptr.get("positions"), ptr.get("velocities"), ptr.get("masses"),
+                                             _TORCH_TO_NB[self._dtype], int(on_device)))
+
+    def set_accelerations(self, accelerations):
+        """Replace the stored (B, N, D) accelerations (what the next tick's opening kick uses)."""
+        t, ptr, on_device = self._pointer("accelerations", accelerations)
+        N.check(N.lib().nb_ens_set_accelerations(self._handle, ptr, _TORCH_TO_NB[self._dtype], int(on_device)))
+
+    def set_params(self, G=None, softening=None, dt=None):
+        """New G / softening / dt (each a float for all members or a length-B sequence); read by the next launch."""
+        B = self.num_members
+        new = {k: _param_list(k, v, B) for k, v in (("G", G), ("softening", softening), ("dt", dt)) if v is not None}
+        if not new:
+            return
+        self.G, self.softening, self.dt = new.get("G", self.G), new.get("softening", self.softening), new.get("dt", self.dt)
+        N.check(N.lib().nb_ens_set_params(self._handle, _doubles(self.G) if "G" in new else None,
+                                          _doubles([s ** 2 for s in self.softening]) if "softening" in new else None,
+                                          _doubles(self.dt) if "dt" in new else None))
+
+    # ------------------------------------------------------------------ hot path
+    def step(self):
+        """One kick-drift-kick leapfrog tick of every member (reference simulation.py:120-143)."""
+        N.check(N.lib().nb_ens_step(self._handle, 1))
+        self.tick += 1
+
+    def run(self, num_ticks: int, callback: Callable = None, callback_interval: int = 100):
+        """`num_ticks` ticks; `callback(self, self.tick)` every `callback_interval` (the contract of
+        GalaxySimulation.run).  Stretches between callbacks are one native call: one launch per tick."""
+        done = 0
+        while done < num_ticks:
+            nxt = min(num_ticks, (done // callback_interval + 1) * callback_interval) if callback else num_ticks
+            N.check(N.lib().nb_ens_step(self._handle, nxt - done))
+            self.tick += nxt - done
+            done = nxt
+            if callback and done % callback_interval == 0:
+                callback(self, self.tick)
+
+    # ------------------------------------------------------------------ reads
+    def _energy(self, kinetic, potential):
+        B = self.num_members
+        ke, pe = (C.c_double * B)(), (C.c_double * B)()
+        N.check(N.lib().nb_ens_energy(self._handle, ke if kinetic else None, pe if potential else None))
+        return list(ke), list(pe)
+
+    def get_kinetic_energy(self) -> list:
+        """Per member, sum(0.5 * m * v^2) (reference simulation.py:170-174)."""
+        return self._energy(True, False)[0]
+
+    def get_potential_energy(self) -> list:
+        """Per member, -G * sum_{i<j} m_i m_j / sqrt(r_ij^2 + eps^2) (reference simulation.py:176-192)."""
+        return self._energy(False, True)[1]
+
+    def get_total_energy(self) -> list:
+        ke, pe = self._energy(True, True)
+        return [k + p for k, p in zip(ke, pe)]
+
+    def get_state(self, b: int) -> dict:
+        """Member b's state as the reference's get_state() dict (simulation.py:160-168)."""
+        b = int(b)
+        if not 0 <= b < self.num_members:
+            raise IndexError(f"member {b} of {self.num_members}")
+        return {
+            "positions": self.positions[b].clone(),
+            "velocities": self.velocities[b].clone(),
+            "masses": self.masses[b].clone(),
+            "tick": self.tick,
+            "precision_mode": self.precision_mode.value,
+        }
+
+    def _info(self):
+        members, launches, name = C.c_int32(), C.c_int64(), C.c_char_p()
+        N.check(N.lib().nb_ens_info(self._handle, C.byref(members), C.byref(launches), C.byref(name)))
+        return members.value, launches.value, (name.value or b"none").decode()
+
+    def launches(self) -> int:
+        """Batched force launches since construction: one for the constructor's evaluation, one per tick.  The
+        elementwise opening kick + drift launch of every step() / run() stretch is not counted."""
+        return self._info()[1]
+
+    def force_kernel_name(self) -> str:
+        return self._info()[2]
+
+    def synchronize(self):
+        N.check(N.lib().nb_ens_synchronize(self._handle))

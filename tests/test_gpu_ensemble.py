@@ -1,0 +1,278 @@
+"""GalaxyEnsemble on the GPU: every member bit-identical to the solo engine, members independent of each other, the
+project's usual bars against the oracle, solo-equal energies, one force launch per tick, and the state round trip.
+
+Members: the clustered-core-plus-halo inputs of test_gpu_plan_shapes with one seed per member, member 3 with uniform
+masses; G, softening and dt differ per member and are not fp32-representable; dt changes after the second tick.
+Shapes sit where the batched indexing can go wrong (see CASES).  One five-tick trajectory per case is computed once by a
+B = 5 ensemble driven with step() and shared by the tests, which compare other drivers and the solo engine with it.
+"""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from test_gpu_plan_shapes import inputs, relerr
+
+pytestmark = pytest.mark.gpu
+
+B = 5
+TICKS = 5
+G_ = [0.001, 0.00113, 0.00091, 0.00127, 0.00107]
+SOFT = [0.1, 0.113, 0.087, 0.131, 0.071]
+DT = [0.01, 0.0123, 0.0071, 0.0157, 0.0093]
+DT2 = [0.0137, 0.0091, 0.0113, 0.0077, 0.0129]        # from the third tick on
+UNIFORM_MEMBER = 3
+
+# (N, D, mode): N = 37 fewer sources than lanes of a target, one partial workgroup; 700 ordinary; 1025 one star past the
+# 1024-source LDS tile; 2049 the workgroup size switches 512 -> 256; 3073 (fp64 only) it switches back to 512; the
+# FLOAT16 / BFLOAT16 hooks once each
+CASES = [
+    (37, 3, "float64"), (37, 2, "float32"),
+    (700, 2, "float64"), (700, 3, "float32"),
+    (1025, 3, "float64"), (1025, 2, "float32"),
+    (2049, 2, "float64"), (2049, 3, "float32"),
+    (3073, 3, "float64"),
+    (1300, 2, "bfloat16"), (1300, 2, "float16"),
+]
+IDS = [f"n{n}-d{d}-{m}" for n, d, m in CASES]
+
+
+@pytest.fixture(scope="module")
+def nb():
+    import nbody_cosmological_simulation_amd as pkg
+    assert pkg._native.device_count() >= 1, "no HIP device: the product path has no CPU fallback"
+    return pkg
+
+
+def T(a):
+    return torch.from_numpy(np.ascontiguousarray(a))
+
+
+@functools.lru_cache(maxsize=None)
+def members(case):
+    """Initial (B, N, D) positions, velocities and (B, N) masses of a case (numpy, the mode's settled dtype)."""
+    n, d, mode = case
+    ms = [inputs(n, d, 1000 + 17 * b, mode == "float64", uniform=(b == UNIFORM_MEMBER)) for b in range(B)]
+    return tuple(np.stack([m[k] for m in ms]) for k in range(3))
+
+
+def make_ens(nb, case, order=range(B), pos=None):
+    p, v, m = members(case)
+    idx = list(order)
+    p = p if pos is None else pos
+    return nb.GalaxyEnsemble(T(p[idx]), T(v[idx]), T(m[idx]), precision_mode=nb.PrecisionMode(case[2]),
+                             G=[G_[b] for b in idx], softening=[SOFT[b] for b in idx], dt=[DT[b] for b in idx])
+
+
+def snapshot(e):
+    return e.positions.numpy(), e.velocities.numpy(), e.accelerations.numpy()
+
+
+def drive_steps(e, order=range(B)):
+    """TICKS step() calls with the dt change after the second; (pos, vel, acc) after every tick."""
+    out = []
+    for t in range(TICKS):
+        if t == 2:
+            e.set_params(dt=[DT2[b] for b in order])
+        e.step()
+        out.append(snapshot(e))
+    return out
+
+
+_TRAJ = {}
+
+
+def trajectory(nb, case):
+    """The shared reference of a case: initial accelerations and the state after every tick of the B = 5 ensemble."""
+    if case not in _TRAJ:
+        e = make_ens(nb, case)
+        acc0 = e.accelerations.numpy()
+        assert e.force_kernel_name() == "ens_step_kernel"
+        ticks = drive_steps(e)
+        e.close()
+        _TRAJ[case] = (acc0, ticks)
+    return _TRAJ[case]
+
+
+def make_solo(nb, case, b, acc0):
+    p, v, m = members(case)
+    s = nb.GalaxySimulation(T(p[b]), T(v[b]), T(m[b]), precision_mode=nb.PrecisionMode(case[2]), G=G_[b],
+                            softening=SOFT[b], dt=DT[b])
+    # the constructor's evaluation takes the tiled path and may differ in the last bit: start from the ensemble's
+    s.accelerations = T(acc0[b]).clone()
+    return s
+
+
+def same(got, want, what):
+    for name, g, w in zip(("positions", "velocities", "accelerations"), got, want):
+        assert g.dtype == w.dtype and np.array_equal(g, w, equal_nan=True), f"{what}: {name} differ"
+
+
+def solo_state(s):
+    return s.positions.numpy(), s.velocities.numpy(), s.accelerations.numpy()
+
+
+# ---- 1. bit identity with the solo engine -----------------------------------------------------------------------------
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_step_loop_is_bit_identical_to_solo(nb, case):
+    acc0, ticks = trajectory(nb, case)
+    for b in range(B):
+        s = make_solo(nb, case, b, acc0)
+        for t in range(TICKS):
+            if t == 2:
+                s.dt = DT2[b]
+            s.step()
+            same(solo_state(s), [a[b] for a in ticks[t]], f"member {b} tick {t + 1}")
+            assert s.force_kernel_name() == "small_step_kernel"
+        s.close()
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_run_is_bit_identical_to_solo_and_to_the_step_loop(nb, case):
+    acc0, ticks = trajectory(nb, case)
+    e = make_ens(nb, case)
+    e.run(2)
+    same(snapshot(e), ticks[1], "ensemble run(2)")
+    e.set_params(dt=DT2)
+    e.run(3)
+    same(snapshot(e), ticks[4], "ensemble run(2) + run(3)")
+    assert e.tick == 5
+    e.close()
+    for b in range(B):
+        s = make_solo(nb, case, b, acc0)
+        s.run(2)
+        same(solo_state(s), [a[b] for a in ticks[1]], f"solo member {b} run(2)")
+        s.dt = DT2[b]
+        s.run(3)
+        same(solo_state(s), [a[b] for a in ticks[4]], f"solo member {b} run(2) + run(3)")
+        assert s.force_kernel_name() == "small_step_kernel"
+        s.close()
+
+
+# ---- 2. members are independent ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_members_do_not_depend_on_their_neighbours(nb, case):
+    acc0, ticks = trajectory(nb, case)
+    rev = list(reversed(range(B)))
+    e = make_ens(nb, case, rev)
+    same([e.accelerations.numpy()], [acc0[rev]], "reversed order, initial")
+    for t, got in enumerate(drive_steps(e, rev)):
+        same(got, [a[rev] for a in ticks[t]], f"reversed order tick {t + 1}")
+    e.close()
+    for b in range(B):
+        e = make_ens(nb, case, [b])
+        assert e.num_members == 1
+        same([e.accelerations.numpy()], [acc0[[b]]], f"member {b} alone, initial")
+        for t, got in enumerate(drive_steps(e, [b])):
+            same(got, [a[[b]] for a in ticks[t]], f"member {b} alone tick {t + 1}")
+        e.close()
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_a_nan_member_leaves_the_others_alone(nb, case):
+    acc0, ticks = trajectory(nb, case)
+    bad = 2
+    p = members(case)[0].copy()
+    p[bad, 0, 0] = np.nan
+    p[bad, min(1, case[0] - 1), 1] = np.inf
+    e = make_ens(nb, case, pos=p)
+    others = [b for b in range(B) if b != bad]
+    same([e.accelerations.numpy()[others]], [acc0[others]], "initial")
+    for t, got in enumerate(drive_steps(e)):
+        same([g[others] for g in got], [a[others] for a in ticks[t]], f"tick {t + 1}")
+    # its own state: NaN propagates silently, as in the reference
+    pos, vel, acc = got
+    assert np.isnan(acc[bad]).all() and np.isnan(vel[bad]).all() and np.isnan(pos[bad]).all()
+    e.close()
+
+
+# ---- 3. against the oracle (bars of test_gpu_plan_shapes for this kernel) ------------------------------------------------
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_forces_and_three_ticks_match_the_oracle(nb, case):
+    from oracle import oracle as O
+    n, d, mode = case
+    f64 = mode == "float64"
+    acc0, ticks = trajectory(nb, case)
+    p, v, m = members(case)
+    for b in range(B):
+        ref = O.accelerations(p[b], m[b], mode, G=G_[b], softening=SOFT[b])
+        err = relerr(acc0[b], ref)
+        print(f"{IDS[CASES.index(case)]} member {b}: initial accelerations relerr {err:.3e}")
+        assert err < (1e-13 if f64 else 2e-6), (b, err)
+        sim = O.OracleSim(p[b], v[b], m[b], mode, G=G_[b], softening=SOFT[b], dt=DT[b])
+        sim.run(2)
+        sim.dt = DT2[b]
+        sim.run(1)
+        err = relerr(ticks[2][0][b], sim.positions)
+        print(f"{IDS[CASES.index(case)]} member {b}: positions after three ticks relerr {err:.3e}")
+        assert err < (1e-13 if f64 else 5e-6), (b, err)
+
+
+# ---- 4. energies ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_energies_equal_the_solo_values(nb, case):
+    e = make_ens(nb, case)
+    e.run(2)
+    ke, pe, tot = e.get_kinetic_energy(), e.get_potential_energy(), e.get_total_energy()
+    pos, vel, mass = e.positions, e.velocities, e.masses
+    assert len(ke) == len(pe) == len(tot) == B and all(isinstance(x, float) for x in ke + pe + tot)
+    for b in range(B):
+        s = nb.GalaxySimulation(pos[b].clone(), vel[b].clone(), mass[b].clone(), precision_mode=nb.PrecisionMode(case[2]),
+                                G=G_[b], softening=SOFT[b], dt=DT[b])
+        assert ke[b] == s.get_kinetic_energy(), (b, ke[b], s.get_kinetic_energy())
+        assert pe[b] == s.get_potential_energy(), (b, pe[b], s.get_potential_energy())
+        assert tot[b] == ke[b] + pe[b]
+        s.close()
+    # the energy evaluation leaves the ensemble's state alone
+    same(snapshot(e), trajectory(nb, case)[1][1], "state after the energy calls")
+    e.close()
+
+
+# ---- 5. one launch per tick ----------------------------------------------------------------------------------------------
+def test_a_tick_is_one_force_launch(nb):
+    n, d, members_ = 700, 2, 8
+    ms = [inputs(n, d, 50 + b, True) for b in range(members_)]
+    p, v, m = (T(np.stack([x[k] for x in ms])) for k in range(3))
+    e = nb.GalaxyEnsemble(p, v, m, dt=[0.01 + 0.0013 * b for b in range(members_)])
+    assert e.num_members == 8 and e.num_stars == 700
+    assert e.launches() == 1            # the constructor's evaluation
+    before = e.launches()
+    e.run(6)
+    # force launches only: the elementwise opening kick + drift launch of the run() is not counted
+    assert e.launches() - before == 6
+    assert e.force_kernel_name() == "ens_step_kernel"
+    seen = []
+    e.run(5, callback=lambda ens, tick: seen.append((ens is e, tick)), callback_interval=2)
+    assert seen == [(True, 8), (True, 10)] and e.tick == 11 and e.launches() - before == 11
+    e.close()
+
+
+# ---- 6. round trip ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode,dtype", [("float64", torch.float64), ("float32", torch.float32)])
+def test_state_round_trip(nb, mode, dtype):
+    case = (37, 3, mode)
+    e = make_ens(nb, case)
+    g = torch.Generator().manual_seed(3)
+    p, v, a = (torch.randn(B, 37, 3, generator=g, dtype=torch.float64).to(dtype) for _ in range(3))
+    m = torch.rand(B, 37, generator=g, dtype=torch.float64).to(dtype)
+    e.set_state(positions=p, velocities=v, masses=m)
+    e.set_accelerations(a)
+    for got, want in ((e.positions, p), (e.velocities, v), (e.masses, m), (e.accelerations, a)):
+        assert got.dtype == dtype and got.shape == want.shape and torch.equal(got, want)
+    e.positions.zero_()                                            # a snapshot: edits are not tracked
+    assert torch.equal(e.positions, p)
+    e.set_state(velocities=2 * v)
+    assert torch.equal(e.velocities, 2 * v) and torch.equal(e.positions, p)
+    st = e.get_state(4)
+    assert sorted(st.keys()) == ["masses", "positions", "precision_mode", "tick", "velocities"]
+    assert torch.equal(st["positions"], p[4]) and torch.equal(st["masses"], m[4]) and st["tick"] == 0
+    assert st["precision_mode"] == mode
+    with pytest.raises(ValueError):
+        e.set_state(positions=p[:, :36])
+    with pytest.raises(TypeError):
+        e.set_accelerations(a.to(torch.float16))
+    with pytest.raises(ValueError):
+        e.set_params(dt=[0.01] * 4)
+    assert e.G == G_ and e.softening == SOFT and e.dt == DT
+    e.close()
