@@ -160,6 +160,11 @@ static inline double gqs_value(int T, double k, double lmin, double lmax, int L,
     return clamp_min(v, scalar_as(T, min_val));
 }
 
+/* libm's double log / exp on arrays: the near-tie masks of tests/hook_cases.py are computed from the very values
+ * that gqs_log / gqs_value round */
+void nbo_log_f64(long n, const double *in, double *out) { for (long i = 0; i < n; ++i) out[i] = log(in[i]); }
+void nbo_exp_f64(long n, const double *in, double *out) { for (long i = 0; i < n; ++i) out[i] = exp(in[i]); }
+
 /* ------------------------------------------------------------------ tensor-level hooks */
 
 /* quantization.py:91-127.  in/out: n doubles holding dtype-T values.  bins may be NULL.

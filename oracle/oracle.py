@@ -62,6 +62,9 @@ def lib():
                                            C.c_double, C.c_int, C.c_int]
         L.nbo_grid_quantize_safe.restype = C.c_int
         L.nbo_grid_quantize_safe.argtypes = [C.c_long, C.c_int, dp, dp, C.c_int, C.c_double, dp, dp, ip]
+        for name in ("nbo_log_f64", "nbo_exp_f64"):
+            getattr(L, name).restype = None
+            getattr(L, name).argtypes = [C.c_long, dp, dp]
         L.nbo_grid_quantize.restype = C.c_int
         L.nbo_grid_quantize.argtypes = [C.c_long, C.c_int, dp, dp, C.c_int, dp, dp, ip]
         L.nbo_quantize_distance_squared.restype = C.c_int
@@ -177,6 +180,22 @@ def grid_quantize(t, levels, bins=False):
     lib().nbo_grid_quantize(a.size, code, _dp(a), _dp(out), levels, C.byref(mn), C.byref(mx), _ip(b))
     res = from_f64(out, code).reshape(t.shape)
     return (res, b.reshape(t.shape), mn.value, mx.value) if bins else res
+
+
+def _libm(name, a):
+    a = as_f64(a)
+    out = np.empty_like(a)
+    getattr(lib(), name)(a.size, _dp(a), _dp(out))
+    return out
+
+
+def log_f64(a):
+    """libm's double log, the one grid_quantize_safe rounds."""
+    return _libm("nbo_log_f64", a)
+
+
+def exp_f64(a):
+    return _libm("nbo_exp_f64", a)
 
 
 def quantize_distance_squared(t, mode, custom_levels=None, min_dist_sq=0.01):

@@ -418,6 +418,17 @@ def torch_formula_safe(t, levels, min_val=0.01):
     return torch.exp(k / (levels - 1) * (lmax - lmin) + lmin).clamp(min=min_val).numpy()
 
 
+def torch_formula_linear(t, levels):
+    """quantization.py:74-88 with torch's own CPU ops: only IEEE add, sub, mul, div, round, min and max, so the kernels
+    must reproduce it bit for bit (tests/test_gpu_hooks_elements.py)."""
+    x = torch.from_numpy(t)
+    mn, mx = x.min(), x.max()
+    if mx - mn < 1e-10:
+        return x.numpy()
+    k = torch.round((x - mn) / (mx - mn) * (levels - 1))
+    return (k / (levels - 1) * (mx - mn) + mn).numpy()
+
+
 def test_cuda_tensors_zero_copy_path(nb):
     """State handed over and read back as device tensors (torch is only the allocator here)."""
     g = load_golden("g1_n257_d2_e0.05.npz")
