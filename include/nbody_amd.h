@@ -178,6 +178,24 @@ int nb_ens_step(nb_ens *e, int32_t nsteps);
 /* kinetic / potential: `members` doubles each, either may be NULL; the values nb_energy gives for the
  * member's state on an nb_sim, bit for bit (off the hot path: evaluated member by member) */
 int nb_ens_energy(nb_ens *e, double *kinetic, double *potential);
+/* The same energies for all members in ONE batched evaluation (two kernel launches on the handle's stream, one
+ * copy per output, one wait): kinetic / potential are `members` doubles each, host or device memory as
+ * `on_device` says; either may be NULL.  Needs positions and masses, and velocities when kinetic is asked for.
+ * The values agree with nb_ens_energy to the project's bars (1e-12 relative under NB_FLOAT64, 2e-6 otherwise),
+ * not bit for bit: every unordered pair is evaluated once per 256-star tile pair and summed in fp64 in a fixed
+ * order, so they are deterministic and independent of the other members.  A member whose softening_sq is zero
+ * in the state dtype has potential NaN, as upstream (0 / 0 on the masked diagonal, simulation.py:189). */
+int nb_ens_energies(nb_ens *e, double *kinetic, double *potential, int on_device);
+/* nb_ens_step(nsteps) that also records the energies on the device: sample 0 is the state at entry, sample s
+ * the state after tick s * every of this call, 1 + nsteps / every samples in all (written to *samples if not
+ * NULL).  kinetic / potential: `capacity` * members doubles each, sample-major (index s * members + b), host or
+ * device as `on_device` says; either may be NULL.  Preconditions of nb_ens_step, and every >= 1, nsteps >= 0,
+ * capacity >= 1 + nsteps / every (else NB_ERR_INVALID).  A sampled tick is issued as a one-tick nb_ens_step
+ * issues it (the force launch closes the tick, the energy launches follow, a separate kick + drift launch opens
+ * the next tick), so the trajectory is bit-identical to nb_ens_step(nsteps); force_launches grows by nsteps.
+ * Nothing waits on the stream between the first launch and the copy-out of the history at the end. */
+int nb_ens_run_recorded(nb_ens *e, int32_t nsteps, int32_t every, double *kinetic, double *potential,
+                        int64_t capacity, int on_device, int32_t *samples);
 /* members; batched force launches issued since creation (nb_ens_compute_accelerations and one per tick;
  * the opening kick + drift launch of an nb_ens_step is not counted); name of the last force kernel
  * ("ens_step_kernel", "none" before the first).  Any output may be NULL. */

@@ -9,7 +9,9 @@
 //
 // Energies are off the hot path and must equal a solo handle's bit for bit, whichever kernel variant the solo engine
 // picks for this shape and these masses: each member's slice is handed (device to device) to one solo handle of the same
-// shape kept for that purpose, and nb_energy runs there.
+// shape kept for that purpose, and nb_energy runs there.  nb_ens_energies and nb_ens_run_recorded evaluate all members at
+// once instead (nb_ens_energy.hip: two launches on the handle's stream, values at the project's bars rather than the
+// solo engine's bits), the latter between the ticks of a run into a history that is copied out once at the end.
 #include <cstring>
 
 #include "nb_state.h"
@@ -29,6 +31,9 @@ struct nb_ens {
     int64_t force_launches = 0;               // batched force launches since creation (kick + drift launches not counted)
     const char *last_kernel = "none";
     nb_sim *probe = nullptr;                  // solo handle of the members' shape: energies (created on first use)
+    double *epart = nullptr;                  // batched energies: members * tile pairs * {pe, ke} slots (created on first use)
+    double *ehist = nullptr;                  // batched energies: ehist_cap samples of kinetic, then as many of potential
+    int64_t ehist_cap = 0;
 };
 
 namespace {
@@ -82,10 +87,47 @@ int copy_out(nb_ens *e, void *dst, const void *src, size_t count, int on_device)
 void release(nb_ens *e)
 {
     if (e->probe) (void)nb_destroy(e->probe);
-    for (void *p : {e->prm, e->pos, e->pos_alt, e->vel, e->acc, e->mass})
+    for (void *p : {e->prm, e->pos, e->pos_alt, e->vel, e->acc, e->mass, (void *)e->epart, (void *)e->ehist})
         if (p) (void)hipFree(p);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
+}
+
+// room for `samples` samples of the batched energies (buffers grow, never shrink)
+int energy_buffers(nb_ens *e, int64_t samples)
+{
+    const size_t B = (size_t)e->cfg.members;
+    if (!e->epart) HIPCHK(hipMalloc((void **)&e->epart, B * nb_ens_energy_pairs(e->cfg.n) * 2 * sizeof(double)));
+    if (samples > e->ehist_cap) {
+        // no launch reads the old history: every call that fills it copies it out and waits before it returns
+        if (e->ehist) { (void)hipFree(e->ehist); e->ehist = nullptr; e->ehist_cap = 0; }
+        hipError_t he = hipMalloc((void **)&e->ehist, (size_t)samples * B * 2 * sizeof(double));
+        if (he != hipSuccess)
+            return fail(he == hipErrorOutOfMemory ? NB_ERR_OOM : NB_ERR_HIP, "energy history of %lld samples: %s",
+                        (long long)samples, hipGetErrorString(he));
+        e->ehist_cap = samples;
+    }
+    return NB_OK;
+}
+
+// sample `s` of the history: the resident state's energies, two launches behind whatever the stream holds
+int launch_energy(nb_ens *e, int64_t s, bool with_kinetic)
+{
+    const nb_ens_config &c = e->cfg;
+    HIPCHK(nb_launch_ens_energy(e->pos, with_kinetic ? e->vel : nullptr, e->mass, c.members, c.n, c.dim, e->is_f64, e->prm,
+                                e->epart, e->ehist, e->ehist + e->ehist_cap * c.members, s, e->stream));
+    return NB_OK;
+}
+
+// the first `samples` samples to the caller's arrays (either may be null), then the one wait of the call
+int history_out(nb_ens *e, int64_t samples, double *kinetic, double *potential, int on_device)
+{
+    const size_t bytes = (size_t)samples * e->cfg.members * sizeof(double);
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (kinetic) HIPCHK(hipMemcpyAsync(kinetic, e->ehist, bytes, kind, e->stream));
+    if (potential) HIPCHK(hipMemcpyAsync(potential, e->ehist + e->ehist_cap * e->cfg.members, bytes, kind, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return NB_OK;
 }
 
 }  // namespace
@@ -253,6 +295,54 @@ int nb_ens_energy(nb_ens *e, double *kinetic, double *potential)
         if (int rc = nb_energy(e->probe, kinetic ? kinetic + b : nullptr, potential ? potential + b : nullptr)) return rc;
     }
     return NB_OK;
+}
+
+int nb_ens_energies(nb_ens *e, double *kinetic, double *potential, int on_device)
+{
+    if (!e) return fail(NB_ERR_INVALID, "null handle");
+    if (!kinetic && !potential) return NB_OK;
+    if (!e->have_mass || !e->have_pos || (kinetic && !e->have_vel)) return fail(NB_ERR_INVALID, "state incomplete");
+    DeviceGuard guard(e->cfg.device);
+    if (int rc = energy_buffers(e, 1)) return rc;
+    if (int rc = launch_energy(e, 0, kinetic != nullptr)) return rc;
+    return history_out(e, 1, kinetic, potential, on_device);
+}
+
+// nb_ens_step's launches, with a sampled tick issued as the step loop issues it: the force launch only closes the tick
+// (velocities and positions are then what a reader sees), the two energy launches follow, and a separate kick + drift
+// launch opens the next tick.  Nothing waits on the stream before history_out.
+int nb_ens_run_recorded(nb_ens *e, int32_t nsteps, int32_t every, double *kinetic, double *potential, int64_t capacity,
+                        int on_device, int32_t *samples)
+{
+    if (!e) return fail(NB_ERR_INVALID, "null handle");
+    if (samples) *samples = 0;
+    if (!e->have_pos || !e->have_vel || !e->have_mass) return fail(NB_ERR_INVALID, "state incomplete");
+    if (!e->have_acc) return fail(NB_ERR_INVALID, "no accelerations yet: call nb_ens_compute_accelerations first");
+    if (nsteps < 0) return fail(NB_ERR_INVALID, "nsteps must be >= 0 (got %d)", nsteps);
+    if (every < 1) return fail(NB_ERR_INVALID, "every must be >= 1 (got %d)", every);
+    const int64_t S = 1 + nsteps / every;
+    if (capacity < S)
+        return fail(NB_ERR_INVALID, "capacity of %lld samples is below the %lld of %d ticks sampled every %d",
+                    (long long)capacity, (long long)S, nsteps, every);
+    DeviceGuard guard(e->cfg.device);
+    const nb_ens_config &c = e->cfg;
+    if (int rc = energy_buffers(e, S)) return rc;
+    if (int rc = launch_energy(e, 0, true)) return rc;
+    if (nsteps >= 1) HIPCHK(nb_launch_ens_kick_drift(e->pos, e->vel, e->acc, c.members, c.n, c.dim, e->is_f64, e->prm, e->stream));
+    for (int t = 1; t <= nsteps; ++t) {
+        const bool last = (t == nsteps), sampled = (t % every == 0);
+        if (sampled || last) {
+            if (int rc = launch_force(e, NB_KICK_CLOSE)) return rc;
+            if (sampled)
+                if (int rc = launch_energy(e, t / every, true)) return rc;
+            if (!last) HIPCHK(nb_launch_ens_kick_drift(e->pos, e->vel, e->acc, c.members, c.n, c.dim, e->is_f64, e->prm, e->stream));
+        } else {
+            if (int rc = launch_force(e, NB_KICK_CLOSE_OPEN)) return rc;
+            std::swap(e->pos, e->pos_alt);               // the launch wrote the drifted positions to the second buffer
+        }
+    }
+    if (samples) *samples = (int32_t)S;
+    return history_out(e, S, kinetic, potential, on_device);
 }
 
 int nb_ens_info(nb_ens *e, int32_t *members, int64_t *force_launches, const char **kernel_name)

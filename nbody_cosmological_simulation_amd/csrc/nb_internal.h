@@ -320,6 +320,15 @@ hipError_t nb_launch_ens_step(const void *pos_in, void *pos_out, void *vel, void
 // opening kick + drift of every member with its own dt (two roundings per line, like nb_launch_kick_drift)
 hipError_t nb_launch_ens_kick_drift(void *pos, void *vel, const void *acc, int members, int n, int dim, int is_f64,
                                     const void *prm, hipStream_t st);
+// ---- batched energies of an ensemble (nb_ens_energy.hip) -----------------------------------------------------------------
+// Two launches on `st`: per-tile-pair partial sums into part (members * nb_ens_energy_pairs(n) * 2 doubles, every slot
+// rewritten), then one wave per member that writes kinetic[sample * members + b] and potential[sample * members + b].
+// vel may be null (the kinetic entries are then 0).  G and eps2 come from the member's scalars in prm.
+constexpr int NB_ENS_ENERGY_TILE = 256;
+int nb_ens_energy_pairs(int n);     // tile pairs of the upper triangle: 136 at n = 4096
+hipError_t nb_launch_ens_energy(const void *pos, const void *vel, const void *mass, int members, int n, int dim, int is_f64,
+                                const void *prm, double *part, double *kinetic, double *potential, int64_t sample,
+                                hipStream_t st);
 // second half of nb_launch_force_quant_step with caller-provided min / max partials (nblocks pairs of doubles)
 hipError_t nb_launch_force_quant_finish(float *acc, int64_t count, int levels, const double *partials, int nblocks,
                                         double *mn_mx, int16_t *bins, float *vel, float *pos, double half_dt, double dt,

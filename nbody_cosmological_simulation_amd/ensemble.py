@@ -13,6 +13,13 @@ Unlike `GalaxySimulation`, the array attributes are SNAPSHOTS: `positions`, `vel
 `accelerations` return fresh (B, ...) tensors at every read, and in-place edits of them are not tracked.
 Writes go through `set_state`, `set_accelerations` and `set_params`.
 
+Energy curves -- what the sweeps above record -- stay on the device: `energies()` evaluates every member's kinetic
+and potential energy in one batched pass (two launches, csrc/nb_ens_energy.hip) and `run_recorded(num_ticks, every)`
+runs the ticks and samples the energies between them without a host round trip, returning an `EnergyHistory`.  Their
+values agree with `get_kinetic_energy()` / `get_potential_energy()` (which stay solo-equal bit for bit, one member
+at a time) to 1e-12 relative under FLOAT64 and 2e-6 under the other modes; `run_recorded` leaves the trajectory
+bit-identical to `run`.
+
 First version: FLOAT64 / FLOAT32 / BFLOAT16 / FLOAT16 modes; state already in its settled dtype (fp64
 tensors under FLOAT64, fp32 under the others); N up to the one-launch step's limit (4096 fp64, 3072 fp32) --
 above it a single system already fills the chip; B up to 1024; one device.  Not covered: the grid modes
@@ -21,7 +28,7 @@ subclass overrides, metrics, checkpoints, multi-GPU.
 """
 import ctypes as C
 import numbers
-from typing import Callable
+from typing import Callable, NamedTuple
 
 import torch
 
@@ -31,6 +38,7 @@ from .quantization import PrecisionMode, mode_code, _TORCH_TO_NB
 
 MAX_MEMBERS = 1024
 MAX_STARS = {torch.float64: 4096, torch.float32: 3072}     # the solo one-launch step's limits (csrc/nb_step.cpp)
+MAX_HISTORY_BYTES = 256 << 20         # an EnergyHistory's kinetic + potential samples (16 bytes per member and sample)
 _MODES = (PrecisionMode.FLOAT64, PrecisionMode.FLOAT32, PrecisionMode.BFLOAT16, PrecisionMode.FLOAT16)
 
 
@@ -93,6 +101,38 @@ def check_arguments(positions, velocities, masses, precision_mode=PrecisionMode.
                          "chip (use GalaxySimulation)")
     return (positions, velocities, masses, _param_list("G", G, B), _param_list("softening", softening, B),
             _param_list("dt", dt, B))
+
+
+def check_record_arguments(num_ticks, every, members) -> list:
+    """Validate run_recorded's arguments without touching a device.  Returns the tick offsets of the samples relative to
+    the tick at entry, [0, every, 2 * every, ...] up to num_ticks; raises TypeError / ValueError."""
+    for name, v in (("num_ticks", num_ticks), ("every", every), ("members", members)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise TypeError(f"{name} must be an int, got {type(v).__name__}")
+    num_ticks, every, members = int(num_ticks), int(every), int(members)
+    if num_ticks < 0:
+        raise ValueError(f"num_ticks must be >= 0, got {num_ticks}")
+    if every < 1:
+        raise ValueError(f"every must be >= 1, got {every}")
+    if members < 1:
+        raise ValueError(f"members must be >= 1, got {members}")
+    samples = 1 + num_ticks // every
+    if samples * members * 16 > MAX_HISTORY_BYTES:
+        raise ValueError(f"{samples} samples of {members} members are {samples * members * 16} bytes of history, above the "
+                         f"limit of {MAX_HISTORY_BYTES}: raise `every` (or record the run in shorter stretches)")
+    return list(range(0, num_ticks + 1, every))
+
+
+class EnergyHistory(NamedTuple):
+    """What run_recorded returns: `ticks[s]` is the absolute tick of sample s; `kinetic` and `potential` are float64
+    tensors of shape (samples, members)."""
+    ticks: list
+    kinetic: torch.Tensor
+    potential: torch.Tensor
+
+    @property
+    def total(self) -> torch.Tensor:
+        return self.kinetic + self.potential
 
 
 def _doubles(values):
@@ -213,7 +253,33 @@ class GalaxyEnsemble:
             if callback and done % callback_interval == 0:
                 callback(self, self.tick)
 
+    def run_recorded(self, num_ticks: int, every: int = 1) -> EnergyHistory:
+        """`num_ticks` ticks like run(), recording every member's kinetic and potential energy on the device: at entry and
+        after every `every`-th tick of this call.  One native call; nothing is copied to the host in between.  The
+        trajectory is bit-identical to run(num_ticks)."""
+        offsets = check_record_arguments(num_ticks, every, self.num_members)
+        S, B = len(offsets), self.num_members
+        ke = torch.empty((S, B), dtype=torch.float64, device=self.device)
+        pe = torch.empty((S, B), dtype=torch.float64, device=self.device)
+        got = C.c_int32()
+        N.check(N.lib().nb_ens_run_recorded(self._handle, int(num_ticks), int(every), C.c_void_p(ke.data_ptr()),
+                                            C.c_void_p(pe.data_ptr()), S, int(self.device.type == "cuda"), C.byref(got)))
+        if got.value != S:
+            raise RuntimeError(f"nb_ens_run_recorded wrote {got.value} samples, expected {S}")
+        ticks = [self.tick + o for o in offsets]
+        self.tick += int(num_ticks)
+        return EnergyHistory(ticks, ke, pe)
+
     # ------------------------------------------------------------------ reads
+    def energies(self):
+        """(kinetic, potential): float64 tensors of shape (B,) on `self.device`, all members evaluated in one batched
+        pass.  Equal to get_kinetic_energy() / get_potential_energy() to the project's bars, not bit for bit."""
+        ke = torch.empty(self.num_members, dtype=torch.float64, device=self.device)
+        pe = torch.empty(self.num_members, dtype=torch.float64, device=self.device)
+        N.check(N.lib().nb_ens_energies(self._handle, C.c_void_p(ke.data_ptr()), C.c_void_p(pe.data_ptr()),
+                                        int(self.device.type == "cuda")))
+        return ke, pe
+
     def _energy(self, kinetic, potential):
         B = self.num_members
         ke, pe = (C.c_double * B)(), (C.c_double * B)()
