@@ -146,16 +146,20 @@ int nb_energy(nb_sim *s, double *kinetic, double *potential);
  * same n, dim, precision mode and state dtype, each with its own state, G, softening and dt, and advances all
  * of them one tick per kernel launch.  No arithmetic crosses members; a member's state is bit-identical to
  * the nb_sim that takes the same steps on the one-launch small-system path.
- * Limits: modes NB_FLOAT64 .. NB_FLOAT16 (the grid modes need per-member tables: NB_ERR_UNSUPPORTED);
- * state of the settled dtype only (NB_F64 under NB_FLOAT64, NB_F32 otherwise); n at most the one-launch
- * step's limit (4096 fp64, 3072 fp32); 1 <= members <= 1024; one device, no communicator.
- * Arrays are whole (members, n, dim) / (members, n) row-major blocks, host or device as flagged. */
+ * Limits: nb_ens_create takes the modes NB_FLOAT64 .. NB_FLOAT16 (the grid modes need per-member tables:
+ * NB_ERR_UNSUPPORTED there) and nb_ens_create_grid takes NB_INT8_SIM, NB_INT4_SIM and NB_CUSTOM with up to 256
+ * levels per member; state of the settled dtype only (NB_F64 under NB_FLOAT64, NB_F32 otherwise); n at most
+ * the one-launch step's limit (4096 fp64, 3072 fp32); 1 <= members <= 1024; one device, no communicator.
+ * Arrays are whole (members, n, dim) / (members, n) row-major blocks, host or device as flagged.
+ * Grid modes: an evaluation is two launches over all members (max r^2 + tables, the pair sweep) and under
+ * INT8 / INT4 a third (force snap + kicks); every member has its own tables (49 KB of device memory each),
+ * built from its own exact max r^2, softening, G and level count, so they are the tables of its solo run. */
 typedef struct nb_ens nb_ens;
 typedef struct nb_ens_config {
     int32_t members;       /* B                                                              */
     int32_t n;             /* stars per member                                               */
     int32_t dim;           /* 2 or 3                                                         */
-    int32_t mode;          /* nb_mode, NB_FLOAT64 .. NB_FLOAT16                              */
+    int32_t mode;          /* nb_mode: NB_FLOAT64 .. NB_FLOAT16, or a grid mode (nb_ens_create_grid) */
     int32_t device;        /* HIP device ordinal                                             */
     int32_t flags;         /* 0                                                              */
 } nb_ens_config;
@@ -163,6 +167,13 @@ typedef struct nb_ens_config {
 /* G / softening_sq / dt: `members` doubles each (softening**2 evaluated by the caller, as in nb_config) */
 int nb_ens_create(nb_ens **out, const nb_ens_config *cfg, const double *G, const double *softening_sq,
                   const double *dt);
+/* The same for the grid modes: cfg->mode is NB_INT8_SIM, NB_INT4_SIM or NB_CUSTOM (any other:
+ * NB_ERR_UNSUPPORTED, as is n above the fp32 limit).  levels: under NB_CUSTOM `members` level counts, each in
+ * [2, 256] (else NB_ERR_INVALID), or NULL for 64 everywhere; under the other two modes it must be NULL (256 /
+ * 16 levels).  Levels are fixed for the life of the handle.  The handle is an ordinary nb_ens: every nb_ens_*
+ * entry works on it, and a member is bit-identical to the nb_sim of the same mode and levels. */
+int nb_ens_create_grid(nb_ens **out, const nb_ens_config *cfg, const int32_t *levels, const double *G,
+                       const double *softening_sq, const double *dt);
 int nb_ens_destroy(nb_ens *e);
 /* any array may be NULL to keep its values; the device copy is updated on the handle's stream */
 int nb_ens_set_params(nb_ens *e, const double *G, const double *softening_sq, const double *dt);
@@ -198,8 +209,13 @@ int nb_ens_run_recorded(nb_ens *e, int32_t nsteps, int32_t every, double *kineti
                         int64_t capacity, int on_device, int32_t *samples);
 /* members; batched force launches issued since creation (nb_ens_compute_accelerations and one per tick;
  * the opening kick + drift launch of an nb_ens_step is not counted); name of the last force kernel
- * ("ens_step_kernel", "none" before the first).  Any output may be NULL. */
+ * ("ens_step_kernel", or "ens_grid_step_kernel" on a grid-mode handle, whose table and finish launches are
+ * not counted either; "none" before the first).  Any output may be NULL. */
 int nb_ens_info(nb_ens *e, int32_t *members, int64_t *force_launches, const char **kernel_name);
+/* Grid-mode handles: out[8 b .. 8 b + 7] = member b's {lmin, lmax, fmin, fmax, r2max, fast_ok, fast_maxdev,
+ * fast_maxrel} of the LAST evaluation, the layout of nb_quant_debug's info (fmin / fmax NaN under NB_CUSTOM,
+ * which does not quantise forces).  NB_ERR_UNSUPPORTED on a handle of nb_ens_create. */
+int nb_ens_quant_info(nb_ens *e, double *out /* members * 8 */);
 int nb_ens_synchronize(nb_ens *e);
 
 /* ---- precision-hook introspection ---------------------------------------------------- */

@@ -34,7 +34,7 @@ EXPORTS = [
     "nb_kernel_time", "nb_force_kernel_name", "nb_pe_kernel_name", "nb_step_path_name", "nb_synchronize", "nb_device_count", "nb_abi_version", "nb_last_error",
     "nb_ens_create", "nb_ens_destroy", "nb_ens_set_params", "nb_ens_set_state", "nb_ens_get_state", "nb_ens_set_accelerations",
     "nb_ens_compute_accelerations", "nb_ens_step", "nb_ens_energy", "nb_ens_info", "nb_ens_synchronize",
-    "nb_ens_energies", "nb_ens_run_recorded",
+    "nb_ens_energies", "nb_ens_run_recorded", "nb_ens_create_grid", "nb_ens_quant_info",
 ]
 
 
@@ -125,6 +125,8 @@ def lib():
         "nb_abi_version": ([], C.c_int),
         "nb_last_error": ([], C.c_char_p),
         "nb_ens_create": ([C.POINTER(vp), C.POINTER(NbEnsConfig), pdbl, pdbl, pdbl], C.c_int),
+        "nb_ens_create_grid": ([C.POINTER(vp), C.POINTER(NbEnsConfig), pi32, pdbl, pdbl, pdbl], C.c_int),
+        "nb_ens_quant_info": ([vp, pdbl], C.c_int),
         "nb_ens_destroy": ([vp], C.c_int),
         "nb_ens_set_params": ([vp, pdbl, pdbl, pdbl], C.c_int),
         "nb_ens_set_state": ([vp, vp, vp, vp, C.c_int, C.c_int], C.c_int),

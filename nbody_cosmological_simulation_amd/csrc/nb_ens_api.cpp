@@ -4,14 +4,19 @@
 //
 // Layout: contiguous (B, N, D) positions (two buffers: they ping-pong as in the solo step), velocities, accelerations and
 // (B, N) masses in the storage type (fp64 under FLOAT64, else fp32), and a device array of NB_ENS_PARAM_WORDS scalars per
-// member, cast on the host exactly as the solo launch casts them.  A mode that needs more per member (the grid modes:
-// tables, force min / max) adds arrays beside these; nothing here is indexed by anything but the member.
+// member, cast on the host exactly as the solo launch casts them.  Nothing here is indexed by anything but the member.
+//
+// Grid modes (nb_ens_create_grid: INT8_SIM / INT4_SIM / CUSTOM, fp32 state) add, beside these: one GridTables and one level
+// count per member, and under INT8 / INT4 the force launch's per-workgroup {min, max} partials and a (B, 2) array of force
+// bounds.  An evaluation is then step_small's sequence (nb_step.cpp) batched: max r2 + tables, the grid step, and under
+// INT8 / INT4 the finish launch that snaps the forces and carries the kicks IN PLACE (no ping-pong of the positions).
 //
 // Energies are off the hot path and must equal a solo handle's bit for bit, whichever kernel variant the solo engine
 // picks for this shape and these masses: each member's slice is handed (device to device) to one solo handle of the same
 // shape kept for that purpose, and nb_energy runs there.  nb_ens_energies and nb_ens_run_recorded evaluate all members at
 // once instead (nb_ens_energy.hip: two launches on the handle's stream, values at the project's bars rather than the
 // solo engine's bits), the latter between the ticks of a run into a history that is copied out once at the end.
+#include <cstddef>
 #include <cstring>
 
 #include "nb_state.h"
@@ -34,6 +39,14 @@ struct nb_ens {
     double *epart = nullptr;                  // batched energies: members * tile pairs * {pe, ke} slots (created on first use)
     double *ehist = nullptr;                  // batched energies: ehist_cap samples of kinetic, then as many of potential
     int64_t ehist_cap = 0;
+    // grid modes only (nb_ens_create_grid)
+    bool grid = false, fq = false;            // HOOK_GRID; INT8 / INT4: forces snapped (and kicks applied) by the finish launch
+    int allow_fast = 1;                       // the table-free pair path may be used (NB_NO_GRID_FAST unset), as nb_sim reads it
+    int grid_blocks = 0;                      // workgroups per member of the grid step: min / max partials per member
+    std::vector<int32_t> levels;              // per member
+    GridTables *tabs = nullptr;               // device: one per member (max r2, arrival counter, the evaluation's tables)
+    int *levels_dev = nullptr;
+    double *fpart = nullptr, *fbounds = nullptr;   // INT8 / INT4: members * grid_blocks * 2 partials; members * {fmin, fmax}
 };
 
 namespace {
@@ -62,9 +75,33 @@ int upload_params(nb_ens *e)
     return NB_OK;
 }
 
+// one evaluation of a grid-mode ensemble, as step_small issues a solo one
+int launch_force_grid(nb_ens *e, int do_kick)
+{
+    const nb_ens_config &c = e->cfg;
+    HIPCHK(nb_launch_ens_r2max_tables((const float *)e->pos, c.members, c.n, c.dim, e->prm, e->tabs, e->levels_dev, 0.01f,
+                                      e->allow_fast, e->stream));
+    HIPCHK(nb_launch_ens_grid_step((const float *)e->pos, (float *)e->pos_alt, (float *)e->vel, (float *)e->acc,
+                                   (const float *)e->mass, c.members, c.n, c.dim, e->prm, e->fq ? NB_KICK_NONE : do_kick, e->lanes,
+                                   e->tabs, e->fq ? e->fpart : nullptr, e->stream));
+    if (e->fq)      // levels[0]: under INT8 / INT4 every member has the mode's 256 / 16 levels
+        HIPCHK(nb_launch_ens_force_quant_finish((float *)e->acc, c.members, c.n * c.dim, e->levels[0], e->fpart, e->grid_blocks,
+                                                e->fbounds, (float *)e->vel, (float *)e->pos, e->prm, do_kick, e->stream));
+    e->force_launches++;
+    e->last_kernel = "ens_grid_step_kernel";
+    return NB_OK;
+}
+
+// a NB_KICK_CLOSE_OPEN evaluation left the drifted positions in pos_alt (else in place: INT8 / INT4)
+inline void advance_positions(nb_ens *e)
+{
+    if (!e->fq) std::swap(e->pos, e->pos_alt);
+}
+
 int launch_force(nb_ens *e, int do_kick)
 {
     const nb_ens_config &c = e->cfg;
+    if (e->grid) return launch_force_grid(e, do_kick);
     HIPCHK(nb_launch_ens_step(e->pos, e->pos_alt, e->vel, e->acc, e->mass, c.members, c.n, c.dim, e->is_f64, e->hook, e->prm,
                               do_kick, e->lanes, e->stream));
     e->force_launches++;
@@ -87,7 +124,8 @@ int copy_out(nb_ens *e, void *dst, const void *src, size_t count, int on_device)
 void release(nb_ens *e)
 {
     if (e->probe) (void)nb_destroy(e->probe);
-    for (void *p : {e->prm, e->pos, e->pos_alt, e->vel, e->acc, e->mass, (void *)e->epart, (void *)e->ehist})
+    for (void *p : {e->prm, e->pos, e->pos_alt, e->vel, e->acc, e->mass, (void *)e->epart, (void *)e->ehist, (void *)e->tabs,
+                    (void *)e->levels_dev, (void *)e->fpart, (void *)e->fbounds})
         if (p) (void)hipFree(p);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
@@ -130,21 +168,20 @@ int history_out(nb_ens *e, int64_t samples, double *kinetic, double *potential, 
     return NB_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int nb_ens_create(nb_ens **out, const nb_ens_config *cfg, const double *G, const double *softening_sq, const double *dt)
+// what both constructors ask of the shape
+int check_shape(const nb_ens_config *cfg)
 {
-    if (!out || !cfg || !G || !softening_sq || !dt) return fail(NB_ERR_INVALID, "null argument");
-    *out = nullptr;
     if (cfg->members < 1 || cfg->members > NB_ENS_MAX_MEMBERS)
         return fail(NB_ERR_INVALID, "members must be in [1, %d] (got %d)", NB_ENS_MAX_MEMBERS, cfg->members);
     if (cfg->n < 1) return fail(NB_ERR_INVALID, "n must be >= 1 (got %d)", cfg->n);
     if (cfg->dim != 2 && cfg->dim != 3) return fail(NB_ERR_INVALID, "dim must be 2 or 3 (got %d)", cfg->dim);
-    if (cfg->mode < NB_FLOAT64 || cfg->mode > NB_FLOAT16)
-        return fail(NB_ERR_UNSUPPORTED, "ensembles run the FLOAT64, FLOAT32, BFLOAT16 and FLOAT16 modes (got mode %d): the grid "
-                                        "modes need per-member tables", cfg->mode);
+    return NB_OK;
+}
+
+// levels: null for the cast modes, else `members` checked level counts (a grid-mode handle)
+int create(nb_ens **out, const nb_ens_config *cfg, const int32_t *levels, const double *G, const double *softening_sq,
+           const double *dt)
+{
     const bool f64 = cfg->mode == NB_FLOAT64;
     if (cfg->n > small_max_n(f64))
         return fail(NB_ERR_UNSUPPORTED, "n = %d is above the one-launch step's limit of %d for this mode: a single system of "
@@ -176,13 +213,67 @@ int nb_ens_create(nb_ens **out, const nb_ens_config *cfg, const double *G, const
     if (he == hipSuccess) he = hipMalloc(&e->acc, nd_bytes);
     if (he == hipSuccess) he = hipMalloc(&e->mass, cnt_n(e) * el(e));
     if (he == hipSuccess) he = hipMemsetAsync(e->acc, 0, nd_bytes, e->stream);
+    if (levels) {
+        e->grid = true;
+        e->fq = cfg->mode != NB_CUSTOM;
+        e->allow_fast = knobs.no_grid_fast ? 0 : 1;
+        e->grid_blocks = nb_ens_grid_blocks(cfg->n, e->lanes);
+        e->levels.assign(levels, levels + B);
+        const size_t part_bytes = (size_t)B * e->grid_blocks * 2 * sizeof(double);
+        // zeroed once: every evaluation puts a member's maximum and arrival counter back (grid_tables_body)
+        if (he == hipSuccess) he = hipMalloc((void **)&e->tabs, (size_t)B * sizeof(GridTables));
+        if (he == hipSuccess) he = hipMemsetAsync(e->tabs, 0, (size_t)B * sizeof(GridTables), e->stream);
+        if (he == hipSuccess) he = hipMalloc((void **)&e->levels_dev, (size_t)B * sizeof(int));
+        if (he == hipSuccess) he = hipMemcpyAsync(e->levels_dev, e->levels.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, e->stream);
+        if (e->fq) {      // CUSTOM does not quantise forces: no partials, no bounds
+            if (he == hipSuccess) he = hipMalloc((void **)&e->fpart, part_bytes);
+            if (he == hipSuccess) he = hipMemsetAsync(e->fpart, 0, part_bytes, e->stream);
+            if (he == hipSuccess) he = hipMalloc((void **)&e->fbounds, (size_t)B * 2 * sizeof(double));
+            if (he == hipSuccess) he = hipMemsetAsync(e->fbounds, 0, (size_t)B * 2 * sizeof(double), e->stream);
+        }
+    }
     if (he != hipSuccess) {
         release(e);
         return fail(he == hipErrorOutOfMemory ? NB_ERR_OOM : NB_ERR_HIP, "ensemble allocation failed: %s", hipGetErrorString(he));
     }
-    if (int rc = upload_params(e)) { release(e); return rc; }
+    if (int rc = upload_params(e)) { release(e); return rc; }      // (waits: the level counts have left e->levels)
     *out = e;
     return NB_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nb_ens_create(nb_ens **out, const nb_ens_config *cfg, const double *G, const double *softening_sq, const double *dt)
+{
+    if (!out || !cfg || !G || !softening_sq || !dt) return fail(NB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (int rc = check_shape(cfg)) return rc;
+    if (cfg->mode < NB_FLOAT64 || cfg->mode > NB_FLOAT16)
+        return fail(NB_ERR_UNSUPPORTED, "ensembles run the FLOAT64, FLOAT32, BFLOAT16 and FLOAT16 modes (got mode %d): the grid "
+                                        "modes need per-member tables", cfg->mode);
+    return create(out, cfg, nullptr, G, softening_sq, dt);
+}
+
+int nb_ens_create_grid(nb_ens **out, const nb_ens_config *cfg, const int32_t *levels, const double *G, const double *softening_sq,
+                       const double *dt)
+{
+    if (!out || !cfg || !G || !softening_sq || !dt) return fail(NB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (int rc = check_shape(cfg)) return rc;
+    if (cfg->mode != NB_INT8_SIM && cfg->mode != NB_INT4_SIM && cfg->mode != NB_CUSTOM)
+        return fail(NB_ERR_UNSUPPORTED, "nb_ens_create_grid runs the INT8_SIM, INT4_SIM and CUSTOM modes (got mode %d): the other "
+                                        "modes are nb_ens_create's", cfg->mode);
+    if (cfg->mode != NB_CUSTOM && levels)
+        return fail(NB_ERR_INVALID, "levels must be NULL under INT8_SIM / INT4_SIM (256 / 16 levels)");
+    std::vector<int32_t> lv(cfg->members, cfg->mode == NB_INT8_SIM ? 256 : cfg->mode == NB_INT4_SIM ? 16 : 64);
+    if (levels) lv.assign(levels, levels + cfg->members);
+    for (int b = 0; b < cfg->members; ++b)
+        if (lv[b] < 2 || lv[b] > NB_LUT_MIN)
+            return fail(NB_ERR_INVALID, "levels[%d] = %d is outside [2, %d]: above it a solo run leaves the one-launch step", b,
+                        lv[b], NB_LUT_MIN);
+    return create(out, cfg, lv.data(), G, softening_sq, dt);
 }
 
 int nb_ens_destroy(nb_ens *e)
@@ -266,7 +357,7 @@ int nb_ens_step(nb_ens *e, int32_t nsteps)
     for (int t = 0; t < nsteps; ++t) {
         const bool last = (t + 1 == nsteps);
         if (int rc = launch_force(e, last ? NB_KICK_CLOSE : NB_KICK_CLOSE_OPEN)) return rc;
-        if (!last) std::swap(e->pos, e->pos_alt);       // the launch wrote the drifted positions to the second buffer
+        if (!last) advance_positions(e);                // the launch wrote the drifted positions to the second buffer
     }
     return NB_OK;
 }
@@ -338,7 +429,7 @@ int nb_ens_run_recorded(nb_ens *e, int32_t nsteps, int32_t every, double *kineti
             if (!last) HIPCHK(nb_launch_ens_kick_drift(e->pos, e->vel, e->acc, c.members, c.n, c.dim, e->is_f64, e->prm, e->stream));
         } else {
             if (int rc = launch_force(e, NB_KICK_CLOSE_OPEN)) return rc;
-            std::swap(e->pos, e->pos_alt);               // the launch wrote the drifted positions to the second buffer
+            advance_positions(e);                        // the launch wrote the drifted positions to the second buffer
         }
     }
     if (samples) *samples = (int32_t)S;
@@ -351,6 +442,30 @@ int nb_ens_info(nb_ens *e, int32_t *members, int64_t *force_launches, const char
     if (members) *members = e->cfg.members;
     if (force_launches) *force_launches = e->force_launches;
     if (kernel_name) *kernel_name = e->last_kernel;
+    return NB_OK;
+}
+
+int nb_ens_quant_info(nb_ens *e, double *out)
+{
+    if (!e || !out) return fail(NB_ERR_INVALID, "null argument");
+    if (!e->grid) return fail(NB_ERR_UNSUPPORTED, "quant info is only defined for the grid modes (nb_ens_create_grid)");
+    DeviceGuard guard(e->cfg.device);
+    const size_t B = (size_t)e->cfg.members;
+    // the scalars behind the tables of every member, not the 48 KB of tables in front of them
+    constexpr size_t off = offsetof(GridTables, lmin), width = sizeof(GridTables) - off;
+    std::vector<char> tail(B * width);
+    std::vector<double> fb(B * 2, __builtin_nan(""));
+    HIPCHK(hipMemcpy2DAsync(tail.data(), width, (const char *)e->tabs + off, sizeof(GridTables), width, B, hipMemcpyDeviceToHost,
+                            e->stream));
+    if (e->fq) HIPCHK(hipMemcpyAsync(fb.data(), e->fbounds, B * 2 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (size_t b = 0; b < B; ++b) {
+        GridTables h;                      // only the members from lmin on are filled in and read
+        memcpy((char *)&h + off, tail.data() + b * width, width);
+        double *o = out + b * 8;
+        o[0] = h.lmin; o[1] = h.lmax; o[2] = fb[2 * b]; o[3] = fb[2 * b + 1]; o[4] = h.r2max;
+        o[5] = h.fast_ok; o[6] = h.fast_maxdev; o[7] = h.fast_maxrel;
+    }
     return NB_OK;
 }
 

@@ -6,6 +6,9 @@
 // launch: gridDim.y = B, blockIdx.y picks the member, and every workgroup runs the solo step's body (nb_small_body.h) on
 // its member's slice of contiguous (B, N, D) / (B, N) buffers with the member's own scalars.  No arithmetic crosses
 // members, and a member's sums are rounded in the solo order (same lanes per target, same workgroup size).
+// The grid modes (INT8 / INT4 / CUSTOM) run small_grid_body the same way, each member with its own tables
+// (ens_grid_step_kernel); their max-r2 + tables launch is ens_r2max_tables_kernel (nb_force.hip) and the INT8 / INT4 force
+// snap ens_force_quant_finish_kernel (nb_misc.hip).
 #include "nb_small_body.h"
 #include "nb_internal.h"
 
@@ -31,6 +34,22 @@ ens_step_kernel(const T *__restrict__ pos_in, T *__restrict__ pos_out, T *__rest
     const size_t o = (size_t)b * n;
     small_step_body<T, D, HOOK, S, BS>(blockIdx.x, pos_in + o * D, pos_out + o * D, vel + o * D, acc + o * D, mass + o, n,
                                        p.G, p.eps2, p.half_dt, p.dt, do_kick, nullptr);
+}
+
+// grid hook: member b reads the tables its own max-r2 launch built (tabs[b]); under INT8 / INT4 (part != null) it leaves
+// one {min, max} pair of its forces per workgroup at part[(b * gridDim.x + blockIdx.x) * 2]
+template <int D, int S, int BS>
+__global__ void __launch_bounds__(BS)
+ens_grid_step_kernel(const float *__restrict__ pos_in, float *__restrict__ pos_out, float *__restrict__ vel,
+                     float *__restrict__ acc, const float *__restrict__ mass, int n, const EnsScalars<float> *__restrict__ prm,
+                     int do_kick, const GridTables *__restrict__ tabs, double *__restrict__ part)
+{
+    const int b = blockIdx.y;
+    const EnsScalars<float> p = prm[b];
+    const size_t o = (size_t)b * n;
+    small_grid_body<D, S, false, BS>(blockIdx.x, pos_in + o * D, pos_out + o * D, vel + o * D, acc + o * D, mass + o, n, p.G,
+                                     p.eps2, p.half_dt, p.dt, do_kick, tabs + b,
+                                     part ? part + (size_t)b * 2 * gridDim.x : nullptr, nullptr);
 }
 
 // opening kick + drift of a run (simulation.py:132,135) for every member with its own dt: v += a dt/2; x += v dt
@@ -71,6 +90,27 @@ hipError_t launch_e(const T *pos_in, T *pos_out, T *vel, T *acc, const T *mass, 
     return hipGetLastError();
 }
 
+template <int D>
+hipError_t launch_g(const float *pos_in, float *pos_out, float *vel, float *acc, const float *mass, int members, int n,
+                    const void *prm, int do_kick, int lanes, const GridTables *tabs, double *part, hipStream_t st)
+{
+    const EnsScalars<float> *p = (const EnsScalars<float> *)prm;
+#define NB_ENSG(SS)                                                                                                        \
+    do {                                                                                                                   \
+        if (nb_small_block(n) == 512)                                                                                      \
+            hipLaunchKernelGGL((ens_grid_step_kernel<D, SS, 512>), dim3((n + 512 / SS - 1) / (512 / SS), members),         \
+                               dim3(512), 0, st, pos_in, pos_out, vel, acc, mass, n, p, do_kick, tabs, part);              \
+        else                                                                                                               \
+            hipLaunchKernelGGL((ens_grid_step_kernel<D, SS, 256>), dim3((n + 256 / SS - 1) / (256 / SS), members),         \
+                               dim3(256), 0, st, pos_in, pos_out, vel, acc, mass, n, p, do_kick, tabs, part);              \
+    } while (0)
+    if (lanes == 64) NB_ENSG(64);
+    else if (lanes == 32) NB_ENSG(32);
+    else NB_ENSG(16);
+#undef NB_ENSG
+    return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t nb_launch_ens_step(const void *pos_in, void *pos_out, void *vel, void *acc, const void *mass, int members, int n,
@@ -95,6 +135,22 @@ hipError_t nb_launch_ens_step(const void *pos_in, void *pos_out, void *vel, void
     if (hook == HOOK_F16) return NB_EF(3, HOOK_F16);
     return NB_EF(3, HOOK_NONE);
 #undef NB_EF
+}
+
+int nb_ens_grid_blocks(int n, int lanes) { return (n + nb_small_block(n) / lanes - 1) / (nb_small_block(n) / lanes); }
+
+hipError_t nb_launch_ens_grid_step(const float *pos_in, float *pos_out, float *vel, float *acc, const float *mass, int members,
+                                   int n, int dim, const void *prm, int do_kick, int lanes, const GridTables *tabs, double *part,
+                                   hipStream_t st)
+{
+    if (dim != 2 && dim != 3) return hipErrorInvalidValue;
+    if (members < 1 || members > NB_ENS_MAX_MEMBERS || n < 1 || !tabs) return hipErrorInvalidValue;
+    if (lanes != 16 && lanes != 32 && lanes != 64) return hipErrorInvalidValue;
+    const int km = do_kick & NB_KICK_MODE_MASK;
+    if (km == NB_KICK_CLOSE_SPEC || (do_kick & NB_KICK_OPEN_ON_READ)) return hipErrorInvalidValue;
+    if (part && km != NB_KICK_NONE) return hipErrorInvalidValue;      // INT8 / INT4: the finish launch carries the kicks
+    if (dim == 2) return launch_g<2>(pos_in, pos_out, vel, acc, mass, members, n, prm, do_kick, lanes, tabs, part, st);
+    return launch_g<3>(pos_in, pos_out, vel, acc, mass, members, n, prm, do_kick, lanes, tabs, part, st);
 }
 
 hipError_t nb_launch_ens_kick_drift(void *pos, void *vel, const void *acc, int members, int n, int dim, int is_f64,

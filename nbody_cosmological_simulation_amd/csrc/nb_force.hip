@@ -959,6 +959,35 @@ r2max_tables_kernel(const float *__restrict__ pos, ForceGeom g, float eps2, Grid
     grid_tables_body<true>(tab, levels, G, eps2, min_val, nullptr, allow_fast, s_bits);
 }
 
+// The same for the B members of an ensemble (nb_ens handles) in one launch: blockIdx.z is the member, blockIdx.x / .y its
+// target block and source chunk as above, on the member's slice of the (B, N, D) positions.  Every member has its own
+// GridTables (maximum, arrival counter, tables), its own eps2 and G (prm: NB_ENS_PARAM_WORDS floats per member =
+// {G, eps2, dt / 2, dt}) and level count; the last workgroup OF A MEMBER to arrive builds that member's tables.  The maximum
+// is exact and the tables a function of it alone (grid_tables_body), so they are the tables a solo evaluation of the member
+// builds, however its workgroups were cut.  No workgroup waits for another.
+template <int D>
+__global__ void __launch_bounds__(NB_BLOCK)
+ens_r2max_tables_kernel(const float *__restrict__ pos, ForceGeom g, const float *__restrict__ prm, GridTables *__restrict__ tabs,
+                        const int *__restrict__ levels, float min_val, int allow_fast)
+{
+    static_assert(NB_BLOCK == NB_LUT_MIN, "the last workgroup runs the single-block tables code");
+    __shared__ unsigned int s_bits;
+    __shared__ int s_mine;
+    const int b = blockIdx.z;
+    GridTables *tab = tabs + b;
+    const float G = prm[b * NB_ENS_PARAM_WORDS], eps2 = prm[b * NB_ENS_PARAM_WORDS + 1];
+    r2max_block<D, 1, NB_R2MAX_SPLIT>(pos + (size_t)b * g.n * D, g, eps2, tab);
+    if (threadIdx.x == 0) {
+        __threadfence();
+        const unsigned int total = gridDim.x * gridDim.y;
+        s_mine = (atomicAdd(&tab->blocks_done, 1u) == total - 1) ? 1 : 0;
+        s_bits = s_mine ? atomicMax(&tab->r2max_bits, 0u) : 0u;
+    }
+    __syncthreads();
+    if (!s_mine) return;
+    grid_tables_body<true>(tab, levels[b], G, eps2, min_val, nullptr, allow_fast, s_bits);
+}
+
 // ------------------------------------------------------------------------------------------
 // Tracked max-r2 search (round 3): two launches per evaluation instead of six (+ tables).
 // Exactness argument as for the pruned search above, with the lower bound LB taken from the far pair of the LAST
@@ -1300,6 +1329,29 @@ hipError_t nb_launch_r2max_tables(const float *pos, const ForceGeom &g, int dim,
         constexpr int DD = decltype(D)::value;
         hipLaunchKernelGGL((r2max_tables_kernel<DD, 1>), grid, dim3(NB_BLOCK), 0, st, pos, g2, eps2, tab, levels, G, min_val,
                            allow_fast);
+        return hipGetLastError();
+    });
+}
+
+hipError_t nb_launch_ens_r2max_tables(const float *pos, int members, int n, int dim, const void *prm, GridTables *tabs,
+                                      const int *levels, float min_val, int allow_fast, hipStream_t st)
+{
+    if (members < 1 || members > NB_ENS_MAX_MEMBERS || n < 1 || !tabs || !levels || !prm) return hipErrorInvalidValue;
+    const int per_block = NB_BLOCK / NB_R2MAX_SPLIT;
+    const int gx = (n + per_block - 1) / per_block;
+    // as nb_launch_r2max_tables: about one workgroup per CU, counted over ALL members, and at least one chunk per member
+    int nch = 256 / (gx * members);
+    const int nch_max = (n + NB_TJ - 1) / NB_TJ;
+    nch = nch < 1 ? 1 : (nch > nch_max ? nch_max : nch);
+    int chunk = (n + nch - 1) / nch;
+    chunk = (chunk + NB_TJ - 1) / NB_TJ * NB_TJ;
+    ForceGeom g{};
+    g.n = n; g.j_begin = 0; g.j_end = n; g.chunk_len = chunk; g.nchunks = (n + chunk - 1) / chunk; g.r = 1;
+    const dim3 grid(gx, g.nchunks, members);
+    return dispatch_dim(dim, [&](auto D) {
+        constexpr int DD = decltype(D)::value;
+        hipLaunchKernelGGL((ens_r2max_tables_kernel<DD>), grid, dim3(NB_BLOCK), 0, st, pos, g, (const float *)prm, tabs, levels,
+                           min_val, allow_fast);
         return hipGetLastError();
     });
 }

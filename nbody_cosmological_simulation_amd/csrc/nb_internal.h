@@ -320,6 +320,23 @@ hipError_t nb_launch_ens_step(const void *pos_in, void *pos_out, void *vel, void
 // opening kick + drift of every member with its own dt (two roundings per line, like nb_launch_kick_drift)
 hipError_t nb_launch_ens_kick_drift(void *pos, void *vel, const void *acc, int members, int n, int dim, int is_f64,
                                     const void *prm, hipStream_t st);
+// The grid modes (INT8 / INT4 / CUSTOM, fp32 state), three launches per evaluation, each over all members:
+//   nb_launch_ens_r2max_tables        max r2 of every member and, by the member's last workgroup, its tables (tabs: `members`
+//                                     GridTables, zeroed once; levels: device, `members` ints in [2, NB_LUT_MIN])
+//   nb_launch_ens_grid_step           the solo grid step's body (nb_small_body.h small_grid_body) on every member with
+//                                     tabs[b]; part (INT8 / INT4, else null): members * nb_ens_grid_blocks * 2 doubles, one
+//                                     {min, max} of the forces per workgroup -- the kicks are then the finish launch's
+//   nb_launch_ens_force_quant_finish  INT8 / INT4: folds a member's partials into bounds[2 b] = {min, max}, snaps its
+//                                     count = n * dim forces to `levels` values and applies the kicks in place; `levels` is
+//                                     ONE value for all members (256 or 16: the force grid is the mode's, not CUSTOM's)
+int nb_ens_grid_blocks(int n, int lanes);     // workgroups per member of nb_launch_ens_grid_step
+hipError_t nb_launch_ens_r2max_tables(const float *pos, int members, int n, int dim, const void *prm, GridTables *tabs,
+                                      const int *levels, float min_val, int allow_fast, hipStream_t st);
+hipError_t nb_launch_ens_grid_step(const float *pos_in, float *pos_out, float *vel, float *acc, const float *mass, int members,
+                                   int n, int dim, const void *prm, int do_kick, int lanes, const GridTables *tabs, double *part,
+                                   hipStream_t st);
+hipError_t nb_launch_ens_force_quant_finish(float *acc, int members, int count, int levels, const double *partials, int nblocks,
+                                            double *bounds, float *vel, float *pos, const void *prm, int kick, hipStream_t st);
 // ---- batched energies of an ensemble (nb_ens_energy.hip) -----------------------------------------------------------------
 // Two launches on `st`: per-tile-pair partial sums into part (members * nb_ens_energy_pairs(n) * 2 doubles, every slot
 // rewritten), then one wave per member that writes kinetic[sample * members + b] and potential[sample * members + b].

@@ -293,6 +293,53 @@ force_quant_finish_kernel(float *__restrict__ acc, int64_t count, int levels, co
     }
 }
 
+// The same for the B members of an ensemble (nb_ens handles) in one launch: blockIdx.y is the member.  Every block folds
+// ITS member's nblocks partials (partials: members * nblocks pairs), block 0 of a member leaves {min, max} in
+// bounds[2 b], and the member's count = n * D forces are snapped and kicked with the member's own dt
+// (prm: NB_ENS_PARAM_WORDS floats per member = {G, eps2, (float)(dt / 2), (float)dt}, the casts of the solo launch).
+__global__ void __launch_bounds__(256)
+ens_force_quant_finish_kernel(float *__restrict__ acc, int count, int levels, const double *__restrict__ partials, int nblocks,
+                              double *__restrict__ bounds, float *__restrict__ vel, float *__restrict__ pos,
+                              const float *__restrict__ prm, int kick)
+{
+    __shared__ double s_mn[4], s_mx[4];
+    __shared__ double s_out[2];
+    const int m = blockIdx.y;
+    const double *mine = partials + (size_t)m * 2 * nblocks;
+    double dmn = __builtin_inf(), dmx = -__builtin_inf();
+    for (int w = threadIdx.x; w < nblocks; w += 256) {      // one pair per workgroup of the member's force launch
+        dmn = nan_min(dmn, mine[2 * w]);
+        dmx = nan_max(dmx, mine[2 * w + 1]);
+    }
+    minmax_fold<double>(dmn, dmx, s_mn, s_mx);
+    if (threadIdx.x == 0) {
+        s_out[0] = dmn;
+        s_out[1] = dmx;
+        if (blockIdx.x == 0) { bounds[2 * m] = dmn; bounds[2 * m + 1] = dmx; }
+    }
+    __syncthreads();
+    const float mn = (float)s_out[0], mx = (float)s_out[1];
+    const float range = __fsub_rn(mx, mn);
+    const bool passthrough = range < 1e-10f;
+    const float lm1 = (float)(levels - 1);
+    const float half_dt = prm[m * NB_ENS_PARAM_WORDS + 2], dt = prm[m * NB_ENS_PARAM_WORDS + 3];
+    const size_t o = (size_t)m * count;
+    for (int k = blockIdx.x * 256 + threadIdx.x; k < count; k += gridDim.x * 256) {
+        const size_t idx = o + k;
+        float a = acc[idx];
+        if (!passthrough) a = lin_quant<float>(a, mn, range, lm1, nullptr);
+        acc[idx] = a;
+        if (kick != NB_KICK_NONE) {
+            float v = axpy1(vel[idx], a, half_dt);
+            if (kick == NB_KICK_CLOSE_OPEN) {
+                v = axpy1(v, a, half_dt);
+                pos[idx] = axpy1(pos[idx], v, dt);
+            }
+            vel[idx] = v;
+        }
+    }
+}
+
 // quantization.py:91-127 elementwise part (tensor-level hook: log/exp per element)
 template <typename T>
 __global__ void __launch_bounds__(EW_BLOCK)
@@ -622,6 +669,18 @@ hipError_t nb_launch_force_quant_finish(float *acc, int64_t count, int levels, c
     grid = grid > 2048 ? 2048 : grid;
     hipLaunchKernelGGL(force_quant_finish_kernel, dim3(grid), dim3(256), 0, st, acc, count, levels, partials, nblocks, mn_mx,
                        bins, vel, pos, (float)half_dt, (float)dt, kick, packed, np, dim);
+    return hipGetLastError();
+}
+
+hipError_t nb_launch_ens_force_quant_finish(float *acc, int members, int count, int levels, const double *partials, int nblocks,
+                                            double *bounds, float *vel, float *pos, const void *prm, int kick, hipStream_t st)
+{
+    if (members < 1 || members > NB_ENS_MAX_MEMBERS || count < 1 || nblocks < 1 || levels < 2) return hipErrorInvalidValue;
+    if (kick != NB_KICK_NONE && kick != NB_KICK_CLOSE && kick != NB_KICK_CLOSE_OPEN) return hipErrorInvalidValue;
+    int gx = (count + 255) / 256;
+    gx = gx > 2048 ? 2048 : gx;
+    hipLaunchKernelGGL(ens_force_quant_finish_kernel, dim3(gx, members), dim3(256), 0, st, acc, count, levels, partials, nblocks,
+                       bounds, vel, pos, (const float *)prm, kick);
     return hipGetLastError();
 }
 

@@ -20,14 +20,24 @@ values agree with `get_kinetic_energy()` / `get_potential_energy()` (which stay 
 at a time) to 1e-12 relative under FLOAT64 and 2e-6 under the other modes; `run_recorded` leaves the trajectory
 bit-identical to `run`.
 
-First version: FLOAT64 / FLOAT32 / BFLOAT16 / FLOAT16 modes; state already in its settled dtype (fp64
+`GalaxyEnsemble` runs the FLOAT64 / FLOAT32 / BFLOAT16 / FLOAT16 modes; state already in its settled dtype (fp64
 tensors under FLOAT64, fp32 under the others); N up to the one-launch step's limit (4096 fp64, 3072 fp32) --
-above it a single system already fills the chip; B up to 1024; one device.  Not covered: the grid modes
-(INT8 / INT4 / CUSTOM), per-member tick counts, mixed dtypes and the fp32 -> fp64 promotion timeline,
-subclass overrides, metrics, checkpoints, multi-GPU.
+above it a single system already fills the chip; B up to 1024; one device.
+
+The grid modes -- what the reference's stability_test.py (INT8, INT4) and falsification_tests.py:44-104 (the number of
+grid levels itself) and :284-356 (softening and time step under a 16-level grid) sweep -- are `QuantizedEnsemble`'s:
+INT8_SIM, INT4_SIM and CUSTOM with `custom_levels` per member (2 .. 256), fp32 state, N up to 3072.  Every member has
+its own quantisation tables, built on the device from its own exact max r^2, softening, G and level count, so they are
+the tables of its solo run and the member stays bit-identical to `GalaxySimulation(custom_levels=levels[b])`.  A tick
+is two launches over all members (max r^2 + tables, pair sweep) and under INT8 / INT4 a third (force snap + kicks);
+`quant_debug()` reads every member's grid bounds back.  It inherits everything else from `GalaxyEnsemble`.
+
+Not covered: more than 256 levels, mixed modes within one ensemble, per-member tick counts, mixed dtypes and the
+fp32 -> fp64 promotion timeline, subclass overrides, metrics, checkpoints, multi-GPU.
 """
 import ctypes as C
 import numbers
+from collections.abc import Sequence
 from typing import Callable, NamedTuple
 
 import torch
@@ -40,6 +50,9 @@ MAX_MEMBERS = 1024
 MAX_STARS = {torch.float64: 4096, torch.float32: 3072}     # the solo one-launch step's limits (csrc/nb_step.cpp)
 MAX_HISTORY_BYTES = 256 << 20         # an EnergyHistory's kinetic + potential samples (16 bytes per member and sample)
 _MODES = (PrecisionMode.FLOAT64, PrecisionMode.FLOAT32, PrecisionMode.BFLOAT16, PrecisionMode.FLOAT16)
+_GRID_MODES = (PrecisionMode.INT8_SIM, PrecisionMode.INT4_SIM, PrecisionMode.CUSTOM)
+MIN_LEVELS, MAX_LEVELS = 2, 256       # MAX_LEVELS: above it the solo engine leaves the one-launch step (csrc/nb_step.cpp)
+DEFAULT_CUSTOM_LEVELS = 64            # the reference's default (quantization.py:67)
 
 
 def state_dtype(precision_mode) -> torch.dtype:
@@ -69,13 +82,18 @@ def check_arguments(positions, velocities, masses, precision_mode=PrecisionMode.
     if precision_mode not in _MODES:
         raise ValueError(f"GalaxyEnsemble runs the FLOAT64, FLOAT32, BFLOAT16 and FLOAT16 modes; {precision_mode.name} needs "
                          "per-member quantisation tables (use GalaxySimulation)")
+    return _check_state(positions, velocities, masses, precision_mode, G, softening, dt)
+
+
+def _check_state(positions, velocities, masses, precision_mode, G, softening, dt, more_lists=()):
+    """check_arguments behind the mode check; more_lists: lengths of further per-member lists a lone galaxy is broadcast over."""
     for name, t in (("positions", positions), ("velocities", velocities), ("masses", masses)):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{name} must be a torch.Tensor")
     if positions.dim() == 2 and masses.dim() == 1:
         # one galaxy under a parameter sweep: as many members as the longest parameter list
         lens = [len(p) for p in (_param_list("G", G, None), _param_list("softening", softening, None),
-                                 _param_list("dt", dt, None)) if p is not None]
+                                 _param_list("dt", dt, None)) if p is not None] + list(more_lists)
         members = max(lens) if lens else 1
         if velocities.dim() != 2:
             raise ValueError(f"velocities must be (N, D) like positions, got {tuple(velocities.shape)}")
@@ -101,6 +119,55 @@ def check_arguments(positions, velocities, masses, precision_mode=PrecisionMode.
                          "chip (use GalaxySimulation)")
     return (positions, velocities, masses, _param_list("G", G, B), _param_list("softening", softening, B),
             _param_list("dt", dt, B))
+
+
+def _level_list(value):
+    """custom_levels as given -> None, an int, or a list of ints (entries type-checked, not yet range- or length-checked)."""
+    if value is None:
+        return None
+    if isinstance(value, torch.Tensor) or type(value).__module__ == "numpy" and hasattr(value, "tolist"):
+        value = value.tolist()                # tensors and numpy arrays / scalars -> Python ints (or lists of them)
+    elif isinstance(value, Sequence) and not isinstance(value, (str, bytes)):
+        value = list(value)                   # range and the like
+    entries = value if isinstance(value, (list, tuple)) else [value]
+    for v in entries:
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise TypeError(f"custom_levels must be an int or a sequence of ints, got {type(v).__name__}")
+    return [int(v) for v in value] if isinstance(value, (list, tuple)) else int(value)
+
+
+def check_grid_arguments(positions, velocities, masses, precision_mode=PrecisionMode.INT8_SIM, custom_levels=None, G=0.001,
+                         softening=0.1, dt=0.01):
+    """Validate QuantizedEnsemble's constructor arguments without touching a device.  Returns (positions, velocities,
+    masses, levels, G, softening, dt) with the tensors shaped (B, N, D) / (B, N) and levels and the parameters as length-B
+    lists; raises ValueError / TypeError."""
+    if not isinstance(precision_mode, PrecisionMode):
+        raise TypeError(f"precision_mode must be a PrecisionMode, got {type(precision_mode).__name__}")
+    if precision_mode not in _GRID_MODES:
+        raise ValueError(f"QuantizedEnsemble runs the INT8_SIM, INT4_SIM and CUSTOM modes; {precision_mode.name} is "
+                         "GalaxyEnsemble's")
+    levels = _level_list(custom_levels)
+    if precision_mode != PrecisionMode.CUSTOM and levels is not None:
+        fixed = 256 if precision_mode == PrecisionMode.INT8_SIM else 16
+        raise ValueError(f"custom_levels belongs to the CUSTOM mode: {precision_mode.name} has {fixed} levels (pass None)")
+    for v in (levels if isinstance(levels, list) else [levels] if levels is not None else []):
+        if not MIN_LEVELS <= v <= MAX_LEVELS:
+            raise ValueError(f"custom_levels must be in [{MIN_LEVELS}, {MAX_LEVELS}], got {v}: above {MAX_LEVELS} a solo run "
+                             "leaves the one-launch step, so a member would have no bit-identical counterpart")
+    positions, velocities, masses, G, softening, dt = _check_state(
+        positions, velocities, masses, precision_mode, G, softening, dt, [len(levels)] if isinstance(levels, list) else [])
+    B = int(positions.shape[0])
+    if precision_mode == PrecisionMode.INT8_SIM:
+        levels = [256] * B
+    elif precision_mode == PrecisionMode.INT4_SIM:
+        levels = [16] * B
+    elif levels is None:
+        levels = [DEFAULT_CUSTOM_LEVELS] * B
+    elif not isinstance(levels, list):
+        levels = [levels] * B
+    elif len(levels) != B:
+        raise ValueError(f"custom_levels has {len(levels)} entries for {B} members")
+    return positions, velocities, masses, levels, G, softening, dt
 
 
 def check_record_arguments(num_ticks, every, members) -> list:
@@ -147,6 +214,10 @@ class GalaxyEnsemble:
         self._handle = C.c_void_p()
         positions, velocities, masses, self.G, self.softening, self.dt = check_arguments(
             positions, velocities, masses, precision_mode, G, softening, dt)
+        self._construct(positions, velocities, masses, precision_mode, device)
+
+    def _construct(self, positions, velocities, masses, precision_mode, device):
+        """Everything behind the argument checks: the native handle, the upload and the initial accelerations."""
         self.device = torch.device(device) if device is not None else positions.device
         self.precision_mode = precision_mode
         self.num_members, self.num_stars, self._dim = (int(v) for v in positions.shape)
@@ -158,12 +229,15 @@ class GalaxyEnsemble:
             dev = runtime.default_hip_device()
         cfg = N.NbEnsConfig(members=self.num_members, n=self.num_stars, dim=self._dim, mode=mode_code(precision_mode),
                             device=int(dev), flags=0)
-        N.check(N.lib().nb_ens_create(C.byref(self._handle), C.byref(cfg), _doubles(self.G),
-                                      _doubles([s ** 2 for s in self.softening]), _doubles(self.dt)))
+        self._create(cfg)
         self.set_state(positions=positions, velocities=velocities, masses=masses)
         N.check(N.lib().nb_ens_compute_accelerations(self._handle))
 
     # ------------------------------------------------------------------ native plumbing
+    def _create(self, cfg):
+        N.check(N.lib().nb_ens_create(C.byref(self._handle), C.byref(cfg), _doubles(self.G),
+                                      _doubles([s ** 2 for s in self.softening]), _doubles(self.dt)))
+
     def close(self):
         """Release the native handle (device buffers, stream) now instead of at garbage collection."""
         h = getattr(self, "_handle", None)
@@ -326,3 +400,33 @@ class GalaxyEnsemble:
 
     def synchronize(self):
         N.check(N.lib().nb_ens_synchronize(self._handle))
+
+
+class QuantizedEnsemble(GalaxyEnsemble):
+    """A GalaxyEnsemble under INT8_SIM, INT4_SIM or CUSTOM: every member with its own quantisation tables and, under
+    CUSTOM, its own number of grid levels (`custom_levels`: None = 64, an int, or one per member; 2 .. 256).  `levels` holds
+    the B level counts in force; they are fixed for the life of the object (see the module docstring)."""
+
+    def __init__(self, positions, velocities, masses, precision_mode=PrecisionMode.INT8_SIM, custom_levels=None,
+                 G=0.001, softening=0.1, dt=0.01, device=None):
+        self._handle = C.c_void_p()
+        positions, velocities, masses, self.levels, self.G, self.softening, self.dt = check_grid_arguments(
+            positions, velocities, masses, precision_mode, custom_levels, G, softening, dt)
+        self._construct(positions, velocities, masses, precision_mode, device)
+
+    def _create(self, cfg):
+        levels = (C.c_int32 * len(self.levels))(*self.levels) if self.precision_mode == PrecisionMode.CUSTOM else None
+        N.check(N.lib().nb_ens_create_grid(C.byref(self._handle), C.byref(cfg), levels, _doubles(self.G),
+                                           _doubles([s ** 2 for s in self.softening]), _doubles(self.dt)))
+
+    def quant_debug(self) -> dict:
+        """Grid internals of every member's last force evaluation, as GalaxySimulation.quant_debug() gives them for a solo
+        run: length-B numpy arrays `lmin`, `lmax` (log grid on r^2), `r2max`, `fmin`, `fmax` (linear force grid; NaN under
+        CUSTOM, which does not quantise forces), `fast_path` (bool: the table-free pair path was enabled) and `levels`."""
+        import numpy as np
+        B = self.num_members
+        info = (C.c_double * (8 * B))()
+        N.check(N.lib().nb_ens_quant_info(self._handle, info))
+        a = np.asarray(info, np.float64).reshape(B, 8)
+        return dict(lmin=a[:, 0].copy(), lmax=a[:, 1].copy(), fmin=a[:, 2].copy(), fmax=a[:, 3].copy(), r2max=a[:, 4].copy(),
+                    fast_path=a[:, 5] != 0, levels=np.asarray(self.levels, np.int64))

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""VGPR / scratch / occupancy table of the kernels of one .hip file (hipcc -Rpass-analysis=kernel-resource-usage).
+"""VGPR / SGPR / scratch / occupancy table of the kernels of one .hip file (hipcc -Rpass-analysis=kernel-resource-usage).
 
     python tools/kernel_resources.py nbody_cosmological_simulation_amd/csrc/nb_force_sym.hip [name-filter]
 """
@@ -22,7 +22,7 @@ def main():
             continue
         g = lambda k: (re.search(k + r": (\d+)", b) or [None, "?"])[1]
         scr, occ, lds = g(r"ScratchSize \[bytes/lane\]"), g(r"Occupancy \[waves/SIMD\]"), g(r"LDS Size \[bytes/block\]")
-        print(f"{dem:70s} VGPR {g('VGPRs'):>3s} spill {g('VGPRs Spill'):>3s} scratch {scr:>4s} occ {occ} LDS {lds}")
+        print(f"{dem:70s} VGPR {g('VGPRs'):>3s} SGPR {g('SGPRs'):>3s} spill {g('VGPRs Spill'):>3s} scratch {scr:>4s} occ {occ} LDS {lds}")
 
 
 if __name__ == "__main__":
