@@ -217,7 +217,7 @@ int create(nb_ens **out, const nb_ens_config *cfg, const int32_t *levels, const 
         e->grid = true;
         e->fq = cfg->mode != NB_CUSTOM;
         e->allow_fast = knobs.no_grid_fast ? 0 : 1;
-        e->grid_blocks = nb_ens_grid_blocks(cfg->n, e->lanes);
+        e->grid_blocks = nb_small_blocks(cfg->n, e->lanes);
         e->levels.assign(levels, levels + B);
         const size_t part_bytes = (size_t)B * e->grid_blocks * 2 * sizeof(double);
         // zeroed once: every evaluation puts a member's maximum and arrival counter back (grid_tables_body)

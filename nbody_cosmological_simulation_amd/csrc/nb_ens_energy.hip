@@ -17,6 +17,7 @@
 //          quotient; each term is added into an fp64 sum
 //   kinetic  m * (sum_k v_k^2) in T, one rounding per operation, added into an fp64 sum
 #include "nb_device.h"
+#include "nb_dispatch.h"
 #include "nb_internal.h"
 
 namespace {
@@ -167,24 +168,6 @@ ens_energy_finish_kernel(const double *__restrict__ part, int npairs, int member
     }
 }
 
-template <typename T>
-hipError_t launch_t(const T *pos, const T *vel, const T *mass, int members, int n, int dim, const void *prm, double *part,
-                    double *kinetic, double *potential, int64_t sample, hipStream_t st)
-{
-    const EnsScalars<T> *p = (const EnsScalars<T> *)prm;
-    const int ntiles = (n + EE_TILE - 1) / EE_TILE, npairs = nb_ens_energy_pairs(n);
-    const dim3 grid(npairs, members);
-    if (dim == 2)
-        hipLaunchKernelGGL((ens_energy_partials_kernel<T, 2>), grid, dim3(EE_TILE), 0, st, pos, vel, mass, n, ntiles, p, part);
-    else
-        hipLaunchKernelGGL((ens_energy_partials_kernel<T, 3>), grid, dim3(EE_TILE), 0, st, pos, vel, mass, n, ntiles, p, part);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL((ens_energy_finish_kernel<T>), dim3(members), dim3(64), 0, st, (const double *)part, npairs, members, p,
-                       kinetic, potential, sample);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 int nb_ens_energy_pairs(int n)
@@ -199,9 +182,19 @@ hipError_t nb_launch_ens_energy(const void *pos, const void *vel, const void *ma
 {
     if (members < 1 || members > NB_ENS_MAX_MEMBERS || n < 1 || (dim != 2 && dim != 3)) return hipErrorInvalidValue;
     if (!pos || !mass || !prm || !part || !kinetic || !potential || sample < 0) return hipErrorInvalidValue;
-    if (is_f64)
-        return launch_t<double>((const double *)pos, (const double *)vel, (const double *)mass, members, n, dim, prm, part,
-                                kinetic, potential, sample, st);
-    return launch_t<float>((const float *)pos, (const float *)vel, (const float *)mass, members, n, dim, prm, part, kinetic,
-                           potential, sample, st);
+    const int ntiles = (n + EE_TILE - 1) / EE_TILE, npairs = nb_ens_energy_pairs(n);
+    const dim3 grid(npairs, members);
+    return nb::pick_real(is_f64, [&](auto real) {
+        using T = typename decltype(real)::type;
+        const EnsScalars<T> *p = (const EnsScalars<T> *)prm;
+        const hipError_t err = nb::pick<2, 3>(dim, [&](auto D) {
+            hipLaunchKernelGGL((ens_energy_partials_kernel<T, D.value>), grid, dim3(EE_TILE), 0, st, (const T *)pos, (const T *)vel,
+                               (const T *)mass, n, ntiles, p, part);
+            return hipGetLastError();
+        });
+        if (err != hipSuccess) return err;
+        hipLaunchKernelGGL((ens_energy_finish_kernel<T>), dim3(members), dim3(64), 0, st, (const double *)part, npairs, members, p,
+                           kinetic, potential, sample);
+        return hipGetLastError();
+    });
 }

@@ -9,6 +9,7 @@
 // The grid modes (INT8 / INT4 / CUSTOM) run small_grid_body the same way, each member with its own tables
 // (ens_grid_step_kernel); their max-r2 + tables launch is ens_r2max_tables_kernel (nb_force.hip) and the INT8 / INT4 force
 // snap ens_force_quant_finish_kernel (nb_misc.hip).
+#include "nb_dispatch.h"
 #include "nb_small_body.h"
 #include "nb_internal.h"
 
@@ -70,45 +71,17 @@ ens_kick_drift_kernel(T *__restrict__ pos, T *__restrict__ vel, const T *__restr
 }
 
 template <typename T, int D, int HOOK>
-hipError_t launch_e(const T *pos_in, T *pos_out, T *vel, T *acc, const T *mass, int members, int n, const void *prm,
+hipError_t launch_e(const void *pos_in, void *pos_out, void *vel, void *acc, const void *mass, int members, int n, const void *prm,
                     int do_kick, int lanes, hipStream_t st)
 {
-    const EnsScalars<T> *p = (const EnsScalars<T> *)prm;
-#define NB_ENS(SS)                                                                                                         \
-    do {                                                                                                                   \
-        if (nb_small_block(n) == 512)                                                                                      \
-            hipLaunchKernelGGL((ens_step_kernel<T, D, HOOK, SS, 512>), dim3((n + 512 / SS - 1) / (512 / SS), members),     \
-                               dim3(512), 0, st, pos_in, pos_out, vel, acc, mass, n, p, do_kick);                          \
-        else                                                                                                               \
-            hipLaunchKernelGGL((ens_step_kernel<T, D, HOOK, SS, 256>), dim3((n + 256 / SS - 1) / (256 / SS), members),     \
-                               dim3(256), 0, st, pos_in, pos_out, vel, acc, mass, n, p, do_kick);                          \
-    } while (0)
-    if (lanes == 64) NB_ENS(64);
-    else if (lanes == 32) NB_ENS(32);
-    else NB_ENS(16);
-#undef NB_ENS
-    return hipGetLastError();
-}
-
-template <int D>
-hipError_t launch_g(const float *pos_in, float *pos_out, float *vel, float *acc, const float *mass, int members, int n,
-                    const void *prm, int do_kick, int lanes, const GridTables *tabs, double *part, hipStream_t st)
-{
-    const EnsScalars<float> *p = (const EnsScalars<float> *)prm;
-#define NB_ENSG(SS)                                                                                                        \
-    do {                                                                                                                   \
-        if (nb_small_block(n) == 512)                                                                                      \
-            hipLaunchKernelGGL((ens_grid_step_kernel<D, SS, 512>), dim3((n + 512 / SS - 1) / (512 / SS), members),         \
-                               dim3(512), 0, st, pos_in, pos_out, vel, acc, mass, n, p, do_kick, tabs, part);              \
-        else                                                                                                               \
-            hipLaunchKernelGGL((ens_grid_step_kernel<D, SS, 256>), dim3((n + 256 / SS - 1) / (256 / SS), members),         \
-                               dim3(256), 0, st, pos_in, pos_out, vel, acc, mass, n, p, do_kick, tabs, part);              \
-    } while (0)
-    if (lanes == 64) NB_ENSG(64);
-    else if (lanes == 32) NB_ENSG(32);
-    else NB_ENSG(16);
-#undef NB_ENSG
-    return hipGetLastError();
+    return nb::pick<64, 32, 16>(lanes, [&](auto S) {
+        return nb::pick<512, 256>(nb_small_block(n), [&](auto BS) {
+            hipLaunchKernelGGL((ens_step_kernel<T, D, HOOK, S.value, BS.value>), dim3(nb_small_blocks(n, lanes), members),
+                               dim3(BS.value), 0, st, (const T *)pos_in, (T *)pos_out, (T *)vel, (T *)acc, (const T *)mass, n,
+                               (const EnsScalars<T> *)prm, do_kick);
+            return hipGetLastError();
+        });
+    });
 }
 
 }  // namespace
@@ -116,41 +89,37 @@ hipError_t launch_g(const float *pos_in, float *pos_out, float *vel, float *acc,
 hipError_t nb_launch_ens_step(const void *pos_in, void *pos_out, void *vel, void *acc, const void *mass, int members, int n,
                               int dim, int is_f64, int hook, const void *prm, int do_kick, int lanes, hipStream_t st)
 {
-    if (dim != 2 && dim != 3) return hipErrorInvalidValue;
     if (members < 1 || members > NB_ENS_MAX_MEMBERS || n < 1) return hipErrorInvalidValue;
     if ((do_kick & NB_KICK_MODE_MASK) == NB_KICK_CLOSE_SPEC || (do_kick & NB_KICK_OPEN_ON_READ)) return hipErrorInvalidValue;
-    if (is_f64) {
-        if (hook != HOOK_NONE) return hipErrorInvalidValue;
-        if (dim == 2) return launch_e<double, 2, HOOK_NONE>((const double *)pos_in, (double *)pos_out, (double *)vel, (double *)acc, (const double *)mass, members, n, prm, do_kick, lanes, st);
-        return launch_e<double, 3, HOOK_NONE>((const double *)pos_in, (double *)pos_out, (double *)vel, (double *)acc, (const double *)mass, members, n, prm, do_kick, lanes, st);
-    }
-    if (hook != HOOK_NONE && hook != HOOK_BF16 && hook != HOOK_F16) return hipErrorInvalidValue;
-#define NB_EF(DD, HH) launch_e<float, DD, HH>((const float *)pos_in, (float *)pos_out, (float *)vel, (float *)acc, (const float *)mass, members, n, prm, do_kick, lanes, st)
-    if (dim == 2) {
-        if (hook == HOOK_BF16) return NB_EF(2, HOOK_BF16);
-        if (hook == HOOK_F16) return NB_EF(2, HOOK_F16);
-        return NB_EF(2, HOOK_NONE);
-    }
-    if (hook == HOOK_BF16) return NB_EF(3, HOOK_BF16);
-    if (hook == HOOK_F16) return NB_EF(3, HOOK_F16);
-    return NB_EF(3, HOOK_NONE);
-#undef NB_EF
+    return nb::pick<2, 3>(dim, [&](auto D) {
+        if (is_f64)
+            return nb::pick<HOOK_NONE>(hook, [&](auto H) {
+                return launch_e<double, D.value, H.value>(pos_in, pos_out, vel, acc, mass, members, n, prm, do_kick, lanes, st);
+            });
+        return nb::pick<HOOK_NONE, HOOK_BF16, HOOK_F16>(hook, [&](auto H) {
+            return launch_e<float, D.value, H.value>(pos_in, pos_out, vel, acc, mass, members, n, prm, do_kick, lanes, st);
+        });
+    });
 }
-
-int nb_ens_grid_blocks(int n, int lanes) { return (n + nb_small_block(n) / lanes - 1) / (nb_small_block(n) / lanes); }
 
 hipError_t nb_launch_ens_grid_step(const float *pos_in, float *pos_out, float *vel, float *acc, const float *mass, int members,
                                    int n, int dim, const void *prm, int do_kick, int lanes, const GridTables *tabs, double *part,
                                    hipStream_t st)
 {
-    if (dim != 2 && dim != 3) return hipErrorInvalidValue;
     if (members < 1 || members > NB_ENS_MAX_MEMBERS || n < 1 || !tabs) return hipErrorInvalidValue;
-    if (lanes != 16 && lanes != 32 && lanes != 64) return hipErrorInvalidValue;
     const int km = do_kick & NB_KICK_MODE_MASK;
     if (km == NB_KICK_CLOSE_SPEC || (do_kick & NB_KICK_OPEN_ON_READ)) return hipErrorInvalidValue;
     if (part && km != NB_KICK_NONE) return hipErrorInvalidValue;      // INT8 / INT4: the finish launch carries the kicks
-    if (dim == 2) return launch_g<2>(pos_in, pos_out, vel, acc, mass, members, n, prm, do_kick, lanes, tabs, part, st);
-    return launch_g<3>(pos_in, pos_out, vel, acc, mass, members, n, prm, do_kick, lanes, tabs, part, st);
+    return nb::pick<2, 3>(dim, [&](auto D) {
+        return nb::pick<64, 32, 16>(lanes, [&](auto S) {
+            return nb::pick<512, 256>(nb_small_block(n), [&](auto BS) {
+                hipLaunchKernelGGL((ens_grid_step_kernel<D.value, S.value, BS.value>), dim3(nb_small_blocks(n, lanes), members),
+                                   dim3(BS.value), 0, st, pos_in, pos_out, vel, acc, mass, n, (const EnsScalars<float> *)prm,
+                                   do_kick, tabs, part);
+                return hipGetLastError();
+            });
+        });
+    });
 }
 
 hipError_t nb_launch_ens_kick_drift(void *pos, void *vel, const void *acc, int members, int n, int dim, int is_f64,
@@ -159,11 +128,10 @@ hipError_t nb_launch_ens_kick_drift(void *pos, void *vel, const void *acc, int m
     if (members < 1 || members > NB_ENS_MAX_MEMBERS || n < 1 || (dim != 2 && dim != 3)) return hipErrorInvalidValue;
     const int count = n * dim;
     const dim3 grid((count + EK_BLOCK - 1) / EK_BLOCK, members);
-    if (is_f64)
-        hipLaunchKernelGGL((ens_kick_drift_kernel<double>), grid, dim3(EK_BLOCK), 0, st, (double *)pos, (double *)vel,
-                           (const double *)acc, count, (const EnsScalars<double> *)prm);
-    else
-        hipLaunchKernelGGL((ens_kick_drift_kernel<float>), grid, dim3(EK_BLOCK), 0, st, (float *)pos, (float *)vel,
-                           (const float *)acc, count, (const EnsScalars<float> *)prm);
-    return hipGetLastError();
+    return nb::pick_real(is_f64, [&](auto real) {
+        using T = typename decltype(real)::type;
+        hipLaunchKernelGGL((ens_kick_drift_kernel<T>), grid, dim3(EK_BLOCK), 0, st, (T *)pos, (T *)vel, (const T *)acc, count,
+                           (const EnsScalars<T> *)prm);
+        return hipGetLastError();
+    });
 }

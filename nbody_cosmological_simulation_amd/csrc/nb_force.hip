@@ -16,6 +16,7 @@
 //   correction instead of sqrt/div/pow, no self-interaction mask (d == 0 kills the diagonal
 //   term exactly as the reference's (1 - eye) multiply does, NaN cases included).
 #include "nb_device.h"
+#include "nb_dispatch.h"
 
 #include <hip/hip_fp16.h>
 
@@ -1199,45 +1200,33 @@ d2bins_kernel(const float *__restrict__ pos, int n, float eps2, const GridTables
     bins[(size_t)(i - i0) * n + j] = (int16_t)b;
 }
 
-template <typename F>
-hipError_t dispatch_dim(int dim, F &&f)
-{
-    if (dim == 2) return f(std::integral_constant<int, 2>{});
-    if (dim == 3) return f(std::integral_constant<int, 3>{});
-    return hipErrorInvalidValue;
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
 constexpr int R_F32 = 2;
+template <int V>
+using ic = std::integral_constant<int, V>;     // a fixed template argument beside picked ones
 
 hipError_t nb_launch_force_f64(const double *pos, const double *mass, double *partial, const ForceGeom &g,
                                int dim, int pair_dt, int qhook, double G, double eps2_py, float eps2_pair,
                                hipStream_t st)
 {
     // pair_dt: -1 (fp64 pairs) or the dtype the positions are typed as (NB_F32 / NB_F16 / NB_BF16)
-    const int r = (pair_dt >= 0 || qhook >= 0) ? 2 : g.r;   // the special variants are compiled for R = 2 only
+    const bool cast = qhook >= 0, typed = !cast && (pair_dt == NB_F32 || pair_dt == NB_F16 || pair_dt == NB_BF16);
+    const int r = (pair_dt >= 0 || cast) ? 2 : g.r;   // the special variants are compiled for R = 2 only
     const dim3 grid((g.n + NB_BLOCK * r - 1) / (NB_BLOCK * r), g.nchunks);
-#define NB_F64(DD, RR, PA, QH) \
-    hipLaunchKernelGGL((force_f64_kernel<DD, RR, PA, QH>), grid, dim3(NB_BLOCK), 0, st, pos, mass, partial, g, G, eps2_py, eps2_pair)
-    return dispatch_dim(dim, [&](auto D) {
-        constexpr int DD = decltype(D)::value;
-        if (qhook == HOOK_NONE) NB_F64(DD, 2, -1, HOOK_NONE);
-        else if (qhook == HOOK_BF16) NB_F64(DD, 2, -1, HOOK_BF16);
-        else if (qhook == HOOK_F16) NB_F64(DD, 2, -1, HOOK_F16);
-        else if (qhook >= 0) return hipErrorInvalidValue;
-        else if (pair_dt == NB_F32) NB_F64(DD, 2, NB_F32, -1);
-        else if (pair_dt == NB_F16) NB_F64(DD, 2, NB_F16, -1);
-        else if (pair_dt == NB_BF16) NB_F64(DD, 2, NB_BF16, -1);
-        else if (g.r == 1) NB_F64(DD, 1, -1, -1);
-        else if (g.r == 2) NB_F64(DD, 2, -1, -1);
-        else NB_F64(DD, 4, -1, -1);
-        return hipGetLastError();
+    return nb::pick<2, 3>(dim, [&](auto D) {
+        auto launch = [&](auto R, auto PA, auto QH) {
+            hipLaunchKernelGGL((force_f64_kernel<D.value, R.value, PA.value, QH.value>), grid, dim3(NB_BLOCK), 0, st, pos, mass,
+                               partial, g, G, eps2_py, eps2_pair);
+            return hipGetLastError();
+        };
+        if (cast) return nb::pick<HOOK_NONE, HOOK_BF16, HOOK_F16>(qhook, [&](auto QH) { return launch(ic<2>{}, ic<-1>{}, QH); });
+        if (typed) return nb::pick<NB_F32, NB_F16, NB_BF16>(pair_dt, [&](auto PA) { return launch(ic<2>{}, PA, ic<-1>{}); });
+        return nb::pick<1, 2, 4>(g.r == 1 || g.r == 2 ? g.r : 4, [&](auto R) { return launch(R, ic<-1>{}, ic<-1>{}); });
     });
-#undef NB_F64
 }
 
 hipError_t nb_launch_force_f32(const float *pos, const float *mass, double *partial, const ForceGeom &g,
@@ -1249,48 +1238,30 @@ hipError_t nb_launch_force_f32(const float *pos, const float *mass, double *part
     // small systems are parallelism-bound: one target per thread doubles the workgroups (like the fp64 kernel)
     const int r = g.n <= 8192 ? 1 : R_F32;
     const dim3 grid((g.n + NB_BLOCK * r - 1) / (NB_BLOCK * r), g.nchunks);
-#define NB_F32KB(DD, HH, PP, BB)                                                                                         \
-    do {                                                                                                                 \
-        if (r == 1)                                                                                                      \
-            hipLaunchKernelGGL((force_f32_kernel<DD, 1, HH, PP, BB>), grid, dim3(NB_BLOCK), lds, st, pos, mass, partial, g, \
-                               G, eps2, tab, lp, bin_out);                                                               \
-        else                                                                                                             \
-            hipLaunchKernelGGL((force_f32_kernel<DD, R_F32, HH, PP, BB>), grid, dim3(NB_BLOCK), lds, st, pos, mass, partial, \
-                               g, G, eps2, tab, lp, bin_out);                                                            \
-    } while (0)
-#define NB_F32K(DD, HH, PP) NB_F32KB(DD, HH, PP, false)
-    return dispatch_dim(dim, [&](auto D) {
-        constexpr int DD = decltype(D)::value;
-        if (bin_out) {           // bin read-out of the grid hook (nb_quant_bin_sums): same body, BINS = true
-            if (hook != HOOK_GRID || pa != NB_F32) return hipErrorInvalidValue;
-            NB_F32KB(DD, HOOK_GRID, NB_F32, true);
-            return hipGetLastError();
-        }
-        if (pa != NB_F32) {
-            // half-typed state: cast hooks only (a grid over a half tensor is not implemented)
-            if (hook == HOOK_GRID) return hipErrorInvalidValue;
-            if (pa == NB_F16) {
-                if (hook == HOOK_NONE) NB_F32K(DD, HOOK_NONE, NB_F16);
-                else if (hook == HOOK_BF16) NB_F32K(DD, HOOK_BF16, NB_F16);
-                else NB_F32K(DD, HOOK_F16, NB_F16);
-            } else {
-                if (hook == HOOK_NONE) NB_F32K(DD, HOOK_NONE, NB_BF16);
-                else if (hook == HOOK_BF16) NB_F32K(DD, HOOK_BF16, NB_BF16);
-                else NB_F32K(DD, HOOK_F16, NB_BF16);
+    return nb::pick<2, 3>(dim, [&](auto D) {
+        return nb::pick<1, R_F32>(r, [&](auto R) {
+            auto launch = [&](auto H, auto PA, auto BINS) {
+                hipLaunchKernelGGL((force_f32_kernel<D.value, R.value, H.value, PA.value, BINS.value>), grid, dim3(NB_BLOCK), lds,
+                                   st, pos, mass, partial, g, G, eps2, tab, lp, bin_out);
+                return hipGetLastError();
+            };
+            if (bin_out) {           // bin read-out of the grid hook (nb_quant_bin_sums): same body, BINS = true
+                if (hook != HOOK_GRID || pa != NB_F32) return hipErrorInvalidValue;
+                return launch(ic<HOOK_GRID>{}, ic<NB_F32>{}, std::true_type{});
             }
-            return hipGetLastError();
-        }
-        switch (hook) {
-        case HOOK_NONE: NB_F32K(DD, HOOK_NONE, NB_F32); break;
-        case HOOK_BF16: NB_F32K(DD, HOOK_BF16, NB_F32); break;
-        case HOOK_F16: NB_F32K(DD, HOOK_F16, NB_F32); break;
-        case HOOK_GRID: NB_F32K(DD, HOOK_GRID, NB_F32); break;
-        default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
+            if (pa != NB_F32) {
+                // half-typed state: cast hooks only (a grid over a half tensor is not implemented); whatever is not fp16 runs
+                // as bf16, and a hook that is neither none nor bf16 as fp16
+                if (hook == HOOK_GRID) return hipErrorInvalidValue;
+                return nb::pick<NB_F16, NB_BF16>(pa == NB_F16 ? NB_F16 : NB_BF16, [&](auto PA) {
+                    return nb::pick<HOOK_NONE, HOOK_BF16, HOOK_F16>(hook == HOOK_NONE || hook == HOOK_BF16 ? hook : HOOK_F16,
+                                                                    [&](auto H) { return launch(H, PA, std::false_type{}); });
+                });
+            }
+            return nb::pick<HOOK_NONE, HOOK_BF16, HOOK_F16, HOOK_GRID>(
+                hook, [&](auto H) { return launch(H, ic<NB_F32>{}, std::false_type{}); });
+        });
     });
-#undef NB_F32K
-#undef NB_F32KB
 }
 
 hipError_t nb_launch_r2max(const float *pos, const ForceGeom &g, int dim, float eps2, GridTables *tab,
@@ -1300,11 +1271,11 @@ hipError_t nb_launch_r2max(const float *pos, const ForceGeom &g, int dim, float 
     // workgroups
     const int r = g.n <= 8192 ? 1 : 4;
     const dim3 grid((g.n + NB_BLOCK * r - 1) / (NB_BLOCK * r), g.nchunks);
-    return dispatch_dim(dim, [&](auto D) {
-        constexpr int DD = decltype(D)::value;
-        if (r == 1) hipLaunchKernelGGL((r2max_kernel<DD, 1>), grid, dim3(NB_BLOCK), 0, st, pos, g, eps2, tab);
-        else hipLaunchKernelGGL((r2max_kernel<DD, 4>), grid, dim3(NB_BLOCK), 0, st, pos, g, eps2, tab);
-        return hipGetLastError();
+    return nb::pick<2, 3>(dim, [&](auto D) {
+        return nb::pick<1, 4>(r, [&](auto R) {
+            hipLaunchKernelGGL((r2max_kernel<D.value, R.value>), grid, dim3(NB_BLOCK), 0, st, pos, g, eps2, tab);
+            return hipGetLastError();
+        });
     });
 }
 
@@ -1325,9 +1296,8 @@ hipError_t nb_launch_r2max_tables(const float *pos, const ForceGeom &g, int dim,
     g2.chunk_len = chunk;
     g2.nchunks = (njr + chunk - 1) / chunk;
     const dim3 grid(gx, g2.nchunks);
-    return dispatch_dim(dim, [&](auto D) {
-        constexpr int DD = decltype(D)::value;
-        hipLaunchKernelGGL((r2max_tables_kernel<DD, 1>), grid, dim3(NB_BLOCK), 0, st, pos, g2, eps2, tab, levels, G, min_val,
+    return nb::pick<2, 3>(dim, [&](auto D) {
+        hipLaunchKernelGGL((r2max_tables_kernel<D.value, 1>), grid, dim3(NB_BLOCK), 0, st, pos, g2, eps2, tab, levels, G, min_val,
                            allow_fast);
         return hipGetLastError();
     });
@@ -1348,9 +1318,8 @@ hipError_t nb_launch_ens_r2max_tables(const float *pos, int members, int n, int 
     ForceGeom g{};
     g.n = n; g.j_begin = 0; g.j_end = n; g.chunk_len = chunk; g.nchunks = (n + chunk - 1) / chunk; g.r = 1;
     const dim3 grid(gx, g.nchunks, members);
-    return dispatch_dim(dim, [&](auto D) {
-        constexpr int DD = decltype(D)::value;
-        hipLaunchKernelGGL((ens_r2max_tables_kernel<DD>), grid, dim3(NB_BLOCK), 0, st, pos, g, (const float *)prm, tabs, levels,
+    return nb::pick<2, 3>(dim, [&](auto D) {
+        hipLaunchKernelGGL((ens_r2max_tables_kernel<D.value>), grid, dim3(NB_BLOCK), 0, st, pos, g, (const float *)prm, tabs, levels,
                            min_val, allow_fast);
         return hipGetLastError();
     });
@@ -1363,14 +1332,13 @@ hipError_t nb_launch_r2max_pruned(const float *pos, int n, int dim, float eps2, 
     const int bbox_blocks = blocks < 128 ? blocks : 128;
     // *ps is in its reset state on entry: nb_api.cpp initialises it once, grid_tables_kernel (which
     // always follows) puts it back after use -- no per-step memset / copy launches
-    return dispatch_dim(dim, [&](auto D) {
-        constexpr int DD = decltype(D)::value;
-        hipLaunchKernelGGL((prune_bbox_kernel<DD>), dim3(bbox_blocks), dim3(NB_BLOCK), 0, st, pos, n, ps);
-        hipLaunchKernelGGL((prune_rho_kernel<DD>), dim3(blocks), dim3(NB_BLOCK), 0, st, pos, n, rho, ps);
-        hipLaunchKernelGGL((prune_hop_kernel<DD>), dim3(blocks), dim3(NB_BLOCK), 0, st, pos, n, eps2, &ps->far, &ps->lb[0]);
-        hipLaunchKernelGGL((prune_hop_kernel<DD>), dim3(blocks), dim3(NB_BLOCK), 0, st, pos, n, eps2, &ps->lb[0], &ps->lb[1]);
-        hipLaunchKernelGGL((prune_compact_kernel<DD>), dim3(blocks), dim3(NB_BLOCK), 0, st, pos, rho, n, eps2, cand, ps);
-        hipLaunchKernelGGL((prune_scan_kernel<DD>), dim3(blocks), dim3(NB_BLOCK), 0, st, cand, eps2, ps, tab);
+    return nb::pick<2, 3>(dim, [&](auto D) {
+        hipLaunchKernelGGL((prune_bbox_kernel<D.value>), dim3(bbox_blocks), dim3(NB_BLOCK), 0, st, pos, n, ps);
+        hipLaunchKernelGGL((prune_rho_kernel<D.value>), dim3(blocks), dim3(NB_BLOCK), 0, st, pos, n, rho, ps);
+        hipLaunchKernelGGL((prune_hop_kernel<D.value>), dim3(blocks), dim3(NB_BLOCK), 0, st, pos, n, eps2, &ps->far, &ps->lb[0]);
+        hipLaunchKernelGGL((prune_hop_kernel<D.value>), dim3(blocks), dim3(NB_BLOCK), 0, st, pos, n, eps2, &ps->lb[0], &ps->lb[1]);
+        hipLaunchKernelGGL((prune_compact_kernel<D.value>), dim3(blocks), dim3(NB_BLOCK), 0, st, pos, rho, n, eps2, cand, ps);
+        hipLaunchKernelGGL((prune_scan_kernel<D.value>), dim3(blocks), dim3(NB_BLOCK), 0, st, cand, eps2, ps, tab);
         return hipGetLastError();
     });
 }
@@ -1382,10 +1350,9 @@ hipError_t nb_launch_r2max_tracked(const float *pos, int n, int dim, float eps2,
     const int fuse = levels <= NB_LUT_MIN ? 1 : 0;
     // (one launch instead of two -- every scan workgroup filtering for itself -- was measured slower at N = 6000 / 12 000:
     // 52.7 / 96.9 vs 41.8 / 73.2 us per INT8 step, profiles/r03_tracked_fused_one_launch_ab.txt)
-    return dispatch_dim(dim, [&](auto D) {
-        constexpr int DD = decltype(D)::value;
-        hipLaunchKernelGGL((track_filter_kernel<DD>), dim3(blocks), dim3(NB_BLOCK), 0, st, pos, n, eps2, cand, cand_idx, ps);
-        hipLaunchKernelGGL((track_scan_kernel<DD>), dim3(NB_TRACK_BLOCKS), dim3(NB_BLOCK), 0, st, pos, cand, cand_idx, n, eps2, ps,
+    return nb::pick<2, 3>(dim, [&](auto D) {
+        hipLaunchKernelGGL((track_filter_kernel<D.value>), dim3(blocks), dim3(NB_BLOCK), 0, st, pos, n, eps2, cand, cand_idx, ps);
+        hipLaunchKernelGGL((track_scan_kernel<D.value>), dim3(NB_TRACK_BLOCKS), dim3(NB_BLOCK), 0, st, pos, cand, cand_idx, n, eps2, ps,
                            tab, levels, G, min_val, allow_fast, fuse);
         return hipGetLastError();
     });
@@ -1421,9 +1388,8 @@ hipError_t nb_launch_d2bins(const float *pos, int n, int dim, float eps2, const 
 {
     if (i1 < 0) i1 = n;
     const dim3 grid((n + NB_BLOCK - 1) / NB_BLOCK, i1 - i0);
-    return dispatch_dim(dim, [&](auto D) {
-        constexpr int DD = decltype(D)::value;
-        hipLaunchKernelGGL((d2bins_kernel<DD>), grid, dim3(NB_BLOCK), 0, st, pos, n, eps2, tab, bins, i0);
+    return nb::pick<2, 3>(dim, [&](auto D) {
+        hipLaunchKernelGGL((d2bins_kernel<D.value>), grid, dim3(NB_BLOCK), 0, st, pos, n, eps2, tab, bins, i0);
         return hipGetLastError();
     });
 }

@@ -20,6 +20,7 @@
 //   LDS in a fixed order, so one column slab per super-row leaves the chip (4x less slab traffic
 //   than one per row).  Row sums go to per-(row, chunk) slots.  reduce_sym_kernel adds slots and
 //   slabs in a fixed order: no atomics, run-to-run bit-identical.
+#include "nb_dispatch.h"
 #include "nb_force_sym_kernel.h"
 
 namespace {
@@ -376,17 +377,18 @@ hipError_t nb_launch_pack(void *pos, void *vel, const void *acc, const void *mas
     // arithmetic the pair loop uses (fp32 pair arithmetic on fp64 storage needs the fp32 value)
     const double pad = (is_f64 && !f32_pairs) ? 1e150 : 1e18;
     const int grid = (p_end - p_begin + NB_BLOCK - 1) / NB_BLOCK;
-#define NB_PACK(TT, DD, KK) \
-    hipLaunchKernelGGL((pack_kernel<TT, DD, KK>), dim3(grid), dim3(NB_BLOCK), 0, st, (TT *)pos, (TT *)vel, \
-                       (const TT *)acc, (const TT *)mass, (TT *)packed, n, np, (TT)half_dt, (TT)dt, (TT)gfac, (TT)pad, \
-                       p_begin, p_end, spread_pad)
-#define NB_PACK_K(TT, DD) do { if (kick == NB_PACK_CLOSE_OPEN) NB_PACK(TT, DD, 2); else if (kick == NB_PACK_OPEN) NB_PACK(TT, DD, 1); else NB_PACK(TT, DD, 0); } while (0)
-    if (dim != 2 && dim != 3) return hipErrorInvalidValue;
-    if (is_f64) { if (dim == 2) NB_PACK_K(double, 2); else NB_PACK_K(double, 3); }
-    else        { if (dim == 2) NB_PACK_K(float, 2); else NB_PACK_K(float, 3); }
-#undef NB_PACK_K
-#undef NB_PACK
-    return hipGetLastError();
+    const int k = (kick == NB_PACK_CLOSE_OPEN || kick == NB_PACK_OPEN) ? kick : NB_PACK_NONE;
+    return nb::pick<2, 3>(dim, [&](auto D) {
+        return nb::pick_real(is_f64, [&](auto real) {
+            using T = typename decltype(real)::type;
+            return nb::pick<NB_PACK_NONE, NB_PACK_OPEN, NB_PACK_CLOSE_OPEN>(k, [&](auto K) {
+                hipLaunchKernelGGL((pack_kernel<T, D.value, K.value>), dim3(grid), dim3(NB_BLOCK), 0, st, (T *)pos, (T *)vel,
+                                   (const T *)acc, (const T *)mass, (T *)packed, n, np, (T)half_dt, (T)dt, (T)gfac, (T)pad, p_begin,
+                                   p_end, spread_pad);
+                return hipGetLastError();
+            });
+        });
+    });
 }
 
 hipError_t nb_launch_force_sym_f64(const double *packed, const SymWork *work, int nwork, double *rowslab,
@@ -398,21 +400,17 @@ hipError_t nb_launch_force_sym_f64(const double *packed, const SymWork *work, in
         if (pa_f32) return launch_sym_rowsplit<HOOK_F32PAIR>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, (float)eps2, st, ev);
         return launch_sym_rowsplit<HOOK_NONE>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, 1.0f, st, ev);
     }
-    if (pa_f32) {   // first evaluation on fp32-typed positions: default tile shapes only
-        const float e32 = (float)eps2;
-        if (dim == 2 && r == 4) return launch_sym_u<double, 2, 4, HOOK_F32PAIR>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, nullptr, e32, st, ev);
-        if (dim == 2 && r == 2) return launch_sym_u<double, 2, 2, HOOK_F32PAIR>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, nullptr, e32, st, ev);
-        if (dim == 3 && r == 2) return launch_sym_u<double, 3, 2, HOOK_F32PAIR>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, nullptr, e32, st, ev);
-        if (dim == 3 && r == 4) return launch_sym_u<double, 3, 4, HOOK_F32PAIR>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, nullptr, e32, st, ev);
-        return hipErrorInvalidValue;
-    }
-    if (dim == 2 && r == 1) return launch_sym_u<double, 2, 1, HOOK_NONE>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, nullptr, 1.0f, st, ev);
-    if (dim == 2 && r == 2) return launch_sym_u<double, 2, 2, HOOK_NONE>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, nullptr, 1.0f, st, ev);
-    if (dim == 2 && r == 4) return launch_sym_u<double, 2, 4, HOOK_NONE>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, nullptr, 1.0f, st, ev);
-    if (dim == 3 && r == 1) return launch_sym_u<double, 3, 1, HOOK_NONE>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, nullptr, 1.0f, st, ev);
-    if (dim == 3 && r == 2) return launch_sym_u<double, 3, 2, HOOK_NONE>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, nullptr, 1.0f, st, ev);
-    if (dim == 3 && r == 4) return launch_sym_u<double, 3, 4, HOOK_NONE>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, nullptr, 1.0f, st, ev);
-    return hipErrorInvalidValue;
+    return nb::pick<2, 3>(dim, [&](auto D) {
+        if (pa_f32)     // first evaluation on fp32-typed positions: default tile shapes only
+            return nb::pick<2, 4>(r, [&](auto R) {
+                return launch_sym_u<double, D.value, R.value, HOOK_F32PAIR>(packed, work, nwork, rowslab, colslab, np, uniform, eps2,
+                                                                            nullptr, (float)eps2, st, ev);
+            });
+        return nb::pick<1, 2, 4>(r, [&](auto R) {
+            return launch_sym_u<double, D.value, R.value, HOOK_NONE>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, nullptr,
+                                                                     1.0f, st, ev);
+        });
+    });
 }
 
 hipError_t nb_launch_force_sym_f32(const float *packed, const SymWork *work, int nwork, double *rowslab,
@@ -420,50 +418,34 @@ hipError_t nb_launch_force_sym_f32(const float *packed, const SymWork *work, int
                                    const GridTables *tab, float G, float mass_value, int levels, hipStream_t st,
                                    NbKernelEvents ev)
 {
-#define NB_SYM32(DD, RR)                                                                                              \
-    switch (hook) {                                                                                                   \
-    case HOOK_NONE: return launch_sym_u<float, DD, RR, HOOK_NONE>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, tab, G, st, ev); \
-    case HOOK_BF16: return launch_sym_u<float, DD, RR, HOOK_BF16>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, tab, G, st, ev); \
-    case HOOK_F16: return launch_sym_u<float, DD, RR, HOOK_F16>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, tab, G, st, ev);   \
-    case HOOK_GRID: return launch_sym_u<float, DD, RR, HOOK_GRID>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, tab, G, st, ev, mass_value, levels); \
-    default: return hipErrorInvalidValue;                                                                             \
-    }
-    if (dim == 2 && r == 2) { NB_SYM32(2, 2) }
-    if (dim == 2 && r == 4) { NB_SYM32(2, 4) }
-    if (dim == 3 && r == 2) { NB_SYM32(3, 2) }
-    if (dim == 3 && r == 4) { NB_SYM32(3, 4) }
-#undef NB_SYM32
-    return hipErrorInvalidValue;
+    return nb::pick<2, 3>(dim, [&](auto D) {
+        return nb::pick<2, 4>(r, [&](auto R) {
+            return nb::pick<HOOK_NONE, HOOK_BF16, HOOK_F16, HOOK_GRID>(hook, [&](auto H) {     // mass_value, levels: the grid hook's
+                return launch_sym_u<float, D.value, R.value, H.value>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, tab, G,
+                                                                      st, ev, mass_value, levels);
+            });
+        });
+    });
 }
 
 hipError_t nb_launch_potential_sym(const void *packed, const SymWork *work, int nwork, double *part, int np, int dim,
                                    int r, int is_f64, int f32_terms, int mass_dt, double eps2, int uniform, hipStream_t st)
 {
     const float e32 = (float)eps2;
-#define NB_PES(TT, DD, RR, FF)                                                                                           \
-    do {                                                                                                                 \
-        if (uniform)                                                                                                     \
-            hipLaunchKernelGGL((potential_sym_kernel<TT, DD, RR, FF, true>), dim3(nwork), dim3(NB_BLOCK), 0, st,         \
-                               (const TT *)packed, work, part, np, eps2, e32, mass_dt);                                  \
-        else                                                                                                             \
-            hipLaunchKernelGGL((potential_sym_kernel<TT, DD, RR, FF, false>), dim3(nwork), dim3(NB_BLOCK), 0, st,        \
-                               (const TT *)packed, work, part, np, eps2, e32, mass_dt);                                  \
-    } while (0)
-    if (is_f64) {
-        if (dim == 2 && r == 4) { if (f32_terms) NB_PES(double, 2, 4, true); else NB_PES(double, 2, 4, false); }
-        else if (dim == 2 && r == 2) { if (f32_terms) NB_PES(double, 2, 2, true); else NB_PES(double, 2, 2, false); }
-        else if (dim == 3 && r == 2) { if (f32_terms) NB_PES(double, 3, 2, true); else NB_PES(double, 3, 2, false); }
-        else if (dim == 3 && r == 4) { if (f32_terms) NB_PES(double, 3, 4, true); else NB_PES(double, 3, 4, false); }
-        else return hipErrorInvalidValue;
-    } else {
-        if (dim == 2 && r == 4) NB_PES(float, 2, 4, true);
-        else if (dim == 2 && r == 2) NB_PES(float, 2, 2, true);
-        else if (dim == 3 && r == 2) NB_PES(float, 3, 2, true);
-        else if (dim == 3 && r == 4) NB_PES(float, 3, 4, true);
-        else return hipErrorInvalidValue;
-    }
-#undef NB_PES
-    return hipGetLastError();
+    return nb::pick<2, 3>(dim, [&](auto D) {
+        return nb::pick<2, 4>(r, [&](auto R) {
+            auto launch = [&](auto real, auto F32T) {
+                using T = typename decltype(real)::type;
+                return nb::pick_bool(uniform, [&](auto U) {
+                    hipLaunchKernelGGL((potential_sym_kernel<T, D.value, R.value, F32T.value, U.value>), dim3(nwork), dim3(NB_BLOCK),
+                                       0, st, (const T *)packed, work, part, np, eps2, e32, mass_dt);
+                    return hipGetLastError();
+                });
+            };
+            if (is_f64) return nb::pick_bool(f32_terms, [&](auto F32T) { return launch(nb::real_tag<double>{}, F32T); });
+            return launch(nb::real_tag<float>{}, std::true_type{});      // fp32 state: fp32 terms only
+        });
+    });
 }
 
 hipError_t nb_launch_finish_sums64(const double *sums64, double scale, float *acc, int64_t count, hipStream_t st)
@@ -484,15 +466,15 @@ hipError_t nb_launch_reduce_sym(const double *rowslab, const void *colslab, cons
     if (p_end <= p_begin) return hipSuccess;
     const int blk0 = p_begin / 64;                  // chunk boundaries are tile boundaries (multiples of 64)
     const int grid = (p_end + 63) / 64 - blk0;
-#define NB_RED(TT, DD) \
-    hipLaunchKernelGGL((reduce_sym_kernel<TT, DD>), dim3(grid), dim3(64 * NB_RED_WAVES), 0, st, rowslab, (const TT *)colslab, \
-                       row_slot0, row_nslots, col_upto, tile_b, n, np, scale, (TT *)acc, (TT *)vel, (TT)half_dt, do_kick, \
-                       (TT *)pos, (TT *)packed, (TT)dt, blk0, sums64, mm_part, (TT *)pos_next)
-    if (dim != 2 && dim != 3) return hipErrorInvalidValue;
-    if (is_f64) { if (dim == 2) NB_RED(double, 2); else NB_RED(double, 3); }
-    else        { if (dim == 2) NB_RED(float, 2); else NB_RED(float, 3); }
-#undef NB_RED
-    return hipGetLastError();
+    return nb::pick<2, 3>(dim, [&](auto D) {
+        return nb::pick_real(is_f64, [&](auto real) {
+            using T = typename decltype(real)::type;
+            hipLaunchKernelGGL((reduce_sym_kernel<T, D.value>), dim3(grid), dim3(64 * NB_RED_WAVES), 0, st, rowslab,
+                               (const T *)colslab, row_slot0, row_nslots, col_upto, tile_b, n, np, scale, (T *)acc, (T *)vel,
+                               (T)half_dt, do_kick, (T *)pos, (T *)packed, (T)dt, blk0, sums64, mm_part, (T *)pos_next);
+            return hipGetLastError();
+        });
+    });
 }
 
 #ifdef NB_WG_TRACE

@@ -7,6 +7,7 @@
 // "bit-identical quant-bin assignments" (reference quantization.py:106-123) is checked on the pair loop that
 // assigns the bins, not on a separate table walk.  A separate translation unit so that the production objects
 // are byte-for-byte what they were and the build parallelises.
+#include "nb_dispatch.h"
 #include "nb_force_sym_kernel.h"
 
 hipError_t nb_launch_force_sym_f32_bins(const float *packed, const SymWork *work, int nwork, double *rowslab,
@@ -15,13 +16,10 @@ hipError_t nb_launch_force_sym_f32_bins(const float *packed, const SymWork *work
                                         unsigned long long *bin_out, int bin_n, hipStream_t st)
 {
     const NbKernelEvents ev{};
-#define NB_SYMB(DD, RR)                                                                                                  \
-    return launch_sym_u<float, DD, RR, HOOK_GRID, true>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, tab, G, st, \
-                                                        ev, mass_value, levels, bin_out, bin_n)
-    if (dim == 2 && r == 2) { NB_SYMB(2, 2); }
-    if (dim == 2 && r == 4) { NB_SYMB(2, 4); }
-    if (dim == 3 && r == 2) { NB_SYMB(3, 2); }
-    if (dim == 3 && r == 4) { NB_SYMB(3, 4); }
-#undef NB_SYMB
-    return hipErrorInvalidValue;
+    return nb::pick<2, 3>(dim, [&](auto D) {
+        return nb::pick<2, 4>(r, [&](auto R) {
+            return launch_sym_u<float, D.value, R.value, HOOK_GRID, true>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, tab,
+                                                                          G, st, ev, mass_value, levels, bin_out, bin_n);
+        });
+    });
 }

@@ -11,6 +11,7 @@
 // would hold it in (identical to native arithmetic in that dtype for + - * / sqrt: 53 >= 2*24 + 2 bits), log / exp /
 // pow in fp64 then rounded.  Slow (a log, an exp and a pow per pair in the grid modes) and only reached by unusual
 // inputs; correct by construction rather than fast.  Golden: tests/golden/g15_dtype_combos.npz.
+#include "nb_dispatch.h"
 #include "nb_internal.h"
 
 namespace {
@@ -239,11 +240,14 @@ hipError_t nb_launch_generic_r2max(const void *pos, int storage_f64, int n, int 
 {
     hipLaunchKernelGGL(generic_reset_kernel, dim3(1), dim3(1), 0, st, (GenScalars *)sc);
     const int blocks = (n + NB_BLOCK - 1) / NB_BLOCK;
-#define NB_GR(SS, DD) hipLaunchKernelGGL((generic_r2max_kernel<SS, DD>), dim3(blocks), dim3(NB_BLOCK), 0, st, (const SS *)pos, n, P, eps2_py, (GenScalars *)sc)
-    if (storage_f64) { if (dim == 2) NB_GR(double, 2); else NB_GR(double, 3); }
-    else             { if (dim == 2) NB_GR(float, 2); else NB_GR(float, 3); }
-#undef NB_GR
-    return hipGetLastError();
+    return nb::pick<2, 3>(dim == 2 ? 2 : 3, [&](auto D) {       // the callers validated dim
+        return nb::pick_real(storage_f64, [&](auto real) {
+            using S = typename decltype(real)::type;
+            hipLaunchKernelGGL((generic_r2max_kernel<S, D.value>), dim3(blocks), dim3(NB_BLOCK), 0, st, (const S *)pos, n, P, eps2_py,
+                               (GenScalars *)sc);
+            return hipGetLastError();
+        });
+    });
 }
 
 hipError_t nb_launch_generic_force(const void *pos, const void *mass, int storage_f64, double *partial, const ForceGeom &geom,
@@ -252,15 +256,16 @@ hipError_t nb_launch_generic_force(const void *pos, const void *mass, int storag
 {
     GenArgs g{geom.n, geom.j_begin, geom.j_end, geom.chunk_len, P, M, mode, levels, G, eps2_py};
     const dim3 grid((geom.n + NB_BLOCK - 1) / NB_BLOCK, geom.nchunks);
-#define NB_GF(SS, DD) hipLaunchKernelGGL((generic_force_kernel<SS, DD>), grid, dim3(NB_BLOCK), 0, st, (const SS *)pos, (const SS *)mass, partial, g, (const GenScalars *)sc)
-    if (storage_f64) { if (dim == 2) NB_GF(double, 2); else NB_GF(double, 3); }
-    else             { if (dim == 2) NB_GF(float, 2); else NB_GF(float, 3); }
-#undef NB_GF
     const int64_t count = (int64_t)geom.n * dim;
     const int blocks = (int)((count + NB_BLOCK - 1) / NB_BLOCK);
-    if (storage_f64)
-        hipLaunchKernelGGL((generic_finish_kernel<double>), dim3(blocks), dim3(NB_BLOCK), 0, st, partial, geom.nchunks, count, A, (double *)acc);
-    else
-        hipLaunchKernelGGL((generic_finish_kernel<float>), dim3(blocks), dim3(NB_BLOCK), 0, st, partial, geom.nchunks, count, A, (float *)acc);
-    return hipGetLastError();
+    return nb::pick<2, 3>(dim == 2 ? 2 : 3, [&](auto D) {
+        return nb::pick_real(storage_f64, [&](auto real) {
+            using S = typename decltype(real)::type;
+            hipLaunchKernelGGL((generic_force_kernel<S, D.value>), grid, dim3(NB_BLOCK), 0, st, (const S *)pos, (const S *)mass, partial,
+                               g, (const GenScalars *)sc);
+            hipLaunchKernelGGL((generic_finish_kernel<S>), dim3(blocks), dim3(NB_BLOCK), 0, st, partial, geom.nchunks, count, A,
+                               (S *)acc);
+            return hipGetLastError();
+        });
+    });
 }

@@ -301,6 +301,7 @@ hipError_t nb_launch_generic_force(const void *pos, const void *mass, int storag
 // ---- one-launch step for small systems (nb_small.hip) -------------------------------------------------------------
 int nb_small_lanes(int n);
 int nb_small_block(int n);          // threads per workgroup of the one-launch step at this size (256 or 512)
+int nb_small_blocks(int n, int lanes);   // its workgroups (one {min, max} pair of `part` each); the batched steps: per member
 hipError_t nb_launch_small_step(const void *pos_in, void *pos_out, void *vel, void *acc, const void *mass, int n, int dim,
                                 int is_f64, int hook, double G, double eps2, double half_dt, double dt,
                                 int do_kick /* NbKick | NB_KICK_OPEN_ON_READ */,
@@ -324,12 +325,11 @@ hipError_t nb_launch_ens_kick_drift(void *pos, void *vel, const void *acc, int m
 //   nb_launch_ens_r2max_tables        max r2 of every member and, by the member's last workgroup, its tables (tabs: `members`
 //                                     GridTables, zeroed once; levels: device, `members` ints in [2, NB_LUT_MIN])
 //   nb_launch_ens_grid_step           the solo grid step's body (nb_small_body.h small_grid_body) on every member with
-//                                     tabs[b]; part (INT8 / INT4, else null): members * nb_ens_grid_blocks * 2 doubles, one
+//                                     tabs[b]; part (INT8 / INT4, else null): members * nb_small_blocks * 2 doubles, one
 //                                     {min, max} of the forces per workgroup -- the kicks are then the finish launch's
 //   nb_launch_ens_force_quant_finish  INT8 / INT4: folds a member's partials into bounds[2 b] = {min, max}, snaps its
 //                                     count = n * dim forces to `levels` values and applies the kicks in place; `levels` is
 //                                     ONE value for all members (256 or 16: the force grid is the mode's, not CUSTOM's)
-int nb_ens_grid_blocks(int n, int lanes);     // workgroups per member of nb_launch_ens_grid_step
 hipError_t nb_launch_ens_r2max_tables(const float *pos, int members, int n, int dim, const void *prm, GridTables *tabs,
                                       const int *levels, float min_val, int allow_fast, hipStream_t st);
 hipError_t nb_launch_ens_grid_step(const float *pos_in, float *pos_out, float *vel, float *acc, const float *mass, int members,

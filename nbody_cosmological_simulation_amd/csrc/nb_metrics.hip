@@ -13,6 +13,7 @@
 // keep index order.  Bin sums are added in a fixed order (one workgroup per bin), in fp64.  Per-particle arithmetic
 // follows torch op by op in the state's LOGICAL dtype A (fp32 state tensors: fp32 products, sums, sqrt, divide -- no
 // fma), so that bin membership and the escape test take the decisions the reference takes.
+#include "nb_dispatch.h"
 #include "nb_internal.h"
 
 namespace {
@@ -369,10 +370,12 @@ size_t nb_metrics_scratch_bytes(int n, int num_bins)
 
 hipError_t nb_launch_metrics(const NbMetricsArgs &a, hipStream_t st)
 {
-    if (a.dim != 2 && a.dim != 3) return hipErrorInvalidValue;
     if (a.num_bins < 0 || a.num_bins > MB - 1) return hipErrorInvalidValue;
-#define NB_MET(SS, AA) (a.dim == 2 ? run<SS, AA, 2>(a, st) : run<SS, AA, 3>(a, st))
-    if (a.storage_f64) return a.arith_f64 ? NB_MET(double, double) : NB_MET(double, float);
-    return a.arith_f64 ? NB_MET(float, double) : NB_MET(float, float);
-#undef NB_MET
+    return nb::pick<2, 3>(a.dim, [&](auto D) {
+        return nb::pick_real(a.storage_f64, [&](auto storage) {
+            return nb::pick_real(a.arith_f64, [&](auto arith) {
+                return run<typename decltype(storage)::type, typename decltype(arith)::type, D.value>(a, st);
+            });
+        });
+    });
 }

@@ -2,6 +2,7 @@
 // (simulation.py:132-141), dtype conversion, linear force quantisation (quantization.py:74-88),
 // energies (simulation.py:170-192) and the tensor-level precision hooks.  gfx950 only.
 #include "nb_device.h"
+#include "nb_dispatch.h"
 
 #include <hip/hip_fp16.h>
 
@@ -118,18 +119,17 @@ convert_kernel(const TI *__restrict__ in, TO *__restrict__ out, int64_t count)
     }
 }
 
-template <typename TI>
-hipError_t convert_out(const TI *in, void *out, int out_dt, int64_t count, hipStream_t st)
+// f(nb::real_tag<element type>{}) for an nb_dtype
+template <typename F>
+hipError_t pick_dtype(int dt, F &&f)
 {
-    const int grid = ew_grid(count);
-    switch (out_dt) {
-    case NB_F16: hipLaunchKernelGGL((convert_kernel<TI, _Float16>), dim3(grid), dim3(EW_BLOCK), 0, st, in, (_Float16 *)out, count); break;
-    case NB_BF16: hipLaunchKernelGGL((convert_kernel<TI, __bf16>), dim3(grid), dim3(EW_BLOCK), 0, st, in, (__bf16 *)out, count); break;
-    case NB_F32: hipLaunchKernelGGL((convert_kernel<TI, float>), dim3(grid), dim3(EW_BLOCK), 0, st, in, (float *)out, count); break;
-    case NB_F64: hipLaunchKernelGGL((convert_kernel<TI, double>), dim3(grid), dim3(EW_BLOCK), 0, st, in, (double *)out, count); break;
+    switch (dt) {
+    case NB_F16: return f(nb::real_tag<_Float16>{});
+    case NB_BF16: return f(nb::real_tag<__bf16>{});
+    case NB_F32: return f(nb::real_tag<float>{});
+    case NB_F64: return f(nb::real_tag<double>{});
     default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
 }
 
 // ---- NaN-propagating min/max helpers (torch.min()/max() return NaN if any element is NaN) ----
@@ -549,63 +549,55 @@ potential_kernel(const T *__restrict__ pos, const T *__restrict__ mass, ForceGeo
 hipError_t nb_launch_reduce(const double *partial, int nchunks, int64_t count, void *acc, int is_f64, void *vel,
                             double half_dt, int do_kick, void *pos, double dt, hipStream_t st)
 {
-    const int grid = ew_grid(count);
-    if (is_f64)
-        hipLaunchKernelGGL((reduce_kernel<double>), dim3(grid), dim3(EW_BLOCK), 0, st, partial, nchunks, count,
-                           (double *)acc, (double *)vel, half_dt, do_kick, (double *)pos, dt);
-    else
-        hipLaunchKernelGGL((reduce_kernel<float>), dim3(grid), dim3(EW_BLOCK), 0, st, partial, nchunks, count,
-                           (float *)acc, (float *)vel, (float)half_dt, do_kick, (float *)pos, (float)dt);
-    return hipGetLastError();
+    return nb::pick_real(is_f64, [&](auto real) {
+        using T = typename decltype(real)::type;
+        hipLaunchKernelGGL((reduce_kernel<T>), dim3(ew_grid(count)), dim3(EW_BLOCK), 0, st, partial, nchunks, count, (T *)acc,
+                           (T *)vel, (T)half_dt, do_kick, (T *)pos, (T)dt);
+        return hipGetLastError();
+    });
 }
 
 hipError_t nb_launch_axpy(void *y, const void *x, double scalar, int64_t count, int is_f64, hipStream_t st)
 {
-    const int grid = ew_grid(count);
-    if (is_f64)
-        hipLaunchKernelGGL((axpy_kernel<double>), dim3(grid), dim3(EW_BLOCK), 0, st, (double *)y, (const double *)x,
-                           scalar, count);
-    else
-        hipLaunchKernelGGL((axpy_kernel<float>), dim3(grid), dim3(EW_BLOCK), 0, st, (float *)y, (const float *)x,
-                           (float)scalar, count);
-    return hipGetLastError();
+    return nb::pick_real(is_f64, [&](auto real) {
+        using T = typename decltype(real)::type;
+        hipLaunchKernelGGL((axpy_kernel<T>), dim3(ew_grid(count)), dim3(EW_BLOCK), 0, st, (T *)y, (const T *)x, (T)scalar, count);
+        return hipGetLastError();
+    });
 }
 
 hipError_t nb_launch_kick_drift(void *pos, void *vel, const void *acc, double half_dt, double dt, int64_t count,
                                 int is_f64, hipStream_t st)
 {
-    const int grid = ew_grid(count);
-    if (is_f64)
-        hipLaunchKernelGGL((kick_drift_kernel<double>), dim3(grid), dim3(EW_BLOCK), 0, st, (double *)pos,
-                           (double *)vel, (const double *)acc, half_dt, dt, count);
-    else
-        hipLaunchKernelGGL((kick_drift_kernel<float>), dim3(grid), dim3(EW_BLOCK), 0, st, (float *)pos,
-                           (float *)vel, (const float *)acc, (float)half_dt, (float)dt, count);
-    return hipGetLastError();
+    return nb::pick_real(is_f64, [&](auto real) {
+        using T = typename decltype(real)::type;
+        hipLaunchKernelGGL((kick_drift_kernel<T>), dim3(ew_grid(count)), dim3(EW_BLOCK), 0, st, (T *)pos, (T *)vel, (const T *)acc,
+                           (T)half_dt, (T)dt, count);
+        return hipGetLastError();
+    });
 }
 
 hipError_t nb_launch_kick_a32(void *pos, void *vel, const void *acc, double half_dt, double dt, int64_t count,
                               int vel_f64, int pos_f64, int drift, hipStream_t st)
 {
-    const int grid = ew_grid(count);
-    if (drift)
-        hipLaunchKernelGGL((kick_a32_kernel<true>), dim3(grid), dim3(EW_BLOCK), 0, st, (double *)pos, (double *)vel,
+    return nb::pick_bool(drift, [&](auto DRIFT) {
+        hipLaunchKernelGGL((kick_a32_kernel<DRIFT.value>), dim3(ew_grid(count)), dim3(EW_BLOCK), 0, st, (double *)pos, (double *)vel,
                            (const double *)acc, half_dt, dt, count, vel_f64, pos_f64);
-    else
-        hipLaunchKernelGGL((kick_a32_kernel<false>), dim3(grid), dim3(EW_BLOCK), 0, st, (double *)pos, (double *)vel,
-                           (const double *)acc, half_dt, dt, count, vel_f64, pos_f64);
-    return hipGetLastError();
+        return hipGetLastError();
+    });
 }
 
 hipError_t nb_launch_convert(const void *in, int in_dt, void *out, int out_dt, int64_t count, hipStream_t st)
 {
-    switch (in_dt) {
-    case NB_F16: return convert_out<_Float16>((const _Float16 *)in, out, out_dt, count, st);
-    case NB_BF16: return convert_out<__bf16>((const __bf16 *)in, out, out_dt, count, st);
-    case NB_F32: return convert_out<float>((const float *)in, out, out_dt, count, st);
-    case NB_F64: return convert_out<double>((const double *)in, out, out_dt, count, st);
-    default: return hipErrorInvalidValue;
-    }
+    return pick_dtype(in_dt, [&](auto in_tag) {
+        return pick_dtype(out_dt, [&](auto out_tag) {
+            using TI = typename decltype(in_tag)::type;
+            using TO = typename decltype(out_tag)::type;
+            hipLaunchKernelGGL((convert_kernel<TI, TO>), dim3(ew_grid(count)), dim3(EW_BLOCK), 0, st, (const TI *)in, (TO *)out,
+                               count);
+            return hipGetLastError();
+        });
+    });
 }
 
 hipError_t nb_launch_minmax_generic(const void *in, int is_f64, int64_t count, int log_clamped, double min_val,
@@ -613,26 +605,26 @@ hipError_t nb_launch_minmax_generic(const void *in, int is_f64, int64_t count, i
 {
     int blocks = (int)((count + 1023) / 1024);          // >= 4 elements per thread
     blocks = blocks < 1 ? 1 : (blocks > MM_BLOCKS ? MM_BLOCKS : blocks);
-#define NB_MM(TT, LL) \
-    hipLaunchKernelGGL((minmax_stage1_kernel<TT, LL>), dim3(blocks), dim3(256), 0, st, (const TT *)in, count, (TT)min_val, partials)
-    if (is_f64) { if (log_clamped) NB_MM(double, true); else NB_MM(double, false); }
-    else        { if (log_clamped) NB_MM(float, true); else NB_MM(float, false); }
-#undef NB_MM
-    hipLaunchKernelGGL(minmax_stage2_kernel, dim3(1), dim3(256), 0, st, partials, blocks, mn_mx);
-    return hipGetLastError();
+    return nb::pick_real(is_f64, [&](auto real) {
+        using T = typename decltype(real)::type;
+        return nb::pick_bool(log_clamped, [&](auto LOGC) {
+            hipLaunchKernelGGL((minmax_stage1_kernel<T, LOGC.value>), dim3(blocks), dim3(256), 0, st, (const T *)in, count,
+                               (T)min_val, partials);
+            hipLaunchKernelGGL(minmax_stage2_kernel, dim3(1), dim3(256), 0, st, partials, blocks, mn_mx);
+            return hipGetLastError();
+        });
+    });
 }
 
 hipError_t nb_launch_grid_quantize(const void *in, void *out, int is_f64, int64_t count, int levels,
                                    const double *mn_mx, hipStream_t st)
 {
-    const int grid = ew_grid(count);
-    if (is_f64)
-        hipLaunchKernelGGL((grid_quantize_kernel<double>), dim3(grid), dim3(EW_BLOCK), 0, st, (const double *)in,
-                           (double *)out, count, levels, mn_mx, (int16_t *)nullptr);
-    else
-        hipLaunchKernelGGL((grid_quantize_kernel<float>), dim3(grid), dim3(EW_BLOCK), 0, st, (const float *)in,
-                           (float *)out, count, levels, mn_mx, (int16_t *)nullptr);
-    return hipGetLastError();
+    return nb::pick_real(is_f64, [&](auto real) {
+        using T = typename decltype(real)::type;
+        hipLaunchKernelGGL((grid_quantize_kernel<T>), dim3(ew_grid(count)), dim3(EW_BLOCK), 0, st, (const T *)in, (T *)out, count,
+                           levels, mn_mx, (int16_t *)nullptr);
+        return hipGetLastError();
+    });
 }
 
 // same kernel, fp32, with optional bin output (force quantisation inside the step)
@@ -687,42 +679,26 @@ hipError_t nb_launch_ens_force_quant_finish(float *acc, int members, int count, 
 hipError_t nb_launch_grid_quantize_safe(const void *in, void *out, int is_f64, int64_t count, int levels,
                                         double min_val, const double *mn_mx, hipStream_t st)
 {
-    const int grid = ew_grid(count);
-    if (is_f64)
-        hipLaunchKernelGGL((grid_quantize_safe_kernel<double>), dim3(grid), dim3(EW_BLOCK), 0, st,
-                           (const double *)in, (double *)out, count, levels, min_val, mn_mx);
-    else
-        hipLaunchKernelGGL((grid_quantize_safe_kernel<float>), dim3(grid), dim3(EW_BLOCK), 0, st, (const float *)in,
-                           (float *)out, count, levels, (float)min_val, mn_mx);
-    return hipGetLastError();
+    return nb::pick_real(is_f64, [&](auto real) {
+        using T = typename decltype(real)::type;
+        hipLaunchKernelGGL((grid_quantize_safe_kernel<T>), dim3(ew_grid(count)), dim3(EW_BLOCK), 0, st, (const T *)in, (T *)out,
+                           count, levels, (T)min_val, mn_mx);
+        return hipGetLastError();
+    });
 }
 
 hipError_t nb_launch_cast_hook(const void *in, int in_dt, void *out, int mode, int64_t count, hipStream_t st)
 {
-    const int grid = ew_grid(count);
-#define NB_CAST(TI, TO, MODE) \
-    hipLaunchKernelGGL((cast_hook_kernel<TI, TO, MODE>), dim3(grid), dim3(EW_BLOCK), 0, st, (const TI *)in, (TO *)out, count)
-    if (in_dt == NB_F32) {
-        switch (mode) {
-        case NB_FLOAT64: NB_CAST(float, double, NB_FLOAT64); break;
-        case NB_FLOAT32: NB_CAST(float, float, NB_FLOAT32); break;
-        case NB_BFLOAT16: NB_CAST(float, float, NB_BFLOAT16); break;
-        case NB_FLOAT16: NB_CAST(float, float, NB_FLOAT16); break;
-        default: return hipErrorInvalidValue;
-        }
-    } else if (in_dt == NB_F64) {
-        switch (mode) {
-        case NB_FLOAT64: NB_CAST(double, double, NB_FLOAT64); break;
-        case NB_FLOAT32: NB_CAST(double, float, NB_FLOAT32); break;
-        case NB_BFLOAT16: NB_CAST(double, float, NB_BFLOAT16); break;
-        case NB_FLOAT16: NB_CAST(double, float, NB_FLOAT16); break;
-        default: return hipErrorInvalidValue;
-        }
-    } else {
-        return hipErrorInvalidValue;
-    }
-#undef NB_CAST
-    return hipGetLastError();
+    if (in_dt != NB_F32 && in_dt != NB_F64) return hipErrorInvalidValue;
+    return nb::pick_real(in_dt == NB_F64, [&](auto real) {
+        using TI = typename decltype(real)::type;
+        return nb::pick<NB_FLOAT64, NB_FLOAT32, NB_BFLOAT16, NB_FLOAT16>(mode, [&](auto MODE) {
+            using TO = std::conditional_t<MODE.value == NB_FLOAT64, double, float>;       // the cast modes hand back fp32
+            hipLaunchKernelGGL((cast_hook_kernel<TI, TO, MODE.value>), dim3(ew_grid(count)), dim3(EW_BLOCK), 0, st, (const TI *)in,
+                               (TO *)out, count);
+            return hipGetLastError();
+        });
+    });
 }
 
 hipError_t nb_launch_final_sum(const double *part, int count, double *out, hipStream_t st)
@@ -731,27 +707,26 @@ hipError_t nb_launch_final_sum(const double *part, int count, double *out, hipSt
     return hipGetLastError();
 }
 
+// kinetic_kernel / potential_kernel<T, ..., F32, HP>: HP is the half type the state is typed as (else -1) and F32 says
+// whether the terms are fp32-typed.  Only fp64 storage that is not half-typed has both F32 variants.
 hipError_t nb_launch_kinetic(const void *vel, const void *mass, int n, int dim, int is_f64, int vel_f32_logical,
                              int half_pa, int mass_dt, double *scratch, double *out, hipStream_t st)
 {
     int blocks = (n + NB_BLOCK - 1) / NB_BLOCK;
     if (blocks > 1024) blocks = 1024;
-    if (is_f64) {
-        if (half_pa == NB_F16)
-            hipLaunchKernelGGL((kinetic_kernel<double, true, NB_F16>), dim3(blocks), dim3(NB_BLOCK), 0, st, (const double *)vel, (const double *)mass, n, dim, mass_dt, scratch);
-        else if (half_pa == NB_BF16)
-            hipLaunchKernelGGL((kinetic_kernel<double, true, NB_BF16>), dim3(blocks), dim3(NB_BLOCK), 0, st, (const double *)vel, (const double *)mass, n, dim, mass_dt, scratch);
-        else if (vel_f32_logical)
-            hipLaunchKernelGGL((kinetic_kernel<double, true>), dim3(blocks), dim3(NB_BLOCK), 0, st, (const double *)vel, (const double *)mass, n, dim, mass_dt, scratch);
-        else
-            hipLaunchKernelGGL((kinetic_kernel<double, false>), dim3(blocks), dim3(NB_BLOCK), 0, st, (const double *)vel, (const double *)mass, n, dim, mass_dt, scratch);
-    } else if (half_pa == NB_F16) {
-        hipLaunchKernelGGL((kinetic_kernel<float, true, NB_F16>), dim3(blocks), dim3(NB_BLOCK), 0, st, (const float *)vel, (const float *)mass, n, dim, mass_dt, scratch);
-    } else if (half_pa == NB_BF16) {
-        hipLaunchKernelGGL((kinetic_kernel<float, true, NB_BF16>), dim3(blocks), dim3(NB_BLOCK), 0, st, (const float *)vel, (const float *)mass, n, dim, mass_dt, scratch);
-    } else {
-        hipLaunchKernelGGL((kinetic_kernel<float, true>), dim3(blocks), dim3(NB_BLOCK), 0, st, (const float *)vel, (const float *)mass, n, dim, mass_dt, scratch);
-    }
+    const hipError_t err = nb::pick_real(is_f64, [&](auto real) {
+        using T = typename decltype(real)::type;
+        return nb::pick<-1, NB_F16, NB_BF16>((half_pa == NB_F16 || half_pa == NB_BF16) ? half_pa : -1, [&](auto HP) {
+            auto launch = [&](auto VF32) {
+                hipLaunchKernelGGL((kinetic_kernel<T, VF32.value, HP.value>), dim3(blocks), dim3(NB_BLOCK), 0, st, (const T *)vel,
+                                   (const T *)mass, n, dim, mass_dt, scratch);
+                return hipSuccess;
+            };
+            if constexpr (sizeof(T) == 8 && HP.value < 0) return nb::pick_bool(vel_f32_logical, launch);
+            else return launch(std::true_type{});
+        });
+    });
+    if (err != hipSuccess) return err;
     hipLaunchKernelGGL(final_sum_kernel, dim3(1), dim3(NB_BLOCK), 0, st, scratch, blocks, out);
     return hipGetLastError();
 }
@@ -762,28 +737,21 @@ hipError_t nb_launch_potential(const void *pos, const void *mass, const ForceGeo
 {
     const dim3 grid((g.n + NB_BLOCK - 1) / NB_BLOCK, g.nchunks);
     const float e32 = (half_pa >= 0) ? eps2_half : (float)eps2_py;
-#define NB_PE(T, D, PA) \
-    hipLaunchKernelGGL((potential_kernel<T, D, PA>), grid, dim3(NB_BLOCK), 0, st, (const T *)pos, (const T *)mass, g, eps2_py, e32, mass_dt, scratch)
-    if (dim != 2 && dim != 3) return hipErrorInvalidValue;
-    if (is_f64 && half_pa == NB_F16) {
-        if (dim == 2) hipLaunchKernelGGL((potential_kernel<double, 2, true, NB_F16>), grid, dim3(NB_BLOCK), 0, st, (const double *)pos, (const double *)mass, g, eps2_py, e32, mass_dt, scratch);
-        else hipLaunchKernelGGL((potential_kernel<double, 3, true, NB_F16>), grid, dim3(NB_BLOCK), 0, st, (const double *)pos, (const double *)mass, g, eps2_py, e32, mass_dt, scratch);
-    } else if (is_f64 && half_pa == NB_BF16) {
-        if (dim == 2) hipLaunchKernelGGL((potential_kernel<double, 2, true, NB_BF16>), grid, dim3(NB_BLOCK), 0, st, (const double *)pos, (const double *)mass, g, eps2_py, e32, mass_dt, scratch);
-        else hipLaunchKernelGGL((potential_kernel<double, 3, true, NB_BF16>), grid, dim3(NB_BLOCK), 0, st, (const double *)pos, (const double *)mass, g, eps2_py, e32, mass_dt, scratch);
-    } else if (is_f64) {
-        if (pa_f32) { if (dim == 2) NB_PE(double, 2, true); else NB_PE(double, 3, true); }
-        else        { if (dim == 2) NB_PE(double, 2, false); else NB_PE(double, 3, false); }
-    } else if (half_pa == NB_F16) {
-        if (dim == 2) hipLaunchKernelGGL((potential_kernel<float, 2, true, NB_F16>), grid, dim3(NB_BLOCK), 0, st, (const float *)pos, (const float *)mass, g, eps2_py, e32, mass_dt, scratch);
-        else hipLaunchKernelGGL((potential_kernel<float, 3, true, NB_F16>), grid, dim3(NB_BLOCK), 0, st, (const float *)pos, (const float *)mass, g, eps2_py, e32, mass_dt, scratch);
-    } else if (half_pa == NB_BF16) {
-        if (dim == 2) hipLaunchKernelGGL((potential_kernel<float, 2, true, NB_BF16>), grid, dim3(NB_BLOCK), 0, st, (const float *)pos, (const float *)mass, g, eps2_py, e32, mass_dt, scratch);
-        else hipLaunchKernelGGL((potential_kernel<float, 3, true, NB_BF16>), grid, dim3(NB_BLOCK), 0, st, (const float *)pos, (const float *)mass, g, eps2_py, e32, mass_dt, scratch);
-    } else {
-        if (dim == 2) NB_PE(float, 2, true); else NB_PE(float, 3, true);
-    }
-#undef NB_PE
+    const hipError_t err = nb::pick<2, 3>(dim, [&](auto D) {
+        return nb::pick_real(is_f64, [&](auto real) {
+            using T = typename decltype(real)::type;
+            return nb::pick<-1, NB_F16, NB_BF16>((half_pa == NB_F16 || half_pa == NB_BF16) ? half_pa : -1, [&](auto HP) {
+                auto launch = [&](auto PA_F32) {
+                    hipLaunchKernelGGL((potential_kernel<T, D.value, PA_F32.value, HP.value>), grid, dim3(NB_BLOCK), 0, st,
+                                       (const T *)pos, (const T *)mass, g, eps2_py, e32, mass_dt, scratch);
+                    return hipSuccess;
+                };
+                if constexpr (sizeof(T) == 8 && HP.value < 0) return nb::pick_bool(pa_f32, launch);
+                else return launch(std::true_type{});
+            });
+        });
+    });
+    if (err != hipSuccess) return err;
     hipLaunchKernelGGL(final_sum_kernel, dim3(1), dim3(NB_BLOCK), 0, st, scratch, (int)(grid.x * grid.y), out);
     return hipGetLastError();
 }

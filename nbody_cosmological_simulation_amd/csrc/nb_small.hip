@@ -16,11 +16,10 @@
 // Arithmetic per pair is that of the tuned kernels (fp64: v_rsq_f64 + second-order correction; fp32: reference op
 // order for r2 without fma, cast hooks, v_rsq_f32 + first-order correction, fp32 products summed in fp64).
 #include "nb_device.h"
+#include "nb_dispatch.h"
 #include "nb_small_body.h"
 
 #include <cstdlib>
-
-int nb_small_block(int n);
 
 namespace {
 
@@ -50,24 +49,18 @@ small_step_kernel(const T *__restrict__ pos_in, T *__restrict__ pos_out, T *__re
 }
 
 template <typename T, int D, int HOOK, bool BINS = false>
-hipError_t launch_s(const T *pos_in, T *pos_out, T *vel, T *acc, const T *mass, int n, double G, double eps2, double half_dt,
-                    double dt, int do_kick, int lanes, hipStream_t st, const GridTables *tab = nullptr, double *part = nullptr,
-                    unsigned long long *bin_out = nullptr)
+hipError_t launch_s(const void *pos_in, void *pos_out, void *vel, void *acc, const void *mass, int n, double G, double eps2,
+                    double half_dt, double dt, int do_kick, int lanes, hipStream_t st, const GridTables *tab = nullptr,
+                    double *part = nullptr, unsigned long long *bin_out = nullptr)
 {
-#define NB_SMALL(SS)                                                                                                       \
-    do {                                                                                                                   \
-        if (nb_small_block(n) == 512)                                                                                      \
-            hipLaunchKernelGGL((small_step_kernel<T, D, HOOK, SS, BINS, 512>), dim3((n + 512 / SS - 1) / (512 / SS)), dim3(512), 0, \
-                               st, pos_in, pos_out, vel, acc, mass, n, (T)G, (T)eps2, (T)half_dt, (T)dt, do_kick, tab, part, bin_out); \
-        else                                                                                                               \
-            hipLaunchKernelGGL((small_step_kernel<T, D, HOOK, SS, BINS, 256>), dim3((n + 256 / SS - 1) / (256 / SS)), dim3(256), 0, \
-                               st, pos_in, pos_out, vel, acc, mass, n, (T)G, (T)eps2, (T)half_dt, (T)dt, do_kick, tab, part, bin_out); \
-    } while (0)
-    if (lanes == 64) NB_SMALL(64);
-    else if (lanes == 32) NB_SMALL(32);
-    else NB_SMALL(16);
-#undef NB_SMALL
-    return hipGetLastError();
+    return nb::pick<64, 32, 16>(lanes, [&](auto S) {
+        return nb::pick<512, 256>(nb_small_block(n), [&](auto BS) {
+            hipLaunchKernelGGL((small_step_kernel<T, D, HOOK, S.value, BINS, BS.value>), dim3(nb_small_blocks(n, lanes)),
+                               dim3(BS.value), 0, st, (const T *)pos_in, (T *)pos_out, (T *)vel, (T *)acc, (const T *)mass, n, (T)G,
+                               (T)eps2, (T)half_dt, (T)dt, do_kick, tab, part, bin_out);
+            return hipGetLastError();
+        });
+    });
 }
 
 }  // namespace
@@ -86,6 +79,14 @@ int nb_small_block(int n)
     return (n <= 2048 || n > 3072) ? 512 : 256;
 }
 
+// workgroups of the one-launch step: nb_small_block(n) / lanes targets each.  The force-bound partials (`part`) hold one
+// {min, max} pair per workgroup, so whoever sizes or reads them takes the count from here
+int nb_small_blocks(int n, int lanes)
+{
+    const int targets = nb_small_block(n) / lanes;
+    return (n + targets - 1) / targets;
+}
+
 int nb_small_lanes(int n)
 {
     // measured (fp32, us per step at N = 1024 / 2048 / 3000 / 4096): 16 lanes 6.8 / 11.4 / 15.9 / 20.5, 32 lanes
@@ -98,30 +99,20 @@ hipError_t nb_launch_small_step(const void *pos_in, void *pos_out, void *vel, vo
                                 int is_f64, int hook, double G, double eps2, double half_dt, double dt, int do_kick, int lanes,
                                 hipStream_t st, const GridTables *tab, double *part, unsigned long long *bin_out)
 {
-    if (dim != 2 && dim != 3) return hipErrorInvalidValue;
     if (bin_out && hook != HOOK_GRID) return hipErrorInvalidValue;
-    if (hook == HOOK_GRID) {
-        if (is_f64 || !tab) return hipErrorInvalidValue;
-        const float g32 = (float)G, e32 = (float)eps2;
-        if (bin_out) {          // bin read-out (nb_quant_bin_sums): the same kernel body, BINS = true
-            if (dim == 2) return launch_s<float, 2, HOOK_GRID, true>((const float *)pos_in, (float *)pos_out, (float *)vel, (float *)acc, (const float *)mass, n, g32, e32, half_dt, dt, do_kick, lanes, st, tab, part, bin_out);
-            return launch_s<float, 3, HOOK_GRID, true>((const float *)pos_in, (float *)pos_out, (float *)vel, (float *)acc, (const float *)mass, n, g32, e32, half_dt, dt, do_kick, lanes, st, tab, part, bin_out);
-        }
-        if (dim == 2) return launch_s<float, 2, HOOK_GRID>((const float *)pos_in, (float *)pos_out, (float *)vel, (float *)acc, (const float *)mass, n, g32, e32, half_dt, dt, do_kick, lanes, st, tab, part);
-        return launch_s<float, 3, HOOK_GRID>((const float *)pos_in, (float *)pos_out, (float *)vel, (float *)acc, (const float *)mass, n, g32, e32, half_dt, dt, do_kick, lanes, st, tab, part);
-    }
-    if (is_f64) {
-        if (dim == 2) return launch_s<double, 2, HOOK_NONE>((const double *)pos_in, (double *)pos_out, (double *)vel, (double *)acc, (const double *)mass, n, G, eps2, half_dt, dt, do_kick, lanes, st);
-        return launch_s<double, 3, HOOK_NONE>((const double *)pos_in, (double *)pos_out, (double *)vel, (double *)acc, (const double *)mass, n, G, eps2, half_dt, dt, do_kick, lanes, st);
-    }
-#define NB_SF(DD, HH) launch_s<float, DD, HH>((const float *)pos_in, (float *)pos_out, (float *)vel, (float *)acc, (const float *)mass, n, (double)(float)G, (double)(float)eps2, half_dt, dt, do_kick, lanes, st)
-    if (dim == 2) {
-        if (hook == HOOK_BF16) return NB_SF(2, HOOK_BF16);
-        if (hook == HOOK_F16) return NB_SF(2, HOOK_F16);
-        return NB_SF(2, HOOK_NONE);
-    }
-    if (hook == HOOK_BF16) return NB_SF(3, HOOK_BF16);
-    if (hook == HOOK_F16) return NB_SF(3, HOOK_F16);
-    return NB_SF(3, HOOK_NONE);
-#undef NB_SF
+    if (hook == HOOK_GRID && (is_f64 || !tab)) return hipErrorInvalidValue;
+    // fp32 state: G and eps2 are rounded to fp32 here; a hook the fp32 kernels do not compile in runs as none
+    const double g = is_f64 ? G : (double)(float)G, e = is_f64 ? eps2 : (double)(float)eps2;
+    const int h = (hook == HOOK_BF16 || hook == HOOK_F16) ? hook : HOOK_NONE;
+    return nb::pick<2, 3>(dim, [&](auto D) {
+        if (hook == HOOK_GRID)      // bin_out: the bin read-out (nb_quant_bin_sums), the same kernel body with BINS = true
+            return nb::pick_bool(bin_out != nullptr, [&](auto B) {
+                return launch_s<float, D.value, HOOK_GRID, B.value>(pos_in, pos_out, vel, acc, mass, n, g, e, half_dt, dt, do_kick,
+                                                                    lanes, st, tab, part, bin_out);
+            });
+        if (is_f64) return launch_s<double, D.value, HOOK_NONE>(pos_in, pos_out, vel, acc, mass, n, g, e, half_dt, dt, do_kick, lanes, st);
+        return nb::pick<HOOK_NONE, HOOK_BF16, HOOK_F16>(h, [&](auto H) {
+            return launch_s<float, D.value, H.value>(pos_in, pos_out, vel, acc, mass, n, g, e, half_dt, dt, do_kick, lanes, st);
+        });
+    });
 }

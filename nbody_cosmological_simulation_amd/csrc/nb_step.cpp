@@ -582,7 +582,7 @@ int step_small(nb_sim *s, int nsteps, bool opened, bool first)
         path_note(s, last ? 2 : 1, note.site);
         if (fq)      // one min / max pair per workgroup of the force launch
             HIPCHK(nb_launch_force_quant_finish((float *)s->acc, nd(s), mode_levels(c), s->small_part,
-                                                (c.n + nb_small_block(c.n) / lanes - 1) / (nb_small_block(c.n) / lanes), s->scalars, s->fbins,
+                                                nb_small_blocks(c.n, lanes), s->scalars, s->fbins,
                                                 (float *)s->vel, (float *)s->pos, c.dt / 2, c.dt, closing, s->stream));
         else if (!last)
             std::swap(s->pos, s->pos_alt);

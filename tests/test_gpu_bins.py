@@ -118,13 +118,18 @@ def test_production_pair_loops_bin_like_the_reference(nb, monkeypatch, case, mod
         assert sim.quant_bin_sums("last")["path"] == "small"
 
 
-@pytest.mark.parametrize("general", [False, True])
+@pytest.mark.parametrize("general", [False, True, pytest.param("all-pairs-max", id="all-pairs-max")])
 @pytest.mark.parametrize("mode", GRID)
 def test_config3_full_size_production_bins_vs_reference_rows(nb, monkeypatch, mode, general):
     """BASELINE config 3's real size, N = 65 536: the production plan (tiles of 256, pruned max-r2 search, packed
     uniform-mass kernel -- or the scalar general-mass one) against the reference's bins of six target rows, one of them
     a row of the farthest pair (golden g16 / g20).  The checksums of those rows collect the kernel's decisions from
-    every source tile, from the target side AND the mirrored source side of the symmetric sweep."""
+    every source tile, from the target side AND the mirrored source side of the symmetric sweep.
+    "all-pairs-max": the uniform-mass plan with NB_NO_PRUNE, the all-pairs max-r2 scan with four targets per thread that
+    only sizes above 8192 take (same bins: the maximum is exact either way)."""
+    if general == "all-pairs-max":
+        monkeypatch.setenv("NB_NO_PRUNE", "1")
+        general = False
     if general:
         monkeypatch.setenv("NB_NO_UNIFORM", "1")
     g16 = load_golden("g16_bins_n65536_rows.npz")

@@ -35,7 +35,18 @@ CASES = [
     (3073, 3, "float64"),
     (1300, 2, "bfloat16"), (1300, 2, "float16"),
 ]
-IDS = [f"n{n}-d{d}-{m}" for n, d, m in CASES]
+# 16 / 32 lanes per target instead of the default 64 (NB_SMALL_LANES, read when a handle is created: ensemble and solo runs of
+# a case share it), each in D = 2 and D = 3; N = 257 is one full 256-source stride plus one star, several workgroups
+LANES = {(257, 2, "float32"): 16, (257, 3, "float64"): 16, (257, 3, "float32"): 32, (257, 2, "float64"): 32}
+CASES += list(LANES)
+IDS = [f"n{n}-d{d}-{m}" + (f"-lanes{LANES[n, d, m]}" if (n, d, m) in LANES else "") for n, d, m in CASES]
+
+
+@pytest.fixture(autouse=True)
+def lanes_knob(request, monkeypatch):
+    case = request.node.callspec.params.get("case") if hasattr(request.node, "callspec") else None
+    if case in LANES:
+        monkeypatch.setenv("NB_SMALL_LANES", str(LANES[case]))
 
 
 @pytest.fixture(scope="module")

@@ -38,7 +38,18 @@ CASES = [
     (2049, 3, "custom"), (2049, 2, "int8_sim"),
     (3072, 3, "int4_sim"),
 ]
-IDS = [f"n{n}-d{d}-{m}" for n, d, m in CASES]
+# 16 / 32 lanes per target instead of the default 64 (NB_SMALL_LANES, read when a handle is created: ensemble and solo runs of
+# a case share it), each in D = 2 and D = 3; N = 257 is one full 256-source stride plus one star, several workgroups
+LANES = {(257, 2, "int8_sim"): 16, (257, 3, "custom"): 16, (257, 3, "int4_sim"): 32, (257, 2, "custom"): 32}
+CASES += list(LANES)
+IDS = [f"n{n}-d{d}-{m}" + (f"-lanes{LANES[n, d, m]}" if (n, d, m) in LANES else "") for n, d, m in CASES]
+
+
+@pytest.fixture(autouse=True)
+def lanes_knob(request, monkeypatch):
+    case = request.node.callspec.params.get("case") if hasattr(request.node, "callspec") else None
+    if case in LANES:
+        monkeypatch.setenv("NB_SMALL_LANES", str(LANES[case]))
 DEBUG_KEYS = ("lmin", "lmax", "r2max", "fmin", "fmax", "fast_path")
 
 
