@@ -207,6 +207,21 @@ int nb_ens_energies(nb_ens *e, double *kinetic, double *potential, int on_device
  * Nothing waits on the stream between the first launch and the copy-out of the history at the end. */
 int nb_ens_run_recorded(nb_ens *e, int32_t nsteps, int32_t every, double *kinetic, double *potential,
                         int64_t capacity, int on_device, int32_t *samples);
+/* The diagnostics of nb_metrics (rotation curve, r_percentile, bound fraction, dispersion) for every member, from
+ * the resident state, in ONE kernel launch (one workgroup per member; no host round trip before the copy-out).
+ * num_bins in [0, 255].  max_radius: `members` doubles, each >= 0 or NaN, the end of that member's bin edges; or
+ * NULL: each member's own largest radius, found on the device.  The edges are torch.linspace(0, max_radius[b],
+ * num_bins + 1) in float32, built on the device.  Outputs are host arrays, any may be NULL: curve_mean /
+ * curve_count members * num_bins (member-major; an empty bin has mean NaN), edges members * (num_bins + 1),
+ * scalars members * 5 = per member {max r, r_kth, bound fraction, dispersion, max_radius used}, the layout of
+ * nb_metrics' scalars[5]; G is the member's own.  Per-star arithmetic is nb_metrics' in the state dtype, so bin
+ * membership, bound flags and the order statistic are a solo evaluation's; the fp64 sums behind the centre of
+ * mass, enclosed masses, bin means and dispersion are added in a fixed order of their own (deterministic,
+ * independent of the other members; equal to nb_metrics wherever the value does not depend on that order, else
+ * to 2e-6 relative).  Needs positions, velocities and masses.  Changes neither the state nor force_launches.
+ * NB_ERR_INVALID for num_bins outside [0, 255], a negative max_radius entry or a NaN percentile. */
+int nb_ens_metrics(nb_ens *e, int32_t num_bins, const double *max_radius, double percentile, double *curve_mean,
+                   int64_t *curve_count, float *edges, double *scalars);
 /* members; batched force launches issued since creation (nb_ens_compute_accelerations and one per tick;
  * the opening kick + drift launch of an nb_ens_step is not counted); name of the last force kernel
  * ("ens_step_kernel", or "ens_grid_step_kernel" on a grid-mode handle, whose table and finish launches are

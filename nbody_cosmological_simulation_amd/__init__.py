@@ -6,8 +6,9 @@ called through ctypes (_native.py).  See DESIGN.md.
 from .quantization import (PrecisionMode, quantize_distance_squared, quantize_force, _grid_quantize,
                            _grid_quantize_safe, get_mode_from_string, describe_mode)
 from .simulation import GalaxySimulation, run_comparison
-from .ensemble import GalaxyEnsemble, QuantizedEnsemble, EnergyHistory, check_record_arguments
+from .ensemble import (GalaxyEnsemble, QuantizedEnsemble, EnergyHistory, EnsembleMetrics, check_record_arguments,
+                       check_metrics_arguments)
 
-__all__ = ["GalaxySimulation", "GalaxyEnsemble", "QuantizedEnsemble", "EnergyHistory", "check_record_arguments", "run_comparison", "PrecisionMode", "quantize_distance_squared",
+__all__ = ["GalaxySimulation", "GalaxyEnsemble", "QuantizedEnsemble", "EnergyHistory", "EnsembleMetrics", "check_record_arguments", "check_metrics_arguments", "run_comparison", "PrecisionMode", "quantize_distance_squared",
            "quantize_force", "_grid_quantize", "_grid_quantize_safe", "get_mode_from_string",
            "describe_mode"]

@@ -16,6 +16,7 @@
 // shape kept for that purpose, and nb_energy runs there.  nb_ens_energies and nb_ens_run_recorded evaluate all members at
 // once instead (nb_ens_energy.hip: two launches on the handle's stream, values at the project's bars rather than the
 // solo engine's bits), the latter between the ticks of a run into a history that is copied out once at the end.
+#include <algorithm>
 #include <cstddef>
 #include <cstring>
 
@@ -39,6 +40,11 @@ struct nb_ens {
     double *epart = nullptr;                  // batched energies: members * tile pairs * {pe, ke} slots (created on first use)
     double *ehist = nullptr;                  // batched energies: ehist_cap samples of kinetic, then as many of potential
     int64_t ehist_cap = 0;
+    // batched diagnostics (nb_ens_metrics; created on first use, sized for mbins_cap bins)
+    void *mscratch = nullptr;                 // vt, |v| and bin of every star of every member
+    double *mout = nullptr, *mradius = nullptr;   // members * (5 + 2 mbins_cap) results; members given max_radius
+    float *medges = nullptr;                  // members * (mbins_cap + 1) edges
+    int mbins_cap = -1;
     // grid modes only (nb_ens_create_grid)
     bool grid = false, fq = false;            // HOOK_GRID; INT8 / INT4: forces snapped (and kicks applied) by the finish launch
     int allow_fast = 1;                       // the table-free pair path may be used (NB_NO_GRID_FAST unset), as nb_sim reads it
@@ -125,7 +131,8 @@ void release(nb_ens *e)
 {
     if (e->probe) (void)nb_destroy(e->probe);
     for (void *p : {e->prm, e->pos, e->pos_alt, e->vel, e->acc, e->mass, (void *)e->epart, (void *)e->ehist, (void *)e->tabs,
-                    (void *)e->levels_dev, (void *)e->fpart, (void *)e->fbounds})
+                    (void *)e->levels_dev, (void *)e->fpart, (void *)e->fbounds, e->mscratch, (void *)e->mout, (void *)e->mradius,
+                    (void *)e->medges})
         if (p) (void)hipFree(p);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
@@ -165,6 +172,24 @@ int history_out(nb_ens *e, int64_t samples, double *kinetic, double *potential, 
     if (kinetic) HIPCHK(hipMemcpyAsync(kinetic, e->ehist, bytes, kind, e->stream));
     if (potential) HIPCHK(hipMemcpyAsync(potential, e->ehist + e->ehist_cap * e->cfg.members, bytes, kind, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
+    return NB_OK;
+}
+
+// room for one batched evaluation of the diagnostics with `num_bins` bins (buffers grow, never shrink)
+int metrics_buffers(nb_ens *e, int num_bins)
+{
+    const size_t B = (size_t)e->cfg.members;
+    if (!e->mscratch) HIPCHK(hipMalloc(&e->mscratch, nb_ens_metrics_scratch_bytes(e->cfg.members, e->cfg.n, e->is_f64)));
+    if (!e->mradius) HIPCHK(hipMalloc((void **)&e->mradius, B * sizeof(double)));
+    if (num_bins > e->mbins_cap) {
+        // no launch reads the old results: every call that fills them copies them out and waits before it returns
+        if (e->mout) { (void)hipFree(e->mout); e->mout = nullptr; }
+        if (e->medges) { (void)hipFree(e->medges); e->medges = nullptr; }
+        e->mbins_cap = -1;
+        HIPCHK(hipMalloc((void **)&e->mout, B * (5 + 2 * (size_t)num_bins) * sizeof(double)));
+        HIPCHK(hipMalloc((void **)&e->medges, B * ((size_t)num_bins + 1) * sizeof(float)));
+        e->mbins_cap = num_bins;
+    }
     return NB_OK;
 }
 
@@ -434,6 +459,59 @@ int nb_ens_run_recorded(nb_ens *e, int32_t nsteps, int32_t every, double *kineti
     }
     if (samples) *samples = (int32_t)S;
     return history_out(e, S, kinetic, potential, on_device);
+}
+
+// the diagnostics of every member from the resident state: one launch, two copies, one wait
+int nb_ens_metrics(nb_ens *e, int32_t num_bins, const double *max_radius, double percentile, double *curve_mean,
+                   int64_t *curve_count, float *edges, double *scalars)
+{
+    if (!e) return fail(NB_ERR_INVALID, "null handle");
+    if (!e->have_pos || !e->have_vel || !e->have_mass) return fail(NB_ERR_INVALID, "state incomplete");
+    if (num_bins < 0 || num_bins > 255) return fail(NB_ERR_INVALID, "num_bins must be in [0, 255] (got %d)", num_bins);
+    if (percentile != percentile) return fail(NB_ERR_INVALID, "percentile is NaN");
+    const nb_ens_config &c = e->cfg;
+    const size_t B = (size_t)c.members, nb = (size_t)num_bins;
+    for (size_t b = 0; max_radius && b < B; ++b)
+        if (max_radius[b] < 0.0)
+            return fail(NB_ERR_INVALID, "max_radius[%d] = %g is negative (pass NULL for every member's own maximum radius)",
+                        (int)b, max_radius[b]);
+    DeviceGuard guard(c.device);
+    if (int rc = metrics_buffers(e, num_bins)) return rc;
+    if (max_radius) HIPCHK(hipMemcpyAsync(e->mradius, max_radius, B * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    NbEnsMetricsArgs a{};
+    a.pos = e->pos; a.vel = e->vel; a.mass = e->mass;
+    a.members = c.members; a.n = c.n; a.dim = c.dim; a.is_f64 = e->is_f64;
+    a.prm = e->prm;
+    a.max_radius = max_radius ? e->mradius : nullptr;
+    a.num_bins = num_bins;
+    const long long k = (long long)((double)c.n * percentile / 100.0);     // int(len(radii) * percentile / 100), as nb_metrics
+    a.kth = (int)std::min<long long>(std::max<long long>(k, 0), c.n - 1);
+    a.scratch = e->mscratch;
+    a.out = e->mout;
+    a.edges_out = e->medges;
+    HIPCHK(nb_launch_ens_metrics(a, e->stream));
+    const size_t per = 5 + 2 * nb;
+    std::vector<double> host(B * per);
+    HIPCHK(hipMemcpyAsync(host.data(), e->mout, host.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    if (edges && nb > 0)
+        HIPCHK(hipMemcpyAsync(edges, e->medges, B * (nb + 1) * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));         // (also: the upload has consumed max_radius)
+    for (size_t b = 0; b < B; ++b) {
+        const double *h = host.data() + b * per;
+        if (scalars) {
+            double *o = scalars + b * 5;
+            o[0] = h[0];
+            o[1] = h[1];
+            o[2] = (double)((float)h[2] / (float)c.n);       // bound_mask.float().mean(), as nb_metrics forms it
+            o[3] = h[3];
+            o[4] = h[4];
+        }
+        for (size_t q = 0; q < nb; ++q) {
+            if (curve_mean) curve_mean[b * nb + q] = h[5 + q];
+            if (curve_count) curve_count[b * nb + q] = (int64_t)h[5 + nb + q];
+        }
+    }
+    return NB_OK;
 }
 
 int nb_ens_info(nb_ens *e, int32_t *members, int64_t *force_launches, const char **kernel_name)

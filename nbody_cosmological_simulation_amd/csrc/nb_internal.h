@@ -346,6 +346,23 @@ int nb_ens_energy_pairs(int n);     // tile pairs of the upper triangle: 136 at 
 hipError_t nb_launch_ens_energy(const void *pos, const void *vel, const void *mass, int members, int n, int dim, int is_f64,
                                 const void *prm, double *part, double *kinetic, double *potential, int64_t sample,
                                 hipStream_t st);
+// ---- batched diagnostics of an ensemble (nb_ens_metrics.hip) -------------------------------------------------------------
+// ONE launch on `st`, one workgroup per member: the four diagnostics of nb_launch_metrics for every member, from the
+// ensemble's (members, n, dim) / (members, n) state of type A = storage = fp32 or fp64.  G comes from the member's scalars.
+struct NbEnsMetricsArgs {
+    const void *pos, *vel, *mass;   // device
+    int members, n, dim, is_f64;
+    const void *prm;                // device, NB_ENS_PARAM_WORDS elements of the storage type per member
+    const double *max_radius;       // device, `members` entries (>= 0 or NaN), or null: each member's own radii.max()
+    int num_bins;                   // rotation-curve bins (<= 255)
+    int kth;                        // order statistic of the radii to report (min(int(N p / 100), N - 1))
+    void *scratch;                  // device, nb_ens_metrics_scratch_bytes(members, n, is_f64): vt, |v|, bin of every star
+    double *out;                    // device, per member 5 + 2 num_bins doubles: max r, r_kth, bound count, dispersion,
+                                    // max_radius used, means[nb], counts[nb]
+    float *edges_out;               // device, per member num_bins + 1 float32 edges
+};
+size_t nb_ens_metrics_scratch_bytes(int members, int n, int is_f64);
+hipError_t nb_launch_ens_metrics(const NbEnsMetricsArgs &a, hipStream_t st);
 // second half of nb_launch_force_quant_step with caller-provided min / max partials (nblocks pairs of doubles)
 hipError_t nb_launch_force_quant_finish(float *acc, int64_t count, int levels, const double *partials, int nblocks,
                                         double *mn_mx, int16_t *bins, float *vel, float *pos, double half_dt, double dt,

@@ -32,8 +32,20 @@ the tables of its solo run and the member stays bit-identical to `GalaxySimulati
 is two launches over all members (max r^2 + tables, pair sweep) and under INT8 / INT4 a third (force snap + kicks);
 `quant_debug()` reads every member's grid bounds back.  It inherits everything else from `GalaxyEnsemble`.
 
+Galaxy diagnostics -- the rotation curve the sweeps record beside the energies, and `collect_metrics`' radius, bound
+fraction and dispersion -- are batched too: `metrics(num_bins, max_radius, percentile)` evaluates all four diagnostics of
+metrics.py for every member from the device-resident state in ONE launch (one workgroup per member,
+csrc/nb_ens_metrics.hip: both rankings are sorted in LDS, the edges are built on the device from the member's own
+maximum radius or its given `max_radius[b]`, G is the member's own) and returns an `EnsembleMetrics`.  Contract: every
+per-star decision (bin membership, bound flag, order statistic) and every returned number equals what
+`metrics.native_metrics` gives for that member alone wherever the value does not depend on the order of a float64 sum
+-- bit for bit; where it can (the centre of mass, enclosed masses, bin means and dispersion of arbitrary masses) bin means
+and dispersion agree to 2e-6 relative, `galaxy_radius`, counts and edges exactly and the bound fraction to 3 / N.  Members
+never influence each other; the trajectory, the tick and `launches()` are untouched.  Not part of it: metric samples
+inside `run_recorded`, float16 / bfloat16-typed evaluation (the state is fp32 or fp64), more than 255 bins, mixed dtypes.
+
 Not covered: more than 256 levels, mixed modes within one ensemble, per-member tick counts, mixed dtypes and the
-fp32 -> fp64 promotion timeline, subclass overrides, metrics, checkpoints, multi-GPU.
+fp32 -> fp64 promotion timeline, subclass overrides, checkpoints, multi-GPU.
 """
 import ctypes as C
 import numbers
@@ -48,6 +60,7 @@ from .quantization import PrecisionMode, mode_code, _TORCH_TO_NB
 
 MAX_MEMBERS = 1024
 MAX_STARS = {torch.float64: 4096, torch.float32: 3072}     # the solo one-launch step's limits (csrc/nb_step.cpp)
+MAX_BINS = 255                        # rotation-curve bins of metrics() (csrc/nb_ens_metrics.hip: the edges live in LDS)
 MAX_HISTORY_BYTES = 256 << 20         # an EnergyHistory's kinetic + potential samples (16 bytes per member and sample)
 _MODES = (PrecisionMode.FLOAT64, PrecisionMode.FLOAT32, PrecisionMode.BFLOAT16, PrecisionMode.FLOAT16)
 _GRID_MODES = (PrecisionMode.INT8_SIM, PrecisionMode.INT4_SIM, PrecisionMode.CUSTOM)
@@ -188,6 +201,63 @@ def check_record_arguments(num_ticks, every, members) -> list:
         raise ValueError(f"{samples} samples of {members} members are {samples * members * 16} bytes of history, above the "
                          f"limit of {MAX_HISTORY_BYTES}: raise `every` (or record the run in shorter stretches)")
     return list(range(0, num_ticks + 1, every))
+
+
+def check_metrics_arguments(num_bins, max_radius, percentile, members):
+    """Validate metrics()' arguments without touching a device.  Returns (num_bins, max_radius, percentile) with
+    max_radius None (every member's own maximum radius) or a list of `members` floats; raises TypeError / ValueError."""
+    for name, v in (("num_bins", num_bins), ("members", members)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise TypeError(f"{name} must be an int, got {type(v).__name__}")
+    num_bins, members = int(num_bins), int(members)
+    if members < 1:
+        raise ValueError(f"members must be >= 1, got {members}")
+    if not 0 <= num_bins <= MAX_BINS:
+        raise ValueError(f"num_bins must be in [0, {MAX_BINS}], got {num_bins}")
+    if isinstance(percentile, bool) or not isinstance(percentile, numbers.Real):
+        raise TypeError(f"percentile must be a number, got {type(percentile).__name__}")
+    if percentile != percentile:
+        raise ValueError("percentile is NaN")
+    if max_radius is not None:
+        if isinstance(max_radius, torch.Tensor) or type(max_radius).__module__ == "numpy" and hasattr(max_radius, "tolist"):
+            max_radius = max_radius.tolist()
+        elif isinstance(max_radius, Sequence) and not isinstance(max_radius, (str, bytes)):
+            max_radius = list(max_radius)
+        entries = max_radius if isinstance(max_radius, (list, tuple)) else [max_radius]
+        for v in entries:
+            if isinstance(v, bool) or not isinstance(v, numbers.Real):
+                raise TypeError(f"max_radius must be None, a number or a sequence of numbers, got {type(v).__name__}")
+            if v < 0:
+                raise ValueError(f"max_radius must be >= 0, got {v}")
+        if not isinstance(max_radius, (list, tuple)):
+            max_radius = [max_radius] * members
+        elif len(max_radius) != members:
+            raise ValueError(f"max_radius has {len(max_radius)} entries for {members} members")
+        max_radius = [float(v) for v in max_radius]
+    return num_bins, max_radius, float(percentile)
+
+
+class EnsembleMetrics(NamedTuple):
+    """What metrics() returns, numpy arrays with the member first: `edges` (B, num_bins + 1) float32 and the bin centres
+    `radii` (B, num_bins) float32; `velocities` (B, num_bins) float64, the mean tangential speed per bin (NaN where
+    `num_stars_per_bin`, int64, is 0); and (B,) float64 `max_radius` (the end of the edges), `galaxy_radius` (the
+    percentile radius), `bound_fraction` and `velocity_dispersion`."""
+    edges: "np.ndarray"
+    radii: "np.ndarray"
+    velocities: "np.ndarray"
+    num_stars_per_bin: "np.ndarray"
+    max_radius: "np.ndarray"
+    galaxy_radius: "np.ndarray"
+    bound_fraction: "np.ndarray"
+    velocity_dispersion: "np.ndarray"
+
+    def rotation_curve(self, b: int) -> dict:
+        """Member b's curve as the reference's compute_rotation_curve dict (metrics.py:74-78)."""
+        b = int(b)
+        if not 0 <= b < self.edges.shape[0]:
+            raise IndexError(f"member {b} of {self.edges.shape[0]}")
+        return {"radii": self.radii[b], "velocities": self.velocities[b],
+                "num_stars_per_bin": [int(c) for c in self.num_stars_per_bin[b]]}
 
 
 class EnergyHistory(NamedTuple):
@@ -353,6 +423,26 @@ class GalaxyEnsemble:
         N.check(N.lib().nb_ens_energies(self._handle, C.c_void_p(ke.data_ptr()), C.c_void_p(pe.data_ptr()),
                                         int(self.device.type == "cuda")))
         return ke, pe
+
+    def metrics(self, num_bins: int = 20, max_radius=None, percentile: float = 90) -> EnsembleMetrics:
+        """Rotation curve, percentile radius, bound fraction and velocity dispersion of every member (reference
+        metrics.py:25-156) from the resident state: one launch, one copy-out.  `max_radius`: None (each member's own
+        maximum radius), a number, or one per member."""
+        import numpy as np
+        num_bins, max_radius, percentile = check_metrics_arguments(num_bins, max_radius, percentile, self.num_members)
+        B = self.num_members
+        mean = np.empty((B, num_bins), np.float64)
+        count = np.empty((B, num_bins), np.int64)
+        edges = np.empty((B, num_bins + 1), np.float32)
+        sc = np.empty((B, 5), np.float64)
+        N.check(N.lib().nb_ens_metrics(self._handle, num_bins, _doubles(max_radius) if max_radius is not None else None,
+                                       percentile, mean.ctypes.data_as(C.POINTER(C.c_double)),
+                                       count.ctypes.data_as(C.POINTER(C.c_int64)),
+                                       edges.ctypes.data_as(C.POINTER(C.c_float)), sc.ctypes.data_as(C.POINTER(C.c_double))))
+        if num_bins == 0:                 # linspace(0, R, 1) is [0] (the library writes no edges without bins)
+            edges[:] = 0
+        radii = ((edges[:, :-1] + edges[:, 1:]) / np.float32(2)).astype(np.float32)
+        return EnsembleMetrics(edges, radii, mean, count, sc[:, 4].copy(), sc[:, 1].copy(), sc[:, 2].copy(), sc[:, 3].copy())
 
     def _energy(self, kinetic, potential):
         B = self.num_members
