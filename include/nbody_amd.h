@@ -207,6 +207,33 @@ int nb_ens_energies(nb_ens *e, double *kinetic, double *potential, int on_device
  * Nothing waits on the stream between the first launch and the copy-out of the history at the end. */
 int nb_ens_run_recorded(nb_ens *e, int32_t nsteps, int32_t every, double *kinetic, double *potential,
                         int64_t capacity, int on_device, int32_t *samples);
+/* Every member with a tick budget of its own, and optionally the reference's explosion watch
+ * (stability_test.py:34-61,94-105), in one call with no host round trip between ticks.  nsteps: `members`
+ * budgets, each >= 0.  Member b takes exactly nsteps[b] leapfrog ticks and is then left alone by every later
+ * launch of the call, its positions, velocities and accelerations bit-identical to nb_ens_step(nsteps[b]) of it
+ * alone (a budget of 0: not touched); max(nsteps) force launches are issued over all members (force_launches
+ * grows by that), a stopped member's workgroups return after reading their member's stop tick.
+ * every = 0: no samples (kinetic, potential, capacity and samples are not used; *samples = 0).  every >= 1: the
+ * history of nb_ens_run_recorded(max(nsteps), every), layout and sampling rule as there (capacity >=
+ * 1 + max(nsteps) / every); a stopped member keeps being sampled at its frozen state.
+ * watch = 1 (needs every >= 1): at every sampled tick after the first, behind the energy launches, each member
+ * that is still running is tested on the device, in this order: a non-finite position or velocity
+ * (NB_ENS_REASON_NONFINITE); fabs(E0) > 1e-10 && fabs(E - E0) / fabs(E0) > 10.0 (NB_ENS_REASON_ENERGY);
+ * E0 < 0 && E > fabs(E0) (NB_ENS_REASON_UNBOUND), with E0 / E = kinetic + potential of sample 0 / this sample in
+ * double.  A member that trips one is halted at that tick (a sampled tick is issued closed, so its state is
+ * that of nb_ens_step(tick)).  A NaN energy by itself trips nothing, as in the reference.
+ * stop_tick / reason: host arrays of `members` entries, either may be NULL, copied once at the end of the call:
+ * the tick of this call at which the member stopped (its budget, or the tick that halted it) and why (0 unless
+ * halted).  With equal budgets and watch = 0 the launches, the trajectory and the history are those of
+ * nb_ens_run_recorded, bit for bit.  Preconditions of nb_ens_step; NB_ERR_INVALID for a negative budget, every < 0,
+ * watch without samples, or too small a capacity. */
+#define NB_ENS_REASON_NONE      0
+#define NB_ENS_REASON_NONFINITE 1
+#define NB_ENS_REASON_ENERGY    2
+#define NB_ENS_REASON_UNBOUND   3
+int nb_ens_run_members(nb_ens *e, const int32_t *nsteps, int32_t every, int32_t watch, double *kinetic,
+                       double *potential, int64_t capacity, int on_device, int32_t *samples, int32_t *stop_tick,
+                       int32_t *reason);
 /* The diagnostics of nb_metrics (rotation curve, r_percentile, bound fraction, dispersion) for every member, from
  * the resident state, in ONE kernel launch (one workgroup per member; no host round trip before the copy-out).
  * num_bins in [0, 255].  max_radius: `members` doubles, each >= 0 or NaN, the end of that member's bin edges; or

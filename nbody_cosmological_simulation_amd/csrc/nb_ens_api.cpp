@@ -16,6 +16,11 @@
 // shape kept for that purpose, and nb_energy runs there.  nb_ens_energies and nb_ens_run_recorded evaluate all members at
 // once instead (nb_ens_energy.hip: two launches on the handle's stream, values at the project's bars rather than the
 // solo engine's bits), the latter between the ticks of a run into a history that is copied out once at the end.
+//
+// nb_ens_step, nb_ens_run_recorded and nb_ens_run_members issue ONE launch train (run_train).  The last gives every member
+// a stop tick of its own in a device array that every kernel of the tick path reads (nb_ensemble.hip) and that the
+// explosion watch (nb_ens_watch.hip) lowers on the device; the first two pass no array: no member ever stops, and the
+// kernels launched are the instantiations without stops.
 #include <algorithm>
 #include <cstddef>
 #include <cstring>
@@ -53,6 +58,9 @@ struct nb_ens {
     GridTables *tabs = nullptr;               // device: one per member (max r2, arrival counter, the evaluation's tables)
     int *levels_dev = nullptr;
     double *fpart = nullptr, *fbounds = nullptr;   // INT8 / INT4: members * grid_blocks * 2 partials; members * {fmin, fmax}
+    // nb_ens_run_members (created on first use): members stop ticks, then members halt reasons; what is uploaded / read back
+    int32_t *stops = nullptr;
+    std::vector<int32_t> stops_host;
 };
 
 namespace {
@@ -81,18 +89,19 @@ int upload_params(nb_ens *e)
     return NB_OK;
 }
 
-// one evaluation of a grid-mode ensemble, as step_small issues a solo one
-int launch_force_grid(nb_ens *e, int do_kick)
+// one evaluation of a grid-mode ensemble, as step_small issues a solo one (stop / t: nb_internal.h)
+int launch_force_grid(nb_ens *e, int do_kick, const int *stop, int t)
 {
     const nb_ens_config &c = e->cfg;
     HIPCHK(nb_launch_ens_r2max_tables((const float *)e->pos, c.members, c.n, c.dim, e->prm, e->tabs, e->levels_dev, 0.01f,
-                                      e->allow_fast, e->stream));
+                                      e->allow_fast, stop, t, e->stream));
     HIPCHK(nb_launch_ens_grid_step((const float *)e->pos, (float *)e->pos_alt, (float *)e->vel, (float *)e->acc,
                                    (const float *)e->mass, c.members, c.n, c.dim, e->prm, e->fq ? NB_KICK_NONE : do_kick, e->lanes,
-                                   e->tabs, e->fq ? e->fpart : nullptr, e->stream));
+                                   e->tabs, e->fq ? e->fpart : nullptr, stop, t, e->stream));
     if (e->fq)      // levels[0]: under INT8 / INT4 every member has the mode's 256 / 16 levels
         HIPCHK(nb_launch_ens_force_quant_finish((float *)e->acc, c.members, c.n * c.dim, e->levels[0], e->fpart, e->grid_blocks,
-                                                e->fbounds, (float *)e->vel, (float *)e->pos, e->prm, do_kick, e->stream));
+                                                e->fbounds, (float *)e->vel, (float *)e->pos, e->prm, do_kick, stop, t,
+                                                e->stream));
     e->force_launches++;
     e->last_kernel = "ens_grid_step_kernel";
     return NB_OK;
@@ -104,12 +113,12 @@ inline void advance_positions(nb_ens *e)
     if (!e->fq) std::swap(e->pos, e->pos_alt);
 }
 
-int launch_force(nb_ens *e, int do_kick)
+int launch_force(nb_ens *e, int do_kick, const int *stop = nullptr, int t = 0)
 {
     const nb_ens_config &c = e->cfg;
-    if (e->grid) return launch_force_grid(e, do_kick);
+    if (e->grid) return launch_force_grid(e, do_kick, stop, t);
     HIPCHK(nb_launch_ens_step(e->pos, e->pos_alt, e->vel, e->acc, e->mass, c.members, c.n, c.dim, e->is_f64, e->hook, e->prm,
-                              do_kick, e->lanes, e->stream));
+                              do_kick, e->lanes, stop, t, e->stream));
     e->force_launches++;
     e->last_kernel = "ens_step_kernel";
     return NB_OK;
@@ -132,7 +141,7 @@ void release(nb_ens *e)
     if (e->probe) (void)nb_destroy(e->probe);
     for (void *p : {e->prm, e->pos, e->pos_alt, e->vel, e->acc, e->mass, (void *)e->epart, (void *)e->ehist, (void *)e->tabs,
                     (void *)e->levels_dev, (void *)e->fpart, (void *)e->fbounds, e->mscratch, (void *)e->mout, (void *)e->mradius,
-                    (void *)e->medges})
+                    (void *)e->medges, (void *)e->stops})
         if (p) (void)hipFree(p);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
@@ -164,14 +173,59 @@ int launch_energy(nb_ens *e, int64_t s, bool with_kinetic)
     return NB_OK;
 }
 
-// the first `samples` samples to the caller's arrays (either may be null), then the one wait of the call
+// the first `samples` samples (may be 0) to the caller's arrays (either may be null), then the one wait of the call
 int history_out(nb_ens *e, int64_t samples, double *kinetic, double *potential, int on_device)
 {
     const size_t bytes = (size_t)samples * e->cfg.members * sizeof(double);
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (kinetic) HIPCHK(hipMemcpyAsync(kinetic, e->ehist, bytes, kind, e->stream));
-    if (potential) HIPCHK(hipMemcpyAsync(potential, e->ehist + e->ehist_cap * e->cfg.members, bytes, kind, e->stream));
+    if (kinetic && bytes) HIPCHK(hipMemcpyAsync(kinetic, e->ehist, bytes, kind, e->stream));
+    if (potential && bytes) HIPCHK(hipMemcpyAsync(potential, e->ehist + e->ehist_cap * e->cfg.members, bytes, kind, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
+    return NB_OK;
+}
+
+// The launch train of nb_ens_step / nb_ens_run_recorded / nb_ens_run_members: `nmax` ticks (simulation.py:120-143).  One
+// elementwise launch opens the first tick (kick + drift), then one force launch per tick closes it and opens the next
+// (NB_KICK_CLOSE_OPEN: the drifted positions go to the second buffer); the last one only closes.  every >= 1: sample 0 is
+// taken at entry, and a sampled tick is issued as a one-tick nb_ens_step issues it -- the force launch only closes the tick
+// (velocities and positions are then what a reader sees), the two energy launches follow, under `watch` the explosion
+// watch, and a separate kick + drift launch opens the next tick.  stop: null, or the members' stop ticks on the device;
+// every launch of the tick path gets it with the number of ticks closed so far.  Nothing waits on the stream.
+int run_train(nb_ens *e, int32_t nmax, int32_t every, int *stop, bool watch)
+{
+    const nb_ens_config &c = e->cfg;
+    auto open_tick = [&](int t) {
+        return nb_launch_ens_kick_drift(e->pos, e->vel, e->acc, c.members, c.n, c.dim, e->is_f64, e->prm, stop, t, e->stream);
+    };
+    if (every)
+        if (int rc = launch_energy(e, 0, true)) return rc;
+    if (nmax >= 1) HIPCHK(open_tick(0));
+    for (int t = 1; t <= nmax; ++t) {
+        const bool last = (t == nmax), sampled = (every && t % every == 0);
+        if (sampled || last) {
+            if (int rc = launch_force(e, NB_KICK_CLOSE, stop, t - 1)) return rc;
+            if (sampled) {
+                if (int rc = launch_energy(e, t / every, true)) return rc;
+                if (watch)
+                    HIPCHK(nb_launch_ens_watch(e->pos, e->vel, c.members, c.n, c.dim, e->is_f64, e->ehist,
+                                               e->ehist + e->ehist_cap * c.members, t / every, t, stop, stop + c.members,
+                                               e->stream));
+            }
+            if (!last) HIPCHK(open_tick(t));
+        } else {
+            if (int rc = launch_force(e, NB_KICK_CLOSE_OPEN, stop, t - 1)) return rc;
+            advance_positions(e);                        // the launch wrote the drifted positions to the second buffer
+        }
+    }
+    return NB_OK;
+}
+
+// what every stepping entry asks of the handle
+int check_steppable(const nb_ens *e)
+{
+    if (!e) return fail(NB_ERR_INVALID, "null handle");
+    if (!e->have_pos || !e->have_vel || !e->have_mass) return fail(NB_ERR_INVALID, "state incomplete");
+    if (!e->have_acc) return fail(NB_ERR_INVALID, "no accelerations yet: call nb_ens_compute_accelerations first");
     return NB_OK;
 }
 
@@ -368,23 +422,13 @@ int nb_ens_compute_accelerations(nb_ens *e)
     return NB_OK;
 }
 
-// `nsteps` leapfrog ticks of every member (simulation.py:120-143): one elementwise launch for the opening kick + drift,
-// then one force launch per tick that closes the tick and opens the next (the last one only closes)
+// `nsteps` leapfrog ticks of every member: run_train without samples
 int nb_ens_step(nb_ens *e, int32_t nsteps)
 {
-    if (!e) return fail(NB_ERR_INVALID, "null handle");
-    if (!e->have_pos || !e->have_vel || !e->have_mass) return fail(NB_ERR_INVALID, "state incomplete");
-    if (!e->have_acc) return fail(NB_ERR_INVALID, "no accelerations yet: call nb_ens_compute_accelerations first");
+    if (int rc = check_steppable(e)) return rc;
     if (nsteps < 1) return NB_OK;
     DeviceGuard guard(e->cfg.device);
-    const nb_ens_config &c = e->cfg;
-    HIPCHK(nb_launch_ens_kick_drift(e->pos, e->vel, e->acc, c.members, c.n, c.dim, e->is_f64, e->prm, e->stream));
-    for (int t = 0; t < nsteps; ++t) {
-        const bool last = (t + 1 == nsteps);
-        if (int rc = launch_force(e, last ? NB_KICK_CLOSE : NB_KICK_CLOSE_OPEN)) return rc;
-        if (!last) advance_positions(e);                // the launch wrote the drifted positions to the second buffer
-    }
-    return NB_OK;
+    return run_train(e, nsteps, 0, nullptr, false);
 }
 
 int nb_ens_energy(nb_ens *e, double *kinetic, double *potential)
@@ -424,16 +468,12 @@ int nb_ens_energies(nb_ens *e, double *kinetic, double *potential, int on_device
     return history_out(e, 1, kinetic, potential, on_device);
 }
 
-// nb_ens_step's launches, with a sampled tick issued as the step loop issues it: the force launch only closes the tick
-// (velocities and positions are then what a reader sees), the two energy launches follow, and a separate kick + drift
-// launch opens the next tick.  Nothing waits on the stream before history_out.
+// run_train with samples; nothing waits on the stream before history_out
 int nb_ens_run_recorded(nb_ens *e, int32_t nsteps, int32_t every, double *kinetic, double *potential, int64_t capacity,
                         int on_device, int32_t *samples)
 {
-    if (!e) return fail(NB_ERR_INVALID, "null handle");
     if (samples) *samples = 0;
-    if (!e->have_pos || !e->have_vel || !e->have_mass) return fail(NB_ERR_INVALID, "state incomplete");
-    if (!e->have_acc) return fail(NB_ERR_INVALID, "no accelerations yet: call nb_ens_compute_accelerations first");
+    if (int rc = check_steppable(e)) return rc;
     if (nsteps < 0) return fail(NB_ERR_INVALID, "nsteps must be >= 0 (got %d)", nsteps);
     if (every < 1) return fail(NB_ERR_INVALID, "every must be >= 1 (got %d)", every);
     const int64_t S = 1 + nsteps / every;
@@ -441,24 +481,49 @@ int nb_ens_run_recorded(nb_ens *e, int32_t nsteps, int32_t every, double *kineti
         return fail(NB_ERR_INVALID, "capacity of %lld samples is below the %lld of %d ticks sampled every %d",
                     (long long)capacity, (long long)S, nsteps, every);
     DeviceGuard guard(e->cfg.device);
-    const nb_ens_config &c = e->cfg;
     if (int rc = energy_buffers(e, S)) return rc;
-    if (int rc = launch_energy(e, 0, true)) return rc;
-    if (nsteps >= 1) HIPCHK(nb_launch_ens_kick_drift(e->pos, e->vel, e->acc, c.members, c.n, c.dim, e->is_f64, e->prm, e->stream));
-    for (int t = 1; t <= nsteps; ++t) {
-        const bool last = (t == nsteps), sampled = (t % every == 0);
-        if (sampled || last) {
-            if (int rc = launch_force(e, NB_KICK_CLOSE)) return rc;
-            if (sampled)
-                if (int rc = launch_energy(e, t / every, true)) return rc;
-            if (!last) HIPCHK(nb_launch_ens_kick_drift(e->pos, e->vel, e->acc, c.members, c.n, c.dim, e->is_f64, e->prm, e->stream));
-        } else {
-            if (int rc = launch_force(e, NB_KICK_CLOSE_OPEN)) return rc;
-            advance_positions(e);                        // the launch wrote the drifted positions to the second buffer
-        }
-    }
+    if (int rc = run_train(e, nsteps, every, nullptr, false)) return rc;
     if (samples) *samples = (int32_t)S;
     return history_out(e, S, kinetic, potential, on_device);
+}
+
+// run_train with the members' budgets as their stop ticks (and the watch lowering them); one upload in front of the
+// launches, one read-back of stop ticks and reasons behind them, one wait
+int nb_ens_run_members(nb_ens *e, const int32_t *nsteps, int32_t every, int32_t watch, double *kinetic, double *potential,
+                       int64_t capacity, int on_device, int32_t *samples, int32_t *stop_tick, int32_t *reason)
+{
+    if (samples) *samples = 0;
+    if (int rc = check_steppable(e)) return rc;
+    if (!nsteps) return fail(NB_ERR_INVALID, "null nsteps");
+    const int B = e->cfg.members;
+    int32_t nmax = 0;
+    for (int b = 0; b < B; ++b) {
+        if (nsteps[b] < 0) return fail(NB_ERR_INVALID, "nsteps[%d] must be >= 0 (got %d)", b, nsteps[b]);
+        nmax = std::max(nmax, nsteps[b]);
+    }
+    if (every < 0) return fail(NB_ERR_INVALID, "every must be >= 0 (got %d)", every);
+    if (watch != 0 && watch != 1) return fail(NB_ERR_INVALID, "watch must be 0 or 1 (got %d)", watch);
+    if (watch && every < 1) return fail(NB_ERR_INVALID, "the watch tests sampled ticks: it needs every >= 1");
+    const int64_t S = every ? 1 + nmax / every : 0;
+    if (capacity < S)
+        return fail(NB_ERR_INVALID, "capacity of %lld samples is below the %lld of %d ticks sampled every %d",
+                    (long long)capacity, (long long)S, nmax, every);
+    DeviceGuard guard(e->cfg.device);
+    if (S)
+        if (int rc = energy_buffers(e, S)) return rc;
+    const size_t bytes = 2 * (size_t)B * sizeof(int32_t);
+    if (!e->stops) HIPCHK(hipMalloc((void **)&e->stops, bytes));
+    // stops_host is free to rewrite: every call that uploads it waits before it returns
+    e->stops_host.assign(2 * (size_t)B, NB_ENS_REASON_NONE);
+    std::copy(nsteps, nsteps + B, e->stops_host.begin());
+    HIPCHK(hipMemcpyAsync(e->stops, e->stops_host.data(), bytes, hipMemcpyHostToDevice, e->stream));
+    if (int rc = run_train(e, nmax, every, e->stops, watch != 0)) return rc;
+    HIPCHK(hipMemcpyAsync(e->stops_host.data(), e->stops, bytes, hipMemcpyDeviceToHost, e->stream));
+    if (int rc = history_out(e, S, kinetic, potential, on_device)) return rc;      // (waits, with S = 0 too)
+    if (stop_tick) std::copy(e->stops_host.begin(), e->stops_host.begin() + B, stop_tick);
+    if (reason) std::copy(e->stops_host.begin() + B, e->stops_host.end(), reason);
+    if (samples) *samples = (int32_t)S;
+    return NB_OK;
 }
 
 // the diagnostics of every member from the resident state: one launch, two copies, one wait

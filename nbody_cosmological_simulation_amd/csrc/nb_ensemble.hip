@@ -9,6 +9,17 @@
 // The grid modes (INT8 / INT4 / CUSTOM) run small_grid_body the same way, each member with its own tables
 // (ens_grid_step_kernel); their max-r2 + tables launch is ens_r2max_tables_kernel (nb_force.hip) and the INT8 / INT4 force
 // snap ens_force_quant_finish_kernel (nb_misc.hip).
+//
+// Per-member stops (nb_ens_run_members): every kernel of the tick path takes `stop` (device, one int per member, or null:
+// no member ever stops) and the launch's tick index t = ticks the call has already closed.  The kernels come in two
+// instantiations, STOPS = false for a launch without the array: its code is what it was before there were stops.  (One
+// kernel with a run-time null test was measured first, N = 1024 on an MI355X: the test sits in front of the loads of the
+// other kernel arguments, a scalar-memory round trip of its own in every launch, +0.3 to +0.9 us per launch.)  With
+// STOPS a workgroup reads its member's stop once: left = stop[b] - t ticks are still the member's.  left <= 0: the member is done and the workgroup
+// returns; left == 1: this launch closes the member's last tick, so it gets NB_KICK_CLOSE whatever the launch's mode is;
+// else the launch's own mode.  Where the positions ping-pong, a member on its last tick (left == 1) or just stopped
+// (left == 0: budget 0, or halted by the watch kernel behind the previous launch) also gets its positions carried into
+// the second buffer, bit for bit, so that both buffers hold a stopped member's final positions whatever the host swaps later.
 #include "nb_dispatch.h"
 #include "nb_small_body.h"
 #include "nb_internal.h"
@@ -25,29 +36,56 @@ struct EnsScalars {
 static_assert(sizeof(EnsScalars<double>) == NB_ENS_PARAM_WORDS * 8 && sizeof(EnsScalars<float>) == NB_ENS_PARAM_WORDS * 4,
               "the host fills NB_ENS_PARAM_WORDS elements per member");
 
-template <typename T, int D, int HOOK, int S, int BS>
+// a stopped member's positions into the second buffer: this workgroup's own targets, nobody else writes or reads them there
+template <typename T, int D, int S, int BS>
+__device__ __forceinline__ void ens_carry_positions(const T *__restrict__ pos_in, T *__restrict__ pos_out, int n)
+{
+    constexpr int PER = BS / S * D;                  // elements of this workgroup's targets
+    const int k = blockIdx.x * PER + threadIdx.x;
+    if (threadIdx.x < PER && k < n * D) pos_out[k] = pos_in[k];
+}
+
+template <typename T, int D, int HOOK, int S, int BS, bool STOPS>
 __global__ void __launch_bounds__(BS)
 ens_step_kernel(const T *__restrict__ pos_in, T *__restrict__ pos_out, T *__restrict__ vel, T *__restrict__ acc,
-                const T *__restrict__ mass, int n, const EnsScalars<T> *__restrict__ prm, int do_kick)
+                const T *__restrict__ mass, int n, const EnsScalars<T> *__restrict__ prm, int do_kick,
+                const int *__restrict__ stop, int t)
 {
     const int b = blockIdx.y;                        // member: uniform per workgroup
     const EnsScalars<T> p = prm[b];
     const size_t o = (size_t)b * n;
+    if constexpr (STOPS) {
+        const int left = stop[b] - t;
+        if (left <= 1) {
+            ens_carry_positions<T, D, S, BS>(pos_in + o * D, pos_out + o * D, n);
+            if (left <= 0) return;
+            if (do_kick != NB_KICK_NONE) do_kick = NB_KICK_CLOSE;
+        }
+    }
     small_step_body<T, D, HOOK, S, BS>(blockIdx.x, pos_in + o * D, pos_out + o * D, vel + o * D, acc + o * D, mass + o, n,
                                        p.G, p.eps2, p.half_dt, p.dt, do_kick, nullptr);
 }
 
 // grid hook: member b reads the tables its own max-r2 launch built (tabs[b]); under INT8 / INT4 (part != null) it leaves
 // one {min, max} pair of its forces per workgroup at part[(b * gridDim.x + blockIdx.x) * 2]
-template <int D, int S, int BS>
+template <int D, int S, int BS, bool STOPS>
 __global__ void __launch_bounds__(BS)
 ens_grid_step_kernel(const float *__restrict__ pos_in, float *__restrict__ pos_out, float *__restrict__ vel,
                      float *__restrict__ acc, const float *__restrict__ mass, int n, const EnsScalars<float> *__restrict__ prm,
-                     int do_kick, const GridTables *__restrict__ tabs, double *__restrict__ part)
+                     int do_kick, const GridTables *__restrict__ tabs, double *__restrict__ part,
+                     const int *__restrict__ stop, int t)
 {
     const int b = blockIdx.y;
     const EnsScalars<float> p = prm[b];
     const size_t o = (size_t)b * n;
+    if constexpr (STOPS) {
+        const int left = stop[b] - t;
+        if (left <= 1) {
+            if (!part) ens_carry_positions<float, D, S, BS>(pos_in + o * D, pos_out + o * D, n);   // (INT8 / INT4: no ping-pong)
+            if (left <= 0) return;
+            if (do_kick != NB_KICK_NONE) do_kick = NB_KICK_CLOSE;
+        }
+    }
     small_grid_body<D, S, false, BS>(blockIdx.x, pos_in + o * D, pos_out + o * D, vel + o * D, acc + o * D, mass + o, n, p.G,
                                      p.eps2, p.half_dt, p.dt, do_kick, tabs + b,
                                      part ? part + (size_t)b * 2 * gridDim.x : nullptr, nullptr);
@@ -55,12 +93,14 @@ ens_grid_step_kernel(const float *__restrict__ pos_in, float *__restrict__ pos_o
 
 // opening kick + drift of a run (simulation.py:132,135) for every member with its own dt: v += a dt/2; x += v dt
 constexpr int EK_BLOCK = 256;
-template <typename T>
+template <typename T, bool STOPS>
 __global__ void __launch_bounds__(EK_BLOCK)
 ens_kick_drift_kernel(T *__restrict__ pos, T *__restrict__ vel, const T *__restrict__ acc, int count /* n * D */,
-                      const EnsScalars<T> *__restrict__ prm)
+                      const EnsScalars<T> *__restrict__ prm, const int *__restrict__ stop, int t)
 {
     const int b = blockIdx.y;
+    if constexpr (STOPS)
+        if (stop[b] - t <= 0) return;                // the member opens no further tick
     const T half_dt = prm[b].half_dt, dt = prm[b].dt;
     const size_t o = (size_t)b * count;
     for (int k = blockIdx.x * EK_BLOCK + threadIdx.x; k < count; k += gridDim.x * EK_BLOCK) {
@@ -72,14 +112,16 @@ ens_kick_drift_kernel(T *__restrict__ pos, T *__restrict__ vel, const T *__restr
 
 template <typename T, int D, int HOOK>
 hipError_t launch_e(const void *pos_in, void *pos_out, void *vel, void *acc, const void *mass, int members, int n, const void *prm,
-                    int do_kick, int lanes, hipStream_t st)
+                    int do_kick, int lanes, const int *stop, int t, hipStream_t st)
 {
     return nb::pick<64, 32, 16>(lanes, [&](auto S) {
         return nb::pick<512, 256>(nb_small_block(n), [&](auto BS) {
-            hipLaunchKernelGGL((ens_step_kernel<T, D, HOOK, S.value, BS.value>), dim3(nb_small_blocks(n, lanes), members),
-                               dim3(BS.value), 0, st, (const T *)pos_in, (T *)pos_out, (T *)vel, (T *)acc, (const T *)mass, n,
-                               (const EnsScalars<T> *)prm, do_kick);
-            return hipGetLastError();
+            return nb::pick_bool(stop != nullptr, [&](auto ST) {
+                hipLaunchKernelGGL((ens_step_kernel<T, D, HOOK, S.value, BS.value, ST.value>),
+                                   dim3(nb_small_blocks(n, lanes), members), dim3(BS.value), 0, st, (const T *)pos_in, (T *)pos_out,
+                                   (T *)vel, (T *)acc, (const T *)mass, n, (const EnsScalars<T> *)prm, do_kick, stop, t);
+                return hipGetLastError();
+            });
         });
     });
 }
@@ -87,51 +129,56 @@ hipError_t launch_e(const void *pos_in, void *pos_out, void *vel, void *acc, con
 }  // namespace
 
 hipError_t nb_launch_ens_step(const void *pos_in, void *pos_out, void *vel, void *acc, const void *mass, int members, int n,
-                              int dim, int is_f64, int hook, const void *prm, int do_kick, int lanes, hipStream_t st)
+                              int dim, int is_f64, int hook, const void *prm, int do_kick, int lanes, const int *stop, int t,
+                              hipStream_t st)
 {
-    if (members < 1 || members > NB_ENS_MAX_MEMBERS || n < 1) return hipErrorInvalidValue;
+    if (members < 1 || members > NB_ENS_MAX_MEMBERS || n < 1 || t < 0) return hipErrorInvalidValue;
     if ((do_kick & NB_KICK_MODE_MASK) == NB_KICK_CLOSE_SPEC || (do_kick & NB_KICK_OPEN_ON_READ)) return hipErrorInvalidValue;
     return nb::pick<2, 3>(dim, [&](auto D) {
         if (is_f64)
             return nb::pick<HOOK_NONE>(hook, [&](auto H) {
-                return launch_e<double, D.value, H.value>(pos_in, pos_out, vel, acc, mass, members, n, prm, do_kick, lanes, st);
+                return launch_e<double, D.value, H.value>(pos_in, pos_out, vel, acc, mass, members, n, prm, do_kick, lanes, stop, t, st);
             });
         return nb::pick<HOOK_NONE, HOOK_BF16, HOOK_F16>(hook, [&](auto H) {
-            return launch_e<float, D.value, H.value>(pos_in, pos_out, vel, acc, mass, members, n, prm, do_kick, lanes, st);
+            return launch_e<float, D.value, H.value>(pos_in, pos_out, vel, acc, mass, members, n, prm, do_kick, lanes, stop, t, st);
         });
     });
 }
 
 hipError_t nb_launch_ens_grid_step(const float *pos_in, float *pos_out, float *vel, float *acc, const float *mass, int members,
                                    int n, int dim, const void *prm, int do_kick, int lanes, const GridTables *tabs, double *part,
-                                   hipStream_t st)
+                                   const int *stop, int t, hipStream_t st)
 {
-    if (members < 1 || members > NB_ENS_MAX_MEMBERS || n < 1 || !tabs) return hipErrorInvalidValue;
+    if (members < 1 || members > NB_ENS_MAX_MEMBERS || n < 1 || !tabs || t < 0) return hipErrorInvalidValue;
     const int km = do_kick & NB_KICK_MODE_MASK;
     if (km == NB_KICK_CLOSE_SPEC || (do_kick & NB_KICK_OPEN_ON_READ)) return hipErrorInvalidValue;
     if (part && km != NB_KICK_NONE) return hipErrorInvalidValue;      // INT8 / INT4: the finish launch carries the kicks
     return nb::pick<2, 3>(dim, [&](auto D) {
         return nb::pick<64, 32, 16>(lanes, [&](auto S) {
             return nb::pick<512, 256>(nb_small_block(n), [&](auto BS) {
-                hipLaunchKernelGGL((ens_grid_step_kernel<D.value, S.value, BS.value>), dim3(nb_small_blocks(n, lanes), members),
-                                   dim3(BS.value), 0, st, pos_in, pos_out, vel, acc, mass, n, (const EnsScalars<float> *)prm,
-                                   do_kick, tabs, part);
-                return hipGetLastError();
+                return nb::pick_bool(stop != nullptr, [&](auto ST) {
+                    hipLaunchKernelGGL((ens_grid_step_kernel<D.value, S.value, BS.value, ST.value>),
+                                       dim3(nb_small_blocks(n, lanes), members), dim3(BS.value), 0, st, pos_in, pos_out, vel, acc,
+                                       mass, n, (const EnsScalars<float> *)prm, do_kick, tabs, part, stop, t);
+                    return hipGetLastError();
+                });
             });
         });
     });
 }
 
 hipError_t nb_launch_ens_kick_drift(void *pos, void *vel, const void *acc, int members, int n, int dim, int is_f64,
-                                    const void *prm, hipStream_t st)
+                                    const void *prm, const int *stop, int t, hipStream_t st)
 {
-    if (members < 1 || members > NB_ENS_MAX_MEMBERS || n < 1 || (dim != 2 && dim != 3)) return hipErrorInvalidValue;
+    if (members < 1 || members > NB_ENS_MAX_MEMBERS || n < 1 || (dim != 2 && dim != 3) || t < 0) return hipErrorInvalidValue;
     const int count = n * dim;
     const dim3 grid((count + EK_BLOCK - 1) / EK_BLOCK, members);
     return nb::pick_real(is_f64, [&](auto real) {
         using T = typename decltype(real)::type;
-        hipLaunchKernelGGL((ens_kick_drift_kernel<T>), grid, dim3(EK_BLOCK), 0, st, (T *)pos, (T *)vel, (const T *)acc, count,
-                           (const EnsScalars<T> *)prm);
-        return hipGetLastError();
+        return nb::pick_bool(stop != nullptr, [&](auto ST) {
+            hipLaunchKernelGGL((ens_kick_drift_kernel<T, ST.value>), grid, dim3(EK_BLOCK), 0, st, (T *)pos, (T *)vel,
+                               (const T *)acc, count, (const EnsScalars<T> *)prm, stop, t);
+            return hipGetLastError();
+        });
     });
 }

@@ -965,16 +965,21 @@ r2max_tables_kernel(const float *__restrict__ pos, ForceGeom g, float eps2, Grid
 // GridTables (maximum, arrival counter, tables), its own eps2 and G (prm: NB_ENS_PARAM_WORDS floats per member =
 // {G, eps2, dt / 2, dt}) and level count; the last workgroup OF A MEMBER to arrive builds that member's tables.  The maximum
 // is exact and the tables a function of it alone (grid_tables_body), so they are the tables a solo evaluation of the member
-// builds, however its workgroups were cut.  No workgroup waits for another.
-template <int D>
+// builds, however its workgroups were cut.  No workgroup waits for another.  All workgroups of a stopped member return
+// together (the test is on the member), so its arrival counter stays at rest.
+template <int D, bool STOPS>
 __global__ void __launch_bounds__(NB_BLOCK)
 ens_r2max_tables_kernel(const float *__restrict__ pos, ForceGeom g, const float *__restrict__ prm, GridTables *__restrict__ tabs,
-                        const int *__restrict__ levels, float min_val, int allow_fast)
+                        const int *__restrict__ levels, float min_val, int allow_fast, const int *__restrict__ stop, int t)
 {
     static_assert(NB_BLOCK == NB_LUT_MIN, "the last workgroup runs the single-block tables code");
     __shared__ unsigned int s_bits;
     __shared__ int s_mine;
     const int b = blockIdx.z;
+    // a stopped member (nb_ensemble.hip: stop[b] - t ticks left; STOPS = false: no array, the code without stops) takes no
+    // further evaluation: its tables stay its last one's
+    if constexpr (STOPS)
+        if (stop[b] - t <= 0) return;
     GridTables *tab = tabs + b;
     const float G = prm[b * NB_ENS_PARAM_WORDS], eps2 = prm[b * NB_ENS_PARAM_WORDS + 1];
     r2max_block<D, 1, NB_R2MAX_SPLIT>(pos + (size_t)b * g.n * D, g, eps2, tab);
@@ -1304,9 +1309,9 @@ hipError_t nb_launch_r2max_tables(const float *pos, const ForceGeom &g, int dim,
 }
 
 hipError_t nb_launch_ens_r2max_tables(const float *pos, int members, int n, int dim, const void *prm, GridTables *tabs,
-                                      const int *levels, float min_val, int allow_fast, hipStream_t st)
+                                      const int *levels, float min_val, int allow_fast, const int *stop, int t, hipStream_t st)
 {
-    if (members < 1 || members > NB_ENS_MAX_MEMBERS || n < 1 || !tabs || !levels || !prm) return hipErrorInvalidValue;
+    if (members < 1 || members > NB_ENS_MAX_MEMBERS || n < 1 || !tabs || !levels || !prm || t < 0) return hipErrorInvalidValue;
     const int per_block = NB_BLOCK / NB_R2MAX_SPLIT;
     const int gx = (n + per_block - 1) / per_block;
     // as nb_launch_r2max_tables: about one workgroup per CU, counted over ALL members, and at least one chunk per member
@@ -1319,9 +1324,11 @@ hipError_t nb_launch_ens_r2max_tables(const float *pos, int members, int n, int 
     g.n = n; g.j_begin = 0; g.j_end = n; g.chunk_len = chunk; g.nchunks = (n + chunk - 1) / chunk; g.r = 1;
     const dim3 grid(gx, g.nchunks, members);
     return nb::pick<2, 3>(dim, [&](auto D) {
-        hipLaunchKernelGGL((ens_r2max_tables_kernel<D.value>), grid, dim3(NB_BLOCK), 0, st, pos, g, (const float *)prm, tabs, levels,
-                           min_val, allow_fast);
-        return hipGetLastError();
+        return nb::pick_bool(stop != nullptr, [&](auto ST) {
+            hipLaunchKernelGGL((ens_r2max_tables_kernel<D.value, ST.value>), grid, dim3(NB_BLOCK), 0, st, pos, g, (const float *)prm,
+                               tabs, levels, min_val, allow_fast, stop, t);
+            return hipGetLastError();
+        });
     });
 }
 

@@ -314,13 +314,19 @@ hipError_t nb_launch_small_step(const void *pos_in, void *pos_out, void *vel, vo
 // NB_ENS_PARAM_WORDS elements of the storage type per member = {G, eps2, dt / 2, dt}, cast on the host exactly as
 // nb_launch_small_step casts the solo step's.  The body is the solo step's (nb_small_body.h), picked by
 // nb_small_block(n) and `lanes` as there; do_kick: NB_KICK_NONE / CLOSE / CLOSE_OPEN.
+// stop / t, on every launch of the tick path (nb_ens_run_members): stop is null (no member ever stops: the kernels'
+// instantiation without stops is launched) or device, one int
+// per member = the tick of the call at which the member stops; t = ticks the call has closed before this launch.  Member b
+// has stop[b] - t ticks left: none -> its workgroups return, one -> it only closes (NB_KICK_CLOSE) whatever do_kick says;
+// nb_ensemble.hip has the rule and what it does to the second position buffer.
 constexpr int NB_ENS_PARAM_WORDS = 4;
 constexpr int NB_ENS_MAX_MEMBERS = 1024;
 hipError_t nb_launch_ens_step(const void *pos_in, void *pos_out, void *vel, void *acc, const void *mass, int members, int n,
-                              int dim, int is_f64, int hook, const void *prm, int do_kick, int lanes, hipStream_t st);
+                              int dim, int is_f64, int hook, const void *prm, int do_kick, int lanes, const int *stop, int t,
+                              hipStream_t st);
 // opening kick + drift of every member with its own dt (two roundings per line, like nb_launch_kick_drift)
 hipError_t nb_launch_ens_kick_drift(void *pos, void *vel, const void *acc, int members, int n, int dim, int is_f64,
-                                    const void *prm, hipStream_t st);
+                                    const void *prm, const int *stop, int t, hipStream_t st);
 // The grid modes (INT8 / INT4 / CUSTOM, fp32 state), three launches per evaluation, each over all members:
 //   nb_launch_ens_r2max_tables        max r2 of every member and, by the member's last workgroup, its tables (tabs: `members`
 //                                     GridTables, zeroed once; levels: device, `members` ints in [2, NB_LUT_MIN])
@@ -331,12 +337,21 @@ hipError_t nb_launch_ens_kick_drift(void *pos, void *vel, const void *acc, int m
 //                                     count = n * dim forces to `levels` values and applies the kicks in place; `levels` is
 //                                     ONE value for all members (256 or 16: the force grid is the mode's, not CUSTOM's)
 hipError_t nb_launch_ens_r2max_tables(const float *pos, int members, int n, int dim, const void *prm, GridTables *tabs,
-                                      const int *levels, float min_val, int allow_fast, hipStream_t st);
+                                      const int *levels, float min_val, int allow_fast, const int *stop, int t, hipStream_t st);
 hipError_t nb_launch_ens_grid_step(const float *pos_in, float *pos_out, float *vel, float *acc, const float *mass, int members,
                                    int n, int dim, const void *prm, int do_kick, int lanes, const GridTables *tabs, double *part,
-                                   hipStream_t st);
+                                   const int *stop, int t, hipStream_t st);
 hipError_t nb_launch_ens_force_quant_finish(float *acc, int members, int count, int levels, const double *partials, int nblocks,
-                                            double *bounds, float *vel, float *pos, const void *prm, int kick, hipStream_t st);
+                                            double *bounds, float *vel, float *pos, const void *prm, int kick, const int *stop,
+                                            int t, hipStream_t st);
+// ---- explosion watch of an ensemble (nb_ens_watch.hip) ------------------------------------------------------------------
+// ONE launch on `st`, one workgroup per member, behind the energy launches of sampled tick `t` (sample `sample` of the
+// history kinetic / potential, index sample * members + b).  A member that is still running (stop[b] >= t, reason[b] == 0)
+// is tested with the reference's three criteria (stability_test.py:34-61) in their order: non-finite positions or
+// velocities (reason 1), |E - E0| / |E0| > 10 where |E0| > 1e-10 (2), E0 < 0 and E > |E0| (3), E0 = sample 0.  A member
+// that trips one gets stop[b] = t and reason[b] set: the launches behind this one leave it alone.
+hipError_t nb_launch_ens_watch(const void *pos, const void *vel, int members, int n, int dim, int is_f64, const double *kinetic,
+                               const double *potential, int64_t sample, int t, int *stop, int *reason, hipStream_t st);
 // ---- batched energies of an ensemble (nb_ens_energy.hip) -----------------------------------------------------------------
 // Two launches on `st`: per-tile-pair partial sums into part (members * nb_ens_energy_pairs(n) * 2 doubles, every slot
 // rewritten), then one wave per member that writes kinetic[sample * members + b] and potential[sample * members + b].

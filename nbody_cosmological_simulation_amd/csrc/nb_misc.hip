@@ -297,14 +297,22 @@ force_quant_finish_kernel(float *__restrict__ acc, int64_t count, int levels, co
 // ITS member's nblocks partials (partials: members * nblocks pairs), block 0 of a member leaves {min, max} in
 // bounds[2 b], and the member's count = n * D forces are snapped and kicked with the member's own dt
 // (prm: NB_ENS_PARAM_WORDS floats per member = {G, eps2, (float)(dt / 2), (float)dt}, the casts of the solo launch).
+template <bool STOPS>
 __global__ void __launch_bounds__(256)
 ens_force_quant_finish_kernel(float *__restrict__ acc, int count, int levels, const double *__restrict__ partials, int nblocks,
                               double *__restrict__ bounds, float *__restrict__ vel, float *__restrict__ pos,
-                              const float *__restrict__ prm, int kick)
+                              const float *__restrict__ prm, int kick, const int *__restrict__ stop, int t)
 {
     __shared__ double s_mn[4], s_mx[4];
     __shared__ double s_out[2];
     const int m = blockIdx.y;
+    // per-member stops (nb_ensemble.hip; STOPS = false: no array, the code without stops): a stopped member keeps its
+    // forces, bounds and state; one on its last tick only closes
+    if constexpr (STOPS) {
+        const int left = stop[m] - t;
+        if (left <= 0) return;
+        if (left == 1 && kick != NB_KICK_NONE) kick = NB_KICK_CLOSE;
+    }
     const double *mine = partials + (size_t)m * 2 * nblocks;
     double dmn = __builtin_inf(), dmx = -__builtin_inf();
     for (int w = threadIdx.x; w < nblocks; w += 256) {      // one pair per workgroup of the member's force launch
@@ -665,15 +673,18 @@ hipError_t nb_launch_force_quant_finish(float *acc, int64_t count, int levels, c
 }
 
 hipError_t nb_launch_ens_force_quant_finish(float *acc, int members, int count, int levels, const double *partials, int nblocks,
-                                            double *bounds, float *vel, float *pos, const void *prm, int kick, hipStream_t st)
+                                            double *bounds, float *vel, float *pos, const void *prm, int kick, const int *stop, int t,
+                                            hipStream_t st)
 {
-    if (members < 1 || members > NB_ENS_MAX_MEMBERS || count < 1 || nblocks < 1 || levels < 2) return hipErrorInvalidValue;
+    if (members < 1 || members > NB_ENS_MAX_MEMBERS || count < 1 || nblocks < 1 || levels < 2 || t < 0) return hipErrorInvalidValue;
     if (kick != NB_KICK_NONE && kick != NB_KICK_CLOSE && kick != NB_KICK_CLOSE_OPEN) return hipErrorInvalidValue;
     int gx = (count + 255) / 256;
     gx = gx > 2048 ? 2048 : gx;
-    hipLaunchKernelGGL(ens_force_quant_finish_kernel, dim3(gx, members), dim3(256), 0, st, acc, count, levels, partials, nblocks,
-                       bounds, vel, pos, (const float *)prm, kick);
-    return hipGetLastError();
+    return nb::pick_bool(stop != nullptr, [&](auto ST) {
+        hipLaunchKernelGGL(ens_force_quant_finish_kernel<ST.value>, dim3(gx, members), dim3(256), 0, st, acc, count, levels, partials,
+                           nblocks, bounds, vel, pos, (const float *)prm, kick, stop, t);
+        return hipGetLastError();
+    });
 }
 
 hipError_t nb_launch_grid_quantize_safe(const void *in, void *out, int is_f64, int64_t count, int levels,

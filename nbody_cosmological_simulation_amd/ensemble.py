@@ -44,7 +44,25 @@ and dispersion agree to 2e-6 relative, `galaxy_radius`, counts and edges exactly
 never influence each other; the trajectory, the tick and `launches()` are untouched.  Not part of it: metric samples
 inside `run_recorded`, float16 / bfloat16-typed evaluation (the state is fp32 or fp64), more than 255 bins, mixed dtypes.
 
-Not covered: more than 256 levels, mixed modes within one ensemble, per-member tick counts, mixed dtypes and the
+Per-member tick counts -- what the time-step sweeps (falsification_tests.py:321-356 and jitter_test.py:193-250 give every
+dt its own tick count so that the simulated time is equal) and the stability sweep (stability_test.py:33-61,94-105 stops a
+system at the first check that finds it "exploded") need -- are `run_members(num_ticks, every)` and
+`run_watched(max_ticks, check_interval)`, each ONE native call with no host round trip between ticks.  The members' stop
+ticks live in a device array that every kernel of the tick path reads: a member that has taken its ticks is left alone by
+every later launch.  Contract: member b takes exactly `num_ticks[b]` ticks, and its positions, velocities and
+accelerations are then bit-identical to the `GalaxySimulation` that took as many steps (a budget of 0: not touched);
+later calls of any kind go on from there as the solo run would; `launches()` and `tick` grow by the largest budget,
+`member_ticks[b]` by the member's own ticks.  Samples follow `run_recorded`'s rule, and a stopped member keeps being
+sampled at its frozen state.  `run_watched` applies the reference's three explosion criteria (`explosion_reason` is their
+definition) on the device at every check after the first sample, to every member that is still running; a member that trips
+one is halted at that tick, its state that of its solo run of `stable_ticks[b]` steps, and tick and reason are read back
+once, in a `StabilityReport`.  The decision uses the batched energies of `run_recorded` (at the bars above, not the solo
+engine's bits), exactly as `explosion_reason` applied to the returned history gives it.  With equal budgets `run_members`
+is `run_recorded`, launch for launch and bit for bit.  `QuantizedEnsemble` inherits all of it: a stopped member's tables,
+force bounds and `quant_debug()` stay those of its last evaluation, which is its solo run's last.
+
+Not covered: more than 256 levels, mixed modes within one ensemble, halting decisions other than the reference's three,
+compacting the launch grid as members finish (a finished member costs its workgroups one load each), mixed dtypes and the
 fp32 -> fp64 promotion timeline, subclass overrides, checkpoints, multi-GPU.
 """
 import ctypes as C
@@ -66,6 +84,8 @@ _MODES = (PrecisionMode.FLOAT64, PrecisionMode.FLOAT32, PrecisionMode.BFLOAT16, 
 _GRID_MODES = (PrecisionMode.INT8_SIM, PrecisionMode.INT4_SIM, PrecisionMode.CUSTOM)
 MIN_LEVELS, MAX_LEVELS = 2, 256       # MAX_LEVELS: above it the solo engine leaves the one-launch step (csrc/nb_step.cpp)
 DEFAULT_CUSTOM_LEVELS = 64            # the reference's default (quantization.py:67)
+# why run_watched halted a member (include/nbody_amd.h NB_ENS_REASON_*; `explosion_reason`)
+REASON_NONE, REASON_NONFINITE, REASON_ENERGY, REASON_UNBOUND = 0, 1, 2, 3
 
 
 def state_dtype(precision_mode) -> torch.dtype:
@@ -203,6 +223,53 @@ def check_record_arguments(num_ticks, every, members) -> list:
     return list(range(0, num_ticks + 1, every))
 
 
+def check_member_ticks_arguments(num_ticks, every, members):
+    """Validate run_members' arguments without touching a device.  `num_ticks`: an int (every member's budget) or a
+    sequence, tensor or numpy array of `members` ints, each >= 0; `every`: None (no samples) or an int >= 1.  Returns
+    (budgets, offsets): the length-`members` list of budgets and the tick offsets of the samples relative to the tick at
+    entry, [0, every, 2 * every, ...] up to the largest budget (None without samples); raises TypeError / ValueError."""
+    if isinstance(members, bool) or not isinstance(members, numbers.Integral):
+        raise TypeError(f"members must be an int, got {type(members).__name__}")
+    members = int(members)
+    if members < 1:
+        raise ValueError(f"members must be >= 1, got {members}")
+    if every is not None and (isinstance(every, bool) or not isinstance(every, numbers.Integral)):
+        raise TypeError(f"every must be None or an int, got {type(every).__name__}")
+    if isinstance(num_ticks, torch.Tensor) or type(num_ticks).__module__ == "numpy" and hasattr(num_ticks, "tolist"):
+        num_ticks = num_ticks.tolist()            # tensors and numpy arrays / scalars -> Python numbers (or lists of them)
+    elif isinstance(num_ticks, Sequence) and not isinstance(num_ticks, (str, bytes)):
+        num_ticks = list(num_ticks)
+    entries = num_ticks if isinstance(num_ticks, list) else [num_ticks]
+    for v in entries:
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise TypeError(f"num_ticks must be an int or a sequence of ints, got {type(v).__name__}")
+    if isinstance(num_ticks, list) and len(num_ticks) != members:
+        raise ValueError(f"num_ticks has {len(num_ticks)} entries for {members} members")
+    budgets = [int(v) for v in num_ticks] if isinstance(num_ticks, list) else [int(num_ticks)] * members
+    for v in budgets:
+        if v < 0:
+            raise ValueError(f"num_ticks must be >= 0, got {v}")
+        if v >= 2 ** 31:
+            raise ValueError(f"num_ticks must fit an int32, got {v}")
+    if every is None:
+        return budgets, None
+    return budgets, check_record_arguments(max(budgets), int(every), members)
+
+
+def explosion_reason(initial_energy, energy, finite) -> int:
+    """The reference's detect_explosion (stability_test.py:34-61) with the criterion that fired: the definition of what
+    run_watched decides on the device for one member at one check.  `finite`: all of the member's positions and
+    velocities are finite.  The comparisons are the reference's own, in its order, so a NaN energy trips nothing."""
+    initial_energy, energy = float(initial_energy), float(energy)
+    if not finite:
+        return REASON_NONFINITE
+    if abs(initial_energy) > 1e-10 and abs(energy - initial_energy) / abs(initial_energy) > 10.0:
+        return REASON_ENERGY
+    if initial_energy < 0 and energy > abs(initial_energy):
+        return REASON_UNBOUND
+    return REASON_NONE
+
+
 def check_metrics_arguments(num_bins, max_radius, percentile, members):
     """Validate metrics()' arguments without touching a device.  Returns (num_bins, max_radius, percentile) with
     max_radius None (every member's own maximum radius) or a list of `members` floats; raises TypeError / ValueError."""
@@ -270,6 +337,19 @@ class EnergyHistory(NamedTuple):
     @property
     def total(self) -> torch.Tensor:
         return self.kinetic + self.potential
+
+
+class StabilityReport(NamedTuple):
+    """What run_watched returns, (B,) numpy arrays: `stable_ticks` int64, the ticks the member took in the call before it
+    stopped (its budget, or the check that halted it); `exploded` bool; `reason` int64, REASON_NONE / REASON_NONFINITE /
+    REASON_ENERGY / REASON_UNBOUND; `initial_energy` and `final_energy` float64, sample 0 and the member's last sample
+    of `history`, the call's EnergyHistory (one sample per check)."""
+    stable_ticks: "np.ndarray"
+    exploded: "np.ndarray"
+    reason: "np.ndarray"
+    initial_energy: "np.ndarray"
+    final_energy: "np.ndarray"
+    history: EnergyHistory
 
 
 def _doubles(values):
@@ -383,7 +463,7 @@ class GalaxyEnsemble:
     def step(self):
         """One kick-drift-kick leapfrog tick of every member (reference simulation.py:120-143)."""
         N.check(N.lib().nb_ens_step(self._handle, 1))
-        self.tick += 1
+        self._advance(1)
 
     def run(self, num_ticks: int, callback: Callable = None, callback_interval: int = 100):
         """`num_ticks` ticks; `callback(self, self.tick)` every `callback_interval` (the contract of
@@ -392,7 +472,7 @@ class GalaxyEnsemble:
         while done < num_ticks:
             nxt = min(num_ticks, (done // callback_interval + 1) * callback_interval) if callback else num_ticks
             N.check(N.lib().nb_ens_step(self._handle, nxt - done))
-            self.tick += nxt - done
+            self._advance(nxt - done)
             done = nxt
             if callback and done % callback_interval == 0:
                 callback(self, self.tick)
@@ -411,8 +491,72 @@ class GalaxyEnsemble:
         if got.value != S:
             raise RuntimeError(f"nb_ens_run_recorded wrote {got.value} samples, expected {S}")
         ticks = [self.tick + o for o in offsets]
-        self.tick += int(num_ticks)
+        self._advance(int(num_ticks))
         return EnergyHistory(ticks, ke, pe)
+
+    def _advance(self, ticks, own=None):
+        """The clocks after a call: `tick` by `ticks`, every member's by the same or by its `own`."""
+        mine = self.__dict__.get("_member_ticks")          # absent until the first uneven call
+        if own is not None or mine is not None:
+            mine = mine if mine is not None else [self.tick] * self.num_members
+            own = [ticks] * self.num_members if own is None else own
+            self._member_ticks = [m + int(o) for m, o in zip(mine, own)]
+        self.tick += ticks
+
+    @property
+    def member_ticks(self) -> list:
+        """Ticks every member has taken since construction; all equal `tick` until the first uneven call."""
+        mine = self.__dict__.get("_member_ticks")
+        return list(mine) if mine is not None else [self.tick] * self.num_members
+
+    def _run_members(self, budgets, every, offsets, watch):
+        """The native call behind run_members / run_watched: (EnergyHistory or None, stop ticks, reasons)."""
+        import numpy as np
+        B = self.num_members
+        S = len(offsets) if offsets is not None else 0
+        ke = pe = None
+        if S:
+            ke = torch.empty((S, B), dtype=torch.float64, device=self.device)
+            pe = torch.empty((S, B), dtype=torch.float64, device=self.device)
+        got = C.c_int32()
+        stop, reason = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        N.check(N.lib().nb_ens_run_members(
+            self._handle, (C.c_int32 * B)(*budgets), int(every or 0), int(bool(watch)),
+            C.c_void_p(ke.data_ptr()) if S else None, C.c_void_p(pe.data_ptr()) if S else None, S,
+            int(self.device.type == "cuda"), C.byref(got), stop.ctypes.data_as(C.POINTER(C.c_int32)),
+            reason.ctypes.data_as(C.POINTER(C.c_int32))))
+        if got.value != S:
+            raise RuntimeError(f"nb_ens_run_members wrote {got.value} samples, expected {S}")
+        history = EnergyHistory([self.tick + o for o in offsets], ke, pe) if S else None
+        self._advance(max(budgets), own=stop)
+        return history, stop.astype(np.int64), reason.astype(np.int64)
+
+    def run_members(self, num_ticks, every=None):
+        """Member b takes `num_ticks[b]` ticks (an int: every member as many) in one native call and is then left alone,
+        bit-identical to its solo run of as many steps.  `every`: None, or record the energies like run_recorded -- at
+        entry and after every `every`-th tick up to the largest budget, a stopped member at its frozen state -- and
+        return the EnergyHistory.  `tick` advances by the largest budget, `member_ticks` by each member's own."""
+        budgets, offsets = check_member_ticks_arguments(num_ticks, every, self.num_members)
+        return self._run_members(budgets, every, offsets, watch=False)[0]
+
+    def run_watched(self, max_ticks, check_interval: int = 50) -> StabilityReport:
+        """The reference's stability loop (stability_test.py:94-105) for every member at once: batches of
+        `check_interval` ticks, ceil(max_ticks[b] / check_interval) of them for member b (`max_ticks`: an int or one
+        per member), and after every batch the explosion test of `explosion_reason` on the device.  A member that trips
+        it is halted there; nothing is read back before the end of the call."""
+        import numpy as np
+        if isinstance(check_interval, bool) or not isinstance(check_interval, numbers.Integral):
+            raise TypeError(f"check_interval must be an int, got {type(check_interval).__name__}")
+        check_interval = int(check_interval)
+        if check_interval < 1:
+            raise ValueError(f"check_interval must be >= 1, got {check_interval}")
+        budgets, _ = check_member_ticks_arguments(max_ticks, None, self.num_members)
+        budgets, offsets = check_member_ticks_arguments([-(-v // check_interval) * check_interval for v in budgets],
+                                                        check_interval, self.num_members)
+        history, stop, reason = self._run_members(budgets, check_interval, offsets, watch=True)
+        total = history.total.cpu().numpy()
+        last = total[stop // check_interval, np.arange(self.num_members)]
+        return StabilityReport(stop, reason != REASON_NONE, reason, total[0].copy(), last, history)
 
     # ------------------------------------------------------------------ reads
     def energies(self):
@@ -471,7 +615,7 @@ class GalaxyEnsemble:
             "positions": self.positions[b].clone(),
             "velocities": self.velocities[b].clone(),
             "masses": self.masses[b].clone(),
-            "tick": self.tick,
+            "tick": self.member_ticks[b],
             "precision_mode": self.precision_mode.value,
         }
 
