@@ -234,6 +234,38 @@ int nb_ens_run_recorded(nb_ens *e, int32_t nsteps, int32_t every, double *kineti
 int nb_ens_run_members(nb_ens *e, const int32_t *nsteps, int32_t every, int32_t watch, double *kinetic,
                        double *potential, int64_t capacity, int on_device, int32_t *samples, int32_t *stop_tick,
                        int32_t *reason);
+/* The reference's crash-point detector (crash_point_test.py:46-139) for every member, on the device.  Per member,
+ * in the state dtype: max_displacement, max_speed and max_radius are the correctly rounded square roots of the
+ * largest squared norm over stars of pos - prev_pos, vel and pos, a squared norm being (c0*c0 + c1*c1) + c2*c2 with
+ * separate multiplies and adds (c2 under dim 3 only); max_abs_velocity is the largest |component| of vel; the NaN
+ * and Inf flags cover positions and velocities.  The kinds, in the reference's order of precedence: a NaN; an Inf;
+ * max_displacement > max_abs_velocity * dt * 10 && max_displacement > 1.0; max_speed > 100.0; E_prev != 0 &&
+ * (fabs(E / E_prev) > 100 || < 0.01); max_radius > 1000 -- all in double, dt the member's as given. */
+#define NB_ENS_CRASH_NONE     0
+#define NB_ENS_CRASH_NAN      1
+#define NB_ENS_CRASH_INF      2
+#define NB_ENS_CRASH_TELEPORT 3
+#define NB_ENS_CRASH_VELOCITY 4
+#define NB_ENS_CRASH_ENERGY   5
+#define NB_ENS_CRASH_RADIUS   6
+/* The measures of the resident state in ONE launch.  flags: members int32 (bit 0 NaN, bit 1 Inf); measures:
+ * members * 4 doubles {max_displacement, max_abs_velocity, max_speed, max_radius}; host arrays, either may be NULL.
+ * prev_pos: NULL (displacement 0) or a (members, n, dim) block of the state dtype, host or device as flagged.
+ * The maxima of a member with a NaN or an Inf are not defined.  Needs positions and velocities.  Changes neither the
+ * state nor force_launches. */
+int nb_ens_crash_measures(nb_ens *e, const void *prev_pos, int on_device, int32_t *flags, double *measures);
+/* The loop of crash_point_test.py:186-215 for every member: nb_ens_run_members(nsteps, every = 1) with the
+ * detector in the explosion watch's place.  Budgets, history (1 + max(nsteps) samples), capacity, stop_tick,
+ * preconditions and error codes as there.  After every tick, behind the energy launches, each member that is still
+ * running is measured against its positions of the tick before (at entry: the resident ones) and tested with
+ * E = kinetic + potential of the tick's sample and E_prev of the sample before; a member that trips a criterion is
+ * halted at that tick, its state that of nb_ens_step(tick).  A member with a budget of 0 is never checked, and none
+ * is checked after its last tick's check.  kind: NB_ENS_CRASH_* per member; flags / measures: as
+ * nb_ens_crash_measures, each member's LAST check (0 for a member never checked); host arrays, any may be NULL,
+ * copied once at the end of the call.  force_launches grows by max(nsteps). */
+int nb_ens_run_crash_watched(nb_ens *e, const int32_t *nsteps, double *kinetic, double *potential,
+                             int64_t capacity, int on_device, int32_t *samples, int32_t *stop_tick,
+                             int32_t *kind, int32_t *flags, double *measures);
 /* The diagnostics of nb_metrics (rotation curve, r_percentile, bound fraction, dispersion) for every member, from
  * the resident state, in ONE kernel launch (one workgroup per member; no host round trip before the copy-out).
  * num_bins in [0, 255].  max_radius: `members` doubles, each >= 0 or NaN, the end of that member's bin edges; or

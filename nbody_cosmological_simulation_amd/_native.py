@@ -35,7 +35,7 @@ EXPORTS = [
     "nb_ens_create", "nb_ens_destroy", "nb_ens_set_params", "nb_ens_set_state", "nb_ens_get_state", "nb_ens_set_accelerations",
     "nb_ens_compute_accelerations", "nb_ens_step", "nb_ens_energy", "nb_ens_info", "nb_ens_synchronize",
     "nb_ens_energies", "nb_ens_run_recorded", "nb_ens_create_grid", "nb_ens_quant_info", "nb_ens_metrics",
-    "nb_ens_run_members",
+    "nb_ens_run_members", "nb_ens_crash_measures", "nb_ens_run_crash_watched",
 ]
 
 
@@ -139,6 +139,8 @@ def lib():
         "nb_ens_energies": ([vp, vp, vp, C.c_int], C.c_int),
         "nb_ens_run_recorded": ([vp, i32, i32, vp, vp, i64, C.c_int, pi32], C.c_int),
         "nb_ens_run_members": ([vp, pi32, i32, i32, vp, vp, i64, C.c_int, pi32, pi32, pi32], C.c_int),
+        "nb_ens_crash_measures": ([vp, vp, C.c_int, pi32, pdbl], C.c_int),
+        "nb_ens_run_crash_watched": ([vp, pi32, vp, vp, i64, C.c_int, pi32, pi32, pi32, pi32, pdbl], C.c_int),
         "nb_ens_metrics": ([vp, i32, pdbl, dbl, pdbl, C.POINTER(C.c_int64), C.POINTER(C.c_float), pdbl], C.c_int),
         "nb_ens_info": ([vp, pi32, C.POINTER(C.c_int64), C.POINTER(C.c_char_p)], C.c_int),
         "nb_ens_synchronize": ([vp], C.c_int),

@@ -20,7 +20,9 @@
 // nb_ens_step, nb_ens_run_recorded and nb_ens_run_members issue ONE launch train (run_train).  The last gives every member
 // a stop tick of its own in a device array that every kernel of the tick path reads (nb_ensemble.hip) and that the
 // explosion watch (nb_ens_watch.hip) lowers on the device; the first two pass no array: no member ever stops, and the
-// kernels launched are the instantiations without stops.
+// kernels launched are the instantiations without stops.  nb_ens_run_crash_watched is the same train with every tick
+// sampled and the crash-point detector (nb_ens_crash.hip) in the watch's place; nb_ens_crash_measures is that kernel alone
+// on the resident state.
 #include <algorithm>
 #include <cstddef>
 #include <cstring>
@@ -61,9 +63,17 @@ struct nb_ens {
     // nb_ens_run_members (created on first use): members stop ticks, then members halt reasons; what is uploaded / read back
     int32_t *stops = nullptr;
     std::vector<int32_t> stops_host;
+    // crash-point detector (created on first use): the positions of the previous tick; the members' dt as given; members * 4
+    // measures, then members flags; what is read back of the last
+    void *prev_pos = nullptr;
+    double *dt_dev = nullptr, *crash_out = nullptr;
+    std::vector<double> crash_host;
 };
 
 namespace {
+
+// what run_train launches behind the energy launches of a sampled tick
+enum WatchMode { WATCH_NONE, WATCH_EXPLOSION, WATCH_CRASH };
 
 inline size_t el(const nb_ens *e) { return e->is_f64 ? 8 : 4; }
 inline size_t cnt_nd(const nb_ens *e) { return (size_t)e->cfg.members * e->cfg.n * e->cfg.dim; }
@@ -141,7 +151,7 @@ void release(nb_ens *e)
     if (e->probe) (void)nb_destroy(e->probe);
     for (void *p : {e->prm, e->pos, e->pos_alt, e->vel, e->acc, e->mass, (void *)e->epart, (void *)e->ehist, (void *)e->tabs,
                     (void *)e->levels_dev, (void *)e->fpart, (void *)e->fbounds, e->mscratch, (void *)e->mout, (void *)e->mradius,
-                    (void *)e->medges, (void *)e->stops})
+                    (void *)e->medges, (void *)e->stops, e->prev_pos, (void *)e->dt_dev, (void *)e->crash_out})
         if (p) (void)hipFree(p);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
@@ -162,6 +172,35 @@ int energy_buffers(nb_ens *e, int64_t samples)
         e->ehist_cap = samples;
     }
     return NB_OK;
+}
+
+// the crash-point detector's buffers (fixed sizes: created once)
+int crash_buffers(nb_ens *e)
+{
+    const size_t B = (size_t)e->cfg.members;
+    if (!e->prev_pos) HIPCHK(hipMalloc(&e->prev_pos, cnt_nd(e) * el(e)));
+    if (!e->dt_dev) HIPCHK(hipMalloc((void **)&e->dt_dev, B * sizeof(double)));
+    if (!e->crash_out) HIPCHK(hipMalloc((void **)&e->crash_out, B * (4 * sizeof(double) + sizeof(int32_t))));
+    return NB_OK;
+}
+
+inline int *crash_flags(nb_ens *e) { return (int *)(e->crash_out + 4 * (size_t)e->cfg.members); }
+
+// flags and measures to the host copy (the caller waits, then hands them on with crash_results)
+int crash_out_async(nb_ens *e)
+{
+    const size_t B = (size_t)e->cfg.members;
+    e->crash_host.resize(4 * B + (B + 1) / 2);          // the int32 flags ride behind the doubles
+    HIPCHK(hipMemcpyAsync(e->crash_host.data(), e->crash_out, B * (4 * sizeof(double) + sizeof(int32_t)), hipMemcpyDeviceToHost,
+                          e->stream));
+    return NB_OK;
+}
+
+void crash_results(const nb_ens *e, int32_t *flags, double *measures)
+{
+    const size_t B = (size_t)e->cfg.members;
+    if (measures) memcpy(measures, e->crash_host.data(), 4 * B * sizeof(double));
+    if (flags) memcpy(flags, e->crash_host.data() + 4 * B, B * sizeof(int32_t));
 }
 
 // sample `s` of the history: the resident state's energies, two launches behind whatever the stream holds
@@ -188,10 +227,11 @@ int history_out(nb_ens *e, int64_t samples, double *kinetic, double *potential, 
 // elementwise launch opens the first tick (kick + drift), then one force launch per tick closes it and opens the next
 // (NB_KICK_CLOSE_OPEN: the drifted positions go to the second buffer); the last one only closes.  every >= 1: sample 0 is
 // taken at entry, and a sampled tick is issued as a one-tick nb_ens_step issues it -- the force launch only closes the tick
-// (velocities and positions are then what a reader sees), the two energy launches follow, under `watch` the explosion
-// watch, and a separate kick + drift launch opens the next tick.  stop: null, or the members' stop ticks on the device;
+// (velocities and positions are then what a reader sees), the two energy launches follow, then the watch of `watch`
+// (none, the explosion watch, or the crash-point detector, which needs every = 1 and crash_buffers), and a separate
+// kick + drift launch opens the next tick.  stop: null, or the members' stop ticks on the device;
 // every launch of the tick path gets it with the number of ticks closed so far.  Nothing waits on the stream.
-int run_train(nb_ens *e, int32_t nmax, int32_t every, int *stop, bool watch)
+int run_train(nb_ens *e, int32_t nmax, int32_t every, int *stop, WatchMode watch)
 {
     const nb_ens_config &c = e->cfg;
     auto open_tick = [&](int t) {
@@ -206,10 +246,14 @@ int run_train(nb_ens *e, int32_t nmax, int32_t every, int *stop, bool watch)
             if (int rc = launch_force(e, NB_KICK_CLOSE, stop, t - 1)) return rc;
             if (sampled) {
                 if (int rc = launch_energy(e, t / every, true)) return rc;
-                if (watch)
+                if (watch == WATCH_EXPLOSION)
                     HIPCHK(nb_launch_ens_watch(e->pos, e->vel, c.members, c.n, c.dim, e->is_f64, e->ehist,
                                                e->ehist + e->ehist_cap * c.members, t / every, t, stop, stop + c.members,
                                                e->stream));
+                else if (watch == WATCH_CRASH)
+                    HIPCHK(nb_launch_ens_crash(e->pos, e->prev_pos, e->vel, c.members, c.n, c.dim, e->is_f64, e->dt_dev, e->ehist,
+                                               e->ehist + e->ehist_cap * c.members, t / every, t, stop, stop + c.members,
+                                               crash_flags(e), e->crash_out, e->stream));
             }
             if (!last) HIPCHK(open_tick(t));
         } else {
@@ -428,7 +472,7 @@ int nb_ens_step(nb_ens *e, int32_t nsteps)
     if (int rc = check_steppable(e)) return rc;
     if (nsteps < 1) return NB_OK;
     DeviceGuard guard(e->cfg.device);
-    return run_train(e, nsteps, 0, nullptr, false);
+    return run_train(e, nsteps, 0, nullptr, WATCH_NONE);
 }
 
 int nb_ens_energy(nb_ens *e, double *kinetic, double *potential)
@@ -482,7 +526,7 @@ int nb_ens_run_recorded(nb_ens *e, int32_t nsteps, int32_t every, double *kineti
                     (long long)capacity, (long long)S, nsteps, every);
     DeviceGuard guard(e->cfg.device);
     if (int rc = energy_buffers(e, S)) return rc;
-    if (int rc = run_train(e, nsteps, every, nullptr, false)) return rc;
+    if (int rc = run_train(e, nsteps, every, nullptr, WATCH_NONE)) return rc;
     if (samples) *samples = (int32_t)S;
     return history_out(e, S, kinetic, potential, on_device);
 }
@@ -517,11 +561,74 @@ int nb_ens_run_members(nb_ens *e, const int32_t *nsteps, int32_t every, int32_t 
     e->stops_host.assign(2 * (size_t)B, NB_ENS_REASON_NONE);
     std::copy(nsteps, nsteps + B, e->stops_host.begin());
     HIPCHK(hipMemcpyAsync(e->stops, e->stops_host.data(), bytes, hipMemcpyHostToDevice, e->stream));
-    if (int rc = run_train(e, nmax, every, e->stops, watch != 0)) return rc;
+    if (int rc = run_train(e, nmax, every, e->stops, watch ? WATCH_EXPLOSION : WATCH_NONE)) return rc;
     HIPCHK(hipMemcpyAsync(e->stops_host.data(), e->stops, bytes, hipMemcpyDeviceToHost, e->stream));
     if (int rc = history_out(e, S, kinetic, potential, on_device)) return rc;      // (waits, with S = 0 too)
     if (stop_tick) std::copy(e->stops_host.begin(), e->stops_host.begin() + B, stop_tick);
     if (reason) std::copy(e->stops_host.begin() + B, e->stops_host.end(), reason);
+    if (samples) *samples = (int32_t)S;
+    return NB_OK;
+}
+
+// the detector's kernel alone on the resident state: one launch, one copy-out, one wait
+int nb_ens_crash_measures(nb_ens *e, const void *prev_pos, int on_device, int32_t *flags, double *measures)
+{
+    if (!e) return fail(NB_ERR_INVALID, "null handle");
+    if (!e->have_pos || !e->have_vel) return fail(NB_ERR_INVALID, "state incomplete");
+    DeviceGuard guard(e->cfg.device);
+    const nb_ens_config &c = e->cfg;
+    if (int rc = crash_buffers(e)) return rc;
+    const void *prev = prev_pos;
+    if (prev_pos && !on_device) {          // (the wait below: the upload has consumed prev_pos)
+        if (int rc = copy_in(e, e->prev_pos, prev_pos, cnt_nd(e), 0)) return rc;
+        prev = e->prev_pos;
+    }
+    HIPCHK(nb_launch_ens_crash(e->pos, const_cast<void *>(prev), e->vel, c.members, c.n, c.dim, e->is_f64, nullptr, nullptr,
+                               nullptr, 0, 0, nullptr, nullptr, crash_flags(e), e->crash_out, e->stream));
+    if (int rc = crash_out_async(e)) return rc;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    crash_results(e, flags, measures);
+    return NB_OK;
+}
+
+// nb_ens_run_members with every tick sampled and the crash-point detector as the watch: the previous positions primed and
+// the members' dt uploaded in front of the launches; stop ticks, kinds, flags and measures read back behind them; one wait
+int nb_ens_run_crash_watched(nb_ens *e, const int32_t *nsteps, double *kinetic, double *potential, int64_t capacity,
+                             int on_device, int32_t *samples, int32_t *stop_tick, int32_t *kind, int32_t *flags, double *measures)
+{
+    if (samples) *samples = 0;
+    if (int rc = check_steppable(e)) return rc;
+    if (!nsteps) return fail(NB_ERR_INVALID, "null nsteps");
+    const int B = e->cfg.members;
+    int32_t nmax = 0;
+    for (int b = 0; b < B; ++b) {
+        if (nsteps[b] < 0) return fail(NB_ERR_INVALID, "nsteps[%d] must be >= 0 (got %d)", b, nsteps[b]);
+        nmax = std::max(nmax, nsteps[b]);
+    }
+    const int64_t S = 1 + (int64_t)nmax;
+    if (capacity < S)
+        return fail(NB_ERR_INVALID, "capacity of %lld samples is below the %lld of %d ticks sampled every tick",
+                    (long long)capacity, (long long)S, nmax);
+    DeviceGuard guard(e->cfg.device);
+    if (int rc = energy_buffers(e, S)) return rc;
+    if (int rc = crash_buffers(e)) return rc;
+    const size_t bytes = 2 * (size_t)B * sizeof(int32_t);
+    if (!e->stops) HIPCHK(hipMalloc((void **)&e->stops, bytes));
+    // stops_host is free to rewrite: every call that uploads it waits before it returns (e->dt: nb_ens_set_params waits too)
+    e->stops_host.assign(2 * (size_t)B, NB_ENS_CRASH_NONE);
+    std::copy(nsteps, nsteps + B, e->stops_host.begin());
+    HIPCHK(hipMemcpyAsync(e->stops, e->stops_host.data(), bytes, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->dt_dev, e->dt.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    // a member that is never checked (a budget of 0) reports no flags and measures of 0
+    HIPCHK(hipMemsetAsync(e->crash_out, 0, (size_t)B * (4 * sizeof(double) + sizeof(int32_t)), e->stream));
+    HIPCHK(hipMemcpyAsync(e->prev_pos, e->pos, cnt_nd(e) * el(e), hipMemcpyDeviceToDevice, e->stream));
+    if (int rc = run_train(e, nmax, 1, e->stops, WATCH_CRASH)) return rc;
+    HIPCHK(hipMemcpyAsync(e->stops_host.data(), e->stops, bytes, hipMemcpyDeviceToHost, e->stream));
+    if (int rc = crash_out_async(e)) return rc;
+    if (int rc = history_out(e, S, kinetic, potential, on_device)) return rc;      // (waits)
+    if (stop_tick) std::copy(e->stops_host.begin(), e->stops_host.begin() + B, stop_tick);
+    if (kind) std::copy(e->stops_host.begin() + B, e->stops_host.end(), kind);
+    crash_results(e, flags, measures);
     if (samples) *samples = (int32_t)S;
     return NB_OK;
 }

@@ -352,6 +352,17 @@ hipError_t nb_launch_ens_force_quant_finish(float *acc, int members, int count, 
 // that trips one gets stop[b] = t and reason[b] set: the launches behind this one leave it alone.
 hipError_t nb_launch_ens_watch(const void *pos, const void *vel, int members, int n, int dim, int is_f64, const double *kinetic,
                                const double *potential, int64_t sample, int t, int *stop, int *reason, hipStream_t st);
+// ---- crash-point detector of an ensemble (nb_ens_crash.hip) -------------------------------------------------------------
+// ONE launch on `st`, one workgroup per member: flags[b] (bit 0: a NaN, bit 1: an Inf in positions or velocities) and
+// measures[4 b ..] = {max |pos - prev|, max |v_k|, max |vel|, max |pos|} in the state dtype, widened to double (device
+// arrays).  stop == null: measure only; prev may be null (displacement 0) and is not written.  stop given: behind the
+// energy launches of tick `t` (sample `sample` >= 1 of the history); a member that is still running (stop[b] >= t,
+// kind[b] == 0) is measured against prev, leaves its positions in prev, and is tested with the reference's six criteria
+// (crash_point_test.py:46-139) in their order with dt[b], E of this sample and of the one before.  A member that trips one
+// gets stop[b] = t and kind[b] set (NB_ENS_CRASH_*); a skipped member's flags and measures are not written.
+hipError_t nb_launch_ens_crash(const void *pos, void *prev, const void *vel, int members, int n, int dim, int is_f64,
+                               const double *dt, const double *kinetic, const double *potential, int64_t sample, int t, int *stop,
+                               int *kind, int *flags, double *measures, hipStream_t st);
 // ---- batched energies of an ensemble (nb_ens_energy.hip) -----------------------------------------------------------------
 // Two launches on `st`: per-tile-pair partial sums into part (members * nb_ens_energy_pairs(n) * 2 doubles, every slot
 // rewritten), then one wave per member that writes kinetic[sample * members + b] and potential[sample * members + b].

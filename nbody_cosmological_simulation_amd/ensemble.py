@@ -61,7 +61,26 @@ engine's bits), exactly as `explosion_reason` applied to the returned history gi
 is `run_recorded`, launch for launch and bit for bit.  `QuantizedEnsemble` inherits all of it: a stopped member's tables,
 force bounds and `quant_debug()` stay those of its last evaluation, which is its solo run's last.
 
-Not covered: more than 256 levels, mixed modes within one ensemble, halting decisions other than the reference's three,
+Crash points -- the reference's crash_point_test.py:142-466 sweeps velocity multipliers, time steps, grid levels and
+softening lengths, steps every system tick by tick and asks detect_crash (:46-139) after each tick whether it has "crashed":
+eight whole-array reductions and six criteria, two of them about the motion since the tick before -- are
+`run_crash_watched(max_ticks)`, ONE native call: every tick is sampled, and behind its energy launches one more launch
+(csrc/nb_ens_crash.hip, one workgroup per member) measures every running member against its positions of the tick before
+and applies the criteria on the device, in the reference's order, halting the member at that tick.  `crash_kind` is the
+definition of the decision and `crash_value` / `crash_severity` give the reference's report fields; the result is a
+`CrashPointReport`.  `crash_measures(prev_positions)` is the same kernel on the resident state alone and returns the
+`CrashMeasures`.  Contract of the measures: in the state dtype, a star's squared norm is (c0*c0 + c1*c1) + c2*c2 with
+separate multiplies and adds (torch's order for a last dimension of 2 or 3); `max_displacement`, `max_speed` and
+`max_radius` are the correctly rounded roots of the largest squared norm of pos - prev, vel and pos; `max_abs_velocity` is
+the largest |component|; the NaN / Inf flags cover positions and velocities; the maxima of a member that has either flag
+are not defined (the reference returns before it computes them).  The decision uses the batched energies of `run_recorded`
+(E of the tick's sample against the sample before), exactly as `crash_kind` applied to the returned history and measures
+gives it.  A halted member's state is that of its solo run of `ticks_taken[b]` steps, bit for bit, `stable_ticks[b]` is the
+reference's 0-based index of the tick whose check fired, and later calls go on from there; `tick`, `member_ticks` and
+`launches()` move as under `run_members`, and a halted QuantizedEnsemble member keeps the tables of its last evaluation.
+
+Not covered: more than 256 levels, mixed modes within one ensemble, a crash check interval other than 1, crash thresholds
+other than the reference's constants,
 compacting the launch grid as members finish (a finished member costs its workgroups one load each), mixed dtypes and the
 fp32 -> fp64 promotion timeline, subclass overrides, checkpoints, multi-GPU.
 """
@@ -86,6 +105,11 @@ MIN_LEVELS, MAX_LEVELS = 2, 256       # MAX_LEVELS: above it the solo engine lea
 DEFAULT_CUSTOM_LEVELS = 64            # the reference's default (quantization.py:67)
 # why run_watched halted a member (include/nbody_amd.h NB_ENS_REASON_*; `explosion_reason`)
 REASON_NONE, REASON_NONFINITE, REASON_ENERGY, REASON_UNBOUND = 0, 1, 2, 3
+# why run_crash_watched halted a member, in the reference's order of precedence (include/nbody_amd.h NB_ENS_CRASH_*;
+# `crash_kind`), and the reference's crash_type strings (crash_point_test.py:61-137)
+CRASH_NONE, CRASH_NAN, CRASH_INF, CRASH_TELEPORT, CRASH_VELOCITY, CRASH_ENERGY, CRASH_RADIUS = range(7)
+CRASH_TYPES = ("", "NaN_EXPLOSION", "INFINITY_OVERFLOW", "TELEPORTATION", "VELOCITY_OVERFLOW", "ENERGY_SINGULARITY",
+               "GALAXY_EXPLOSION")
 
 
 def state_dtype(precision_mode) -> torch.dtype:
@@ -270,6 +294,60 @@ def explosion_reason(initial_energy, energy, finite) -> int:
     return REASON_NONE
 
 
+def crash_kind(has_nan, has_inf, max_displacement, max_abs_velocity, max_speed, max_radius, energy, prev_energy, dt) -> int:
+    """The reference's detect_crash (crash_point_test.py:46-139) with the criterion that fired: the definition of what
+    run_crash_watched decides on the device for one member at one check, from the member's measures (`CrashMeasures`),
+    its total energy at this check and at the one before, and its dt as given.  The comparisons are the reference's own,
+    in its order and in Python floats, so a NaN energy ratio trips nothing and a zero `prev_energy` of either sign skips
+    the energy test."""
+    max_displacement, max_abs_velocity, max_speed, max_radius = (
+        float(max_displacement), float(max_abs_velocity), float(max_speed), float(max_radius))
+    energy, prev_energy, dt = float(energy), float(prev_energy), float(dt)
+    if has_nan:
+        return CRASH_NAN
+    if has_inf:
+        return CRASH_INF
+    if max_displacement > max_abs_velocity * dt * 10 and max_displacement > 1.0:
+        return CRASH_TELEPORT
+    if max_speed > 100.0:
+        return CRASH_VELOCITY
+    if prev_energy != 0:
+        energy_ratio = abs(energy / prev_energy)
+        if energy_ratio > 100 or energy_ratio < 0.01:
+            return CRASH_ENERGY
+    if max_radius > 1000:
+        return CRASH_RADIUS
+    return CRASH_NONE
+
+
+def crash_value(kind, max_displacement, max_speed, max_radius, energy) -> float:
+    """The reference's CrashReport.value as detect_crash sets it for the criterion `kind` (NaN for CRASH_NONE)."""
+    kind = int(kind)
+    if kind in (CRASH_NAN, CRASH_INF):
+        return 0.0
+    if kind == CRASH_NONE:
+        return float("nan")
+    return float({CRASH_TELEPORT: max_displacement, CRASH_VELOCITY: max_speed, CRASH_ENERGY: energy,
+                  CRASH_RADIUS: max_radius}[kind])
+
+
+def crash_severity(kind, max_displacement, max_speed, max_radius, energy, prev_energy) -> float:
+    """The reference's CrashReport.severity for the criterion `kind` (0 for CRASH_NONE)."""
+    import numpy as np
+    kind = int(kind)
+    if kind == CRASH_NONE:
+        return 0.0
+    if kind in (CRASH_NAN, CRASH_INF):
+        return 1.0
+    if kind == CRASH_ENERGY:
+        ratio = abs(float(energy) / float(prev_energy))
+        if ratio == 0 or ratio == float("inf"):         # |log10| is inf
+            return 1.0
+        return min(1.0, float(abs(np.log10(ratio))) / 5)      # numpy's log10, as the reference takes it
+    value = crash_value(kind, max_displacement, max_speed, max_radius, energy)
+    return min(1.0, value / {CRASH_TELEPORT: 100, CRASH_VELOCITY: 1000, CRASH_RADIUS: 10000}[kind])
+
+
 def check_metrics_arguments(num_bins, max_radius, percentile, members):
     """Validate metrics()' arguments without touching a device.  Returns (num_bins, max_radius, percentile) with
     max_radius None (every member's own maximum radius) or a list of `members` floats; raises TypeError / ValueError."""
@@ -350,6 +428,42 @@ class StabilityReport(NamedTuple):
     initial_energy: "np.ndarray"
     final_energy: "np.ndarray"
     history: EnergyHistory
+
+
+class CrashMeasures(NamedTuple):
+    """What crash_measures returns, (B,) numpy arrays: `has_nan`, `has_inf` bool (positions and velocities); the four
+    measures of detect_crash, float64 widened exactly from the state dtype: `max_displacement`, `max_abs_velocity`,
+    `max_speed`, `max_radius` (not defined for a member with either flag)."""
+    has_nan: "np.ndarray"
+    has_inf: "np.ndarray"
+    max_displacement: "np.ndarray"
+    max_abs_velocity: "np.ndarray"
+    max_speed: "np.ndarray"
+    max_radius: "np.ndarray"
+
+
+class CrashPointReport(NamedTuple):
+    """What run_crash_watched returns, (B,) numpy arrays: `ticks_taken` int64, the ticks the member took in the call;
+    `stable_ticks` int64, the reference's results[...]["stable_ticks"] (the budget without a crash, else the 0-based index
+    of the tick whose check fired, ticks_taken - 1); `crashed` bool; `kind` int64, CRASH_NONE .. CRASH_RADIUS; `crash_type`,
+    a list of the reference's strings ("" for none); `value` and `severity` float64, the reference's report fields (NaN and
+    0 for none); `measures`, the CrashMeasures of every member's last check (zeros for a member never checked); `history`,
+    the call's EnergyHistory (one sample per tick)."""
+    ticks_taken: "np.ndarray"
+    stable_ticks: "np.ndarray"
+    crashed: "np.ndarray"
+    kind: "np.ndarray"
+    crash_type: list
+    value: "np.ndarray"
+    severity: "np.ndarray"
+    measures: CrashMeasures
+    history: EnergyHistory
+
+
+def _crash_measures(flags, meas) -> CrashMeasures:
+    """The native flags (B,) int32 and measures (B, 4) float64 as a CrashMeasures."""
+    return CrashMeasures((flags & 1) != 0, (flags & 2) != 0, meas[:, 0].copy(), meas[:, 1].copy(), meas[:, 2].copy(),
+                         meas[:, 3].copy())
 
 
 def _doubles(values):
@@ -558,7 +672,62 @@ class GalaxyEnsemble:
         last = total[stop // check_interval, np.arange(self.num_members)]
         return StabilityReport(stop, reason != REASON_NONE, reason, total[0].copy(), last, history)
 
+    def run_crash_watched(self, max_ticks) -> CrashPointReport:
+        """The reference's crash-point loop (crash_point_test.py:186-215) for every member at once: up to `max_ticks[b]`
+        ticks (`max_ticks`: an int or one per member), and after every tick detect_crash's test (`crash_kind`) on the
+        device, against the member's positions and energy of the tick before.  A member that trips it is halted there;
+        nothing is read back before the end of the call."""
+        import numpy as np
+        budgets, offsets = check_member_ticks_arguments(max_ticks, 1, self.num_members)
+        B, S = self.num_members, len(offsets)
+        on_device = int(self.device.type == "cuda")
+        ke = torch.empty((S, B), dtype=torch.float64, device=self.device)
+        pe = torch.empty((S, B), dtype=torch.float64, device=self.device)
+        got = C.c_int32()
+        stop, kind, flags = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
+        meas = np.zeros((B, 4), np.float64)
+        pi32 = C.POINTER(C.c_int32)
+        N.check(N.lib().nb_ens_run_crash_watched(
+            self._handle, (C.c_int32 * B)(*budgets), C.c_void_p(ke.data_ptr()), C.c_void_p(pe.data_ptr()), S, on_device,
+            C.byref(got), stop.ctypes.data_as(pi32), kind.ctypes.data_as(pi32), flags.ctypes.data_as(pi32),
+            meas.ctypes.data_as(C.POINTER(C.c_double))))
+        if got.value != S:
+            raise RuntimeError(f"nb_ens_run_crash_watched wrote {got.value} samples, expected {S}")
+        history = EnergyHistory([self.tick + o for o in offsets], ke, pe)
+        return self._crash_report(budgets, stop, kind, flags, meas, history)
+
+    def _crash_report(self, budgets, stop, kind, flags, meas, history) -> CrashPointReport:
+        """The clocks and the report behind run_crash_watched's native call: value and severity are the reference's,
+        from the measures of the member's last check and the history's samples at and before its last tick."""
+        import numpy as np
+        B = self.num_members
+        stop, kind = np.asarray(stop).astype(np.int64), np.asarray(kind).astype(np.int64)
+        self._advance(max(budgets), own=stop)
+        measures = _crash_measures(np.asarray(flags), np.asarray(meas))
+        total = history.total.cpu().numpy()
+        crashed = kind != CRASH_NONE
+        value, severity = np.full(B, np.nan), np.zeros(B)
+        for b in np.nonzero(crashed)[0]:
+            args = (int(kind[b]), measures.max_displacement[b], measures.max_speed[b], measures.max_radius[b],
+                    total[stop[b], b])
+            value[b] = crash_value(*args)
+            severity[b] = crash_severity(*args, total[stop[b] - 1, b])
+        return CrashPointReport(stop, np.where(crashed, stop - 1, np.asarray(budgets, np.int64)), crashed, kind,
+                                [CRASH_TYPES[k] for k in kind], value, severity, measures, history)
+
     # ------------------------------------------------------------------ reads
+    def crash_measures(self, prev_positions=None) -> CrashMeasures:
+        """detect_crash's measures (crash_point_test.py:60-127) of every member from the resident state: one launch, one
+        copy-out.  `prev_positions`: None (displacement 0) or a (B, N, D) tensor of the state dtype on either device."""
+        import numpy as np
+        held, ptr, on_device = (None, None, False) if prev_positions is None else self._pointer("prev_positions", prev_positions)
+        B = self.num_members
+        flags, meas = np.zeros(B, np.int32), np.zeros((B, 4), np.float64)
+        N.check(N.lib().nb_ens_crash_measures(self._handle, ptr, int(on_device), flags.ctypes.data_as(C.POINTER(C.c_int32)),
+                                              meas.ctypes.data_as(C.POINTER(C.c_double))))
+        del held
+        return _crash_measures(flags, meas)
+
     def energies(self):
         """(kinetic, potential): float64 tensors of shape (B,) on `self.device`, all members evaluated in one batched
         pass.  Equal to get_kinetic_energy() / get_potential_energy() to the project's bars, not bit for bit."""
