@@ -14,6 +14,8 @@
 //   one particle-set per lane too, together with ITS accumulators; after each of 64 steps the J
 //   data and the J accumulators rotate by one lane (ds_bpermute_b32: the LDS crossbar, no VALU
 //   cycles), so every lane meets every J particle once and the accumulators return home.
+//   (fp64, 2-D, R = 4: by default the LDS hand-off of nb_force_sym_kernel.h -- a position ring staged once per
+//   workgroup and wave-private accumulator mailboxes -- replaces the rotation; NB_SYM_ROT=0 keeps it.)
 //   J == I (diagonal tile) is evaluated one-sided, so each ordered pair is counted once.
 //   A workgroup = four waves = four consecutive target tiles (a "super-row") walking the SAME
 //   source tiles in step; after each source tile the four waves' column sums are added through
@@ -393,9 +395,14 @@ hipError_t nb_launch_pack(void *pos, void *vel, const void *acc, const void *mas
 
 hipError_t nb_launch_force_sym_f64(const double *packed, const SymWork *work, int nwork, double *rowslab,
                                    double *colslab, int np, int dim, int r, int uniform, int pa_f32, double eps2,
-                                   hipStream_t st, NbKernelEvents ev, int rowsplit)
+                                   hipStream_t st, NbKernelEvents ev, int rowsplit, int ldsrot)
 {
-    if (rowsplit) {         // row-split work items (nb_plan.cpp): their own instantiations
+    // LDS hand-off in place of the lane rotation (NB_SYM_ROT): the shapes it is instantiated for, others keep the rotation
+    if (ldsrot && dim == 2 && r == 4 && !pa_f32)
+        return nb::pick_bool(rowsplit, [&](auto RS) {
+            return launch_sym_ldsrot<RS.value>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, st, ev);
+        });
+    if (rowsplit) {      // row-split work items (nb_plan.cpp): their own instantiations
         if (dim != 2 || r != 4) return hipErrorInvalidValue;
         if (pa_f32) return launch_sym_rowsplit<HOOK_F32PAIR>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, (float)eps2, st, ev);
         return launch_sym_rowsplit<HOOK_NONE>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, 1.0f, st, ev);

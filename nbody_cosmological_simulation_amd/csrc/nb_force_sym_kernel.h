@@ -5,6 +5,7 @@
 // makes it -- table-free estimate, wave ballot, threshold fallback -- as per-particle integer checksums).
 #pragma once
 #include "nb_device.h"
+#include "nb_dispatch.h"
 #ifdef NB_GRID_R2_EXACT
 #define NB_GRID_R2_EXACT_V 1
 #else
@@ -136,6 +137,30 @@ template <int R, int RJ> struct BinDbg<R, RJ, true> {
     }
 };
 
+// ---- LDS hand-off (LDSROT = true instantiations: fp64, D = 2, R = 4, no hook) -------------------------------------
+// The register rotation costs 32 ds_bpermute_b32 per step of 16 pairs (two per fp64 value: four positions and four
+// accumulator halves per source slot), each with its own address and data VGPR reads and its own LDS queue entry.  The
+// hand-off moves the same values with 12 wide LDS instructions per step:
+//   positions    all four waves of a workgroup sweep the same source tile, so the workgroup stages it once in LDS
+//                (`ring`: per slot 128 entries {x, y}, the 64 particles repeated, so that lane l reads entry
+//                l + s_begin + s at step s with no wrap: one v_add_u32 per step, one ds_read_b128 per slot); the mass
+//                factors of the general-mass kernels ride in a second ring (ds_read_b64)
+//   accumulators still travel one lane per step, as 16-byte records through a wave-private mailbox: ds_write_b128 of
+//                {aj_x, aj_y} to mail[rj][lane], ds_read_b128 of mail[rj][(lane + 1) & 63].  A wave's LDS instructions
+//                complete in order, so one buffer per slot is enough and no barrier is involved; a wavefront-scope
+//                release / acquire fence pair keeps the compiler from moving the read above the write.
+// Same values, same arithmetic, same order: results are bit for bit those of the rotation.
+// LDS pipe: per wave and step 8 ds_read_b128 (4 cycles each) + 4 ds_write_b128 (13 cycles each: the store's VGPR
+// transfer) = 84 cycles; 16 waves per CU make that 1344 of the ~4900 CU cycles a step of 16 pairs takes (27 %), or
+// 12 KiB x 16 = 192 KiB per 4900 cycles = 40 B/clk against the array's 256 B/clk per CU.
+typedef double d2 __attribute__((ext_vector_type(2)));
+struct LdsRot {
+    const d2 *ring;         // this lane's entry of source slot 0 at the sweep's first step (slot rj: + 128 rj, step s: + s)
+    const double *ring_g;   // ... of the mass-factor ring (general masses only)
+    d2 *mail_w;             // mail[0][lane]             (slot rj: + 64 rj)
+    const d2 *mail_r;       // mail[0][(lane + 1) & 63]
+};
+
 // One sweep of a target tile (R particles per lane) against RJ source slots: `nsteps` rotation steps (64 = all
 // lanes), R*RJ pairs per lane per step, J data rotating by one lane per step.  RJ = R covers the whole
 // source tile; D = 3 sweeps it in two halves (RJ = 2) to stay inside 128 VGPRs with R = 4 targets.
@@ -143,11 +168,15 @@ template <int R, int RJ> struct BinDbg<R, RJ, true> {
 // UNIFORM: all masses equal -> the mass factor is applied once to the finished sums
 //          (reduce_sym_kernel), saving both mass multiplies and the rotation of the masses.
 // HOOK:    precision hook applied to the fp32 r2 (HOOK_NONE for fp64); EST: grid bins by estimate.
-template <typename T, int D, int R, int RJ, bool DIAG, bool UNIFORM, int HOOK, int EST, bool BINS = false>
+// LDSROT:  the source data come from the LDS ring and the accumulators travel through the mailbox `lr` (see LdsRot)
+//          instead of rotating through ds_bpermute_b32; xj / gj hold the current step's values either way.
+template <typename T, int D, int R, int RJ, bool DIAG, bool UNIFORM, int HOOK, int EST, bool BINS = false, bool LDSROT = false>
 __device__ __forceinline__ void sweep(const T (&xi)[R][D], const T (&gi)[R], T (&ai)[R][D], T (&xj)[RJ][D],
                                       T (&gj)[RJ], T (&aj)[RJ][D], T eps2, int rot_addr, const GridArgs &ga,
-                                      int nsteps, BinDbg<R, RJ, BINS> &bd)
+                                      int nsteps, BinDbg<R, RJ, BINS> &bd, const LdsRot lr = LdsRot{})
 {
+    static_assert(!LDSROT || (std::is_same_v<T, double> && D == 2 && R == 4 && RJ == 4 && HOOK == HOOK_NONE && !BINS),
+                  "LDS hand-off: fp64, 2-D, four targets per lane, no hook, no bin read-out");
     T c15 = (T)1.5, c1875 = (T)1.875;
     if constexpr (std::is_same_v<T, double>) asm volatile("" : "+v"(c15), "+s"(c1875));
 #pragma unroll 1
@@ -257,13 +286,30 @@ __device__ __forceinline__ void sweep(const T (&xi)[R][D], const T (&gi)[R], T (
                     }
                 }
             }
+            if constexpr (LDSROT) {
+                // next step's source of this slot: one entry further along the ring
+                const d2 nx = lr.ring[rj * 128 + s + 1];
+                xj[rj][0] = nx.x;
+                xj[rj][1] = nx.y;
+                if (!UNIFORM) gj[rj] = lr.ring_g[rj * 128 + s + 1];
+                if (!DIAG) {
+                    lr.mail_w[rj * 64] = d2{aj[rj][0], aj[rj][1]};
+                    // the wave's LDS instructions complete in order; the fences keep the compiler from reordering them
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    const d2 na = lr.mail_r[rj * 64];
+                    aj[rj][0] = na.x;
+                    aj[rj][1] = na.y;
+                }
+            } else {
 #pragma unroll
-            for (int k = 0; k < D; ++k) {
-                xj[rj][k] = rot1<T>(xj[rj][k], rot_addr);
-                if (!DIAG) aj[rj][k] = rot1<T>(aj[rj][k], rot_addr);
+                for (int k = 0; k < D; ++k) {
+                    xj[rj][k] = rot1<T>(xj[rj][k], rot_addr);
+                    if (!DIAG) aj[rj][k] = rot1<T>(aj[rj][k], rot_addr);
+                }
+                if (!UNIFORM) gj[rj] = rot1<T>(gj[rj], rot_addr);
+                if constexpr (BINS) bd.rotate(rj, rot_addr, DIAG);
             }
-            if (!UNIFORM) gj[rj] = rot1<T>(gj[rj], rot_addr);
-            if constexpr (BINS) bd.rotate(rj, rot_addr, DIAG);
         }
     }
 }
@@ -457,7 +503,12 @@ __device__ unsigned long long nb_wg_trace_buf[NB_WG_TRACE_MAX][8];
 // (The general-mass row-split instantiations need 134-140 VGPRs: three waves per SIMD instead of spilling.)
 // BINS (nb_force_sym_bins.hip only): the same body with the bin read-out of BinDbg; bin_out = {s1[n], s2[n],
 // {table-free pairs, table pairs}} as unsigned 64-bit integers, added with atomics (integer sums: order-free).
-template <typename T, int D, int R, bool UNIFORM, int HOOK, int LPC = NB_LUT_MIN, bool BINS = false, bool RSPLIT = false>
+// LDSROT (fp64, D = 2, R = 4, HOOK_NONE, never with BINS): the LDS hand-off of LdsRot in place of the lane rotation.  A
+// separate instantiation picked by the launcher, like RSPLIT.  118-126 VGPRs, except the general-mass row-split one, which
+// like its rotation twin runs three waves per SIMD (156 VGPRs; bounded to four waves it spills 37 around the sweeps):
+// profiles/rotation_exchange_resources.txt.
+template <typename T, int D, int R, bool UNIFORM, int HOOK, int LPC = NB_LUT_MIN, bool BINS = false, bool RSPLIT = false,
+          bool LDSROT = false>
 __global__ void __launch_bounds__(NB_BLOCK, BINS ? 2 : ((HOOK == HOOK_GRID && LPC > NB_LUT_MIN) || (RSPLIT && !UNIFORM) ? 3 : 4))
 force_sym_kernel(const T *__restrict__ packed, const SymWork *__restrict__ work, double *__restrict__ rowslab,
                  T *__restrict__ colslab, int np, T eps2, const GridTables *__restrict__ tab, float gfac, float g_newton,
@@ -469,7 +520,14 @@ force_sym_kernel(const T *__restrict__ packed, const SymWork *__restrict__ work,
     constexpr int RJ = (NB_GRID_GENERAL_PACKED == 2 && F32_ && HOOK == HOOK_GRID && !UNIFORM && R == 4 && D == 2) ? 2 : sym_rj(D, R);
     constexpr int W = NB_BLOCK / 64;
     constexpr bool F32 = std::is_same_v<T, float>;
-    __shared__ T s_aj[W][RJ][D][64];
+    alignas(LDSROT ? 16 : alignof(T)) __shared__ T s_aj[W][RJ][D][64];
+    // LDS hand-off: the source tile's positions (and mass factors) as rings, staged once per source tile by the whole
+    // workgroup; the waves' mailboxes reuse s_aj (wave w owns s_aj[w] = mail[w][RJ][64] of 16 bytes until it leaves its
+    // column sums there after the sweep).  16 + 8 (+ 4) KiB per workgroup.
+    static_assert(!LDSROT || (!F32_ && D == 2 && R == 4 && HOOK == HOOK_NONE && !BINS), "LDS hand-off: fp64, 2-D, R = 4, no hook");
+    static_assert(!LDSROT || sizeof(s_aj) == sizeof(d2) * W * RJ * 64, "the mailboxes reuse the column buffer");
+    __shared__ d2 s_ring[LDSROT ? RJ : 1][LDSROT ? 128 : 1];
+    __shared__ double s_ring_g[LDSROT && !UNIFORM ? RJ : 1][LDSROT && !UNIFORM ? 128 : 1];
     // grid hook: threshold and LUT tables with compile-time offsets (a run-time table base costs an address add per
     // lookup: +4..8 % on the INT8 / CUSTOM kernels).  LPC = 256 serves INT8 / INT4 / CUSTOM <= 256, LPC = NB_MAX_LUT
     // the larger CUSTOM grids (33 KB: three workgroups per CU instead of four).
@@ -562,6 +620,30 @@ force_sym_kernel(const T *__restrict__ packed, const SymWork *__restrict__ work,
         for (int r = 0; r < R; ++r) { bd.ip[r] = I * B + r * 64 + lane; bd.i1[r] = bd.i2[r] = 0; }
     }
 
+    // LDS hand-off: thread t stages particle t of source tile Jt twice, 64 entries apart (NB_BLOCK = RJ x 64 threads)
+    auto stage_ring = [&](int Jt) {
+        if constexpr (LDSROT) {
+            static_assert(!LDSROT || NB_BLOCK == RJ * 64, "one staging thread per source particle");
+            const int r = threadIdx.x >> 6, l = threadIdx.x & 63;
+            const size_t p = (size_t)Jt * B + threadIdx.x;
+            const d2 v = {packed[p], packed[(size_t)np + p]};
+            s_ring[r][l] = v;
+            s_ring[r][l + 64] = v;
+            if constexpr (!UNIFORM) {
+                const double g = packed[(size_t)D * np + p];
+                s_ring_g[r][l] = g;
+                s_ring_g[r][l + 64] = g;
+            }
+        }
+    };
+    LdsRot lr{};
+    if constexpr (LDSROT) {
+        d2 *mail = reinterpret_cast<d2 *>(&s_aj[wave][0][0][0]);
+        lr = LdsRot{&s_ring[0][lane + wk_s_begin], &s_ring_g[0][UNIFORM ? 0 : lane + wk_s_begin], mail + lane, mail + ((lane + 1) & 63)};
+        if (wk.jt_begin < wk.jt_end) stage_ring(wk.jt_begin);
+        __syncthreads();
+    }
+
     for (int J = wk.jt_begin; J < wk.jt_end; ++J) {     // all four waves take the same source tile
       for (int half = 0; half < R / RJ; ++half) {       // ... in R / RJ parts of RJ source slots each
         const int hs = half * RJ;                       // first source slot of this part
@@ -632,11 +714,19 @@ force_sym_kernel(const T *__restrict__ packed, const SymWork *__restrict__ work,
                 T xj[RJ][D], gj[RJ], ai[R][D];
 #pragma unroll
                 for (int r = 0; r < RJ; ++r) {
-                    const int p = J * B + (hs + r) * 64 + ((lane + wk_s_begin) & 63);
+                    if constexpr (LDSROT) {     // the same particle (lane + s_begin) from the staged ring
+                        const d2 x0 = lr.ring[r * 128];
+                        xj[r][0] = x0.x;
+                        xj[r][1] = x0.y;
+                        if constexpr (UNIFORM) gj[r] = (T)1;
+                        else gj[r] = lr.ring_g[r * 128];
+                    } else {
+                        const int p = J * B + (hs + r) * 64 + ((lane + wk_s_begin) & 63);
 #pragma unroll
-                    for (int k = 0; k < D; ++k) xj[r][k] = packed[(size_t)k * np + p];
-                    gj[r] = UNIFORM ? (T)1 : packed[(size_t)D * np + p];
-                    if constexpr (F32 && HOOK == HOOK_GRID && !UNIFORM) gj[r] = ldexpf(gj[r], mass_exp);
+                        for (int k = 0; k < D; ++k) xj[r][k] = packed[(size_t)k * np + p];
+                        gj[r] = UNIFORM ? (T)1 : packed[(size_t)D * np + p];
+                        if constexpr (F32 && HOOK == HOOK_GRID && !UNIFORM) gj[r] = ldexpf(gj[r], mass_exp);
+                    }
                 }
 #pragma unroll
                 for (int r = 0; r < R; ++r)
@@ -644,8 +734,8 @@ force_sym_kernel(const T *__restrict__ packed, const SymWork *__restrict__ work,
                     for (int k = 0; k < D; ++k) ai[r][k] = F32 ? (T)0 : (T)row_ref(r, k);
 #define NB_SWEEP(EE)                                                                                                  \
     do {                                                                                                                 \
-        if (diag) sweep<T, D, R, RJ, true, UNIFORM, HOOK, EE, BINS>(xi, gi, ai, xj, gj, aj, eps2, rot_addr, ga, wk_s_count, bd);     \
-        else sweep<T, D, R, RJ, false, UNIFORM, HOOK, EE, BINS>(xi, gi, ai, xj, gj, aj, eps2, rot_addr, ga, wk_s_count, bd);         \
+        if (diag) sweep<T, D, R, RJ, true, UNIFORM, HOOK, EE, BINS, LDSROT>(xi, gi, ai, xj, gj, aj, eps2, rot_addr, ga, wk_s_count, bd, lr); \
+        else sweep<T, D, R, RJ, false, UNIFORM, HOOK, EE, BINS, LDSROT>(xi, gi, ai, xj, gj, aj, eps2, rot_addr, ga, wk_s_count, bd, lr);     \
     } while (0)
                 if (HOOK == HOOK_GRID && degenerate) NB_SWEEP(GRID_DEGENERATE);
                 else if (HOOK == HOOK_GRID && fast && eps2 < (T)0.01) NB_SWEEP(GRID_FAST_CLAMP);
@@ -679,7 +769,11 @@ force_sym_kernel(const T *__restrict__ packed, const SymWork *__restrict__ work,
 #pragma unroll
             for (int k = 0; k < D; ++k) s_aj[wave][r][k][home] = aj[r][k];
         __syncthreads();
-        if (J > wk.tile_i) {                            // block-uniform: at least the first row lies below J
+        // LDS hand-off: every wave is done with the ring of tile J; the next tile's goes in before the second barrier
+        if constexpr (LDSROT) {
+            if (J + 1 < wk.jt_end) stage_ring(J + 1);
+        }
+        if (J > wk.tile_i) {                           // block-uniform: at least the first row lies below J
             for (int idx = threadIdx.x; idx < RJ * D * 64; idx += NB_BLOCK) {
                 const int l = idx & 63, rk = idx >> 6;
                 const int r = rk / D, k = rk % D;
@@ -791,6 +885,19 @@ hipError_t launch_sym_rowsplit(const double *packed, const SymWork *work, int nw
         hipExtLaunchKernelGGL((force_sym_kernel<double, 2, 4, false, HOOK, NB_LUT_MIN, false, true>), dim3(nwork), dim3(NB_BLOCK), 0, st,
                               ev.start, ev.stop, 0, packed, work, rowslab, colslab, np, eps2, nullptr, gfac, 0.0f, nullptr, 0);
     return hipGetLastError();
+}
+
+// LDS hand-off instantiations (fp64, D = 2, R = 4, no hook; classic and row-split work items): see LdsRot
+template <bool RSPLIT>
+hipError_t launch_sym_ldsrot(const double *packed, const SymWork *work, int nwork, double *rowslab, double *colslab, int np,
+                             int uniform, double eps2, hipStream_t st, NbKernelEvents ev)
+{
+    return nb::pick_bool(uniform, [&](auto U) {
+        hipExtLaunchKernelGGL((force_sym_kernel<double, 2, 4, U.value, HOOK_NONE, NB_LUT_MIN, false, RSPLIT, true>), dim3(nwork),
+                              dim3(NB_BLOCK), 0, st, ev.start, ev.stop, 0, packed, work, rowslab, colslab, np, eps2, nullptr, 1.0f,
+                              0.0f, nullptr, 0);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace

@@ -365,7 +365,7 @@ int launch_pairs(nb_sim *s, const EvalRequest &rq, const Eval &e)
     if (s->is_f64) {
         HIPCHK(nb_launch_force_sym_f64((const double *)sp.packed, sp.work, sp.nwork, sp.rowslab, (double *)sp.colslab, sp.np,
                                        c.dim, sp.r, s->mass_uniform, pa_f32, c.softening_sq, s->stream, prof_events(s, slot),
-                                       sp.rowsplit ? 1 : 0));
+                                       sp.rowsplit ? 1 : 0, s->knobs.sym_rot >= 0 ? s->knobs.sym_rot : NB_SYM_ROT_DEFAULT));
         s->last_kernel = "force_sym_kernel<double";
         return NB_OK;
     }

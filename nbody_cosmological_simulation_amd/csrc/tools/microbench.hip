@@ -8,6 +8,8 @@
 #include <cstdlib>
 #include <vector>
 
+#include "../nb_force_sym_kernel.h"     // sweep<>, inv_r3_sym, LdsRot: the rotation-cost rows run the library's own pair loop
+
 #define CHECK(x)                                                                        \
     do {                                                                                \
         hipError_t e = (x);                                                             \
@@ -107,6 +109,77 @@ __global__ void __launch_bounds__(256) pair_kernel(double *out, double seed)
     out[blockIdx.x * blockDim.x + threadIdx.x] = ax + ay;
 }
 
+// ---- what the rotation step of the pair-symmetric fp64 sweep costs (nb_force_sym_kernel.h: sweep<double, 2, 4, 4>, uniform
+// masses, off-diagonal: 14 VALU + rsq per pair, 16 pairs per step).  ROT_BPERMUTE and ROT_LDS run the library's own sweep<>
+// (two ds_bpermute_b32 per pair, or the LDS hand-off of LdsRot: 0.75 wide LDS instructions per pair); ROT_NONE is the same
+// pair body with the source data and accumulators staying where they are (made opaque to the compiler once per slot, so
+// that nothing is hoisted: no instruction is emitted for that).
+enum { ROT_NONE, ROT_BPERMUTE, ROT_LDS };
+constexpr int ROT_SWEEPS = 64;      // sweeps of 64 steps per launch: 65 536 pairs per lane
+
+template <int MODE>
+__global__ void __launch_bounds__(256, 4) sweep_rot_kernel(double *out, double seed)
+{
+    constexpr int R = 4, D = 2;
+    __shared__ d2 s_ring[R][128];
+    __shared__ d2 s_mail[4][R][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double xi[R][D], gi[R], ai[R][D], xj[R][D], gj[R], aj[R][D];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        gi[r] = gj[r] = 1.0;
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            xi[r][k] = seed + threadIdx.x * 1e-3 + r + 0.5 * k;
+            xj[r][k] = 0.25 + lane * 2e-3 + 0.75 * r + 0.125 * k;
+            ai[r][k] = aj[r][k] = 0.0;
+        }
+    }
+    if (MODE == ROT_LDS) {      // the ring as force_sym_kernel stages it: 64 entries per slot, repeated
+        const int r = threadIdx.x >> 6;
+        const d2 v = {0.25 + lane * 2e-3 + 0.75 * r, 0.25 + lane * 2e-3 + 0.75 * r + 0.125};
+        s_ring[r][lane] = v;
+        s_ring[r][lane + 64] = v;
+        __syncthreads();
+    }
+    const LdsRot lr{&s_ring[0][lane], nullptr, &s_mail[wave][0][lane], &s_mail[wave][0][(lane + 1) & 63]};
+    const int rot_addr = ((lane + 1) & 63) << 2;
+    const GridArgs ga{};
+    BinDbg<R, R, false> bd;
+    const double eps2 = 0.01;
+    for (int o = 0; o < ROT_SWEEPS; ++o) {
+        if constexpr (MODE == ROT_NONE) {
+            double c15 = 1.5, c1875 = 1.875;
+            asm volatile("" : "+v"(c15), "+s"(c1875));
+#pragma unroll 1
+            for (int s = 0; s < 64; ++s) {
+#pragma unroll
+                for (int rj = 0; rj < R; ++rj) {
+#pragma unroll
+                    for (int ri = 0; ri < R; ++ri) {
+                        const double dx = xj[rj][0] - xi[ri][0], dy = xj[rj][1] - xi[ri][1];
+                        const double q = __builtin_fma(dx, dx, __builtin_fma(dy, dy, eps2));
+                        const double w = inv_r3_sym(q, c15, c1875);
+                        ai[ri][0] = __builtin_fma(w, dx, ai[ri][0]);
+                        ai[ri][1] = __builtin_fma(w, dy, ai[ri][1]);
+                        aj[rj][0] = __builtin_fma(-w, dx, aj[rj][0]);
+                        aj[rj][1] = __builtin_fma(-w, dy, aj[rj][1]);
+                    }
+                    asm volatile("" : "+v"(xj[rj][0]), "+v"(xj[rj][1]), "+v"(aj[rj][0]), "+v"(aj[rj][1]));
+                }
+            }
+        } else {
+            sweep<double, D, R, R, false, true, HOOK_NONE, 0, false, MODE == ROT_LDS>(xi, gi, ai, xj, gj, aj, eps2, rot_addr, ga, 64, bd, lr);
+        }
+    }
+    double s = 0;
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int k = 0; k < D; ++k) s += ai[r][k] + aj[r][k];
+    out[blockIdx.x * blockDim.x + threadIdx.x] = s;
+}
+
 __global__ void rsq_accuracy_kernel(const double *x, double *y_rsq, double *y_r3, int n)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -144,7 +217,7 @@ int main()
     CHECK(hipGetDeviceProperties(&prop, 0));
     const int cus = prop.multiProcessorCount;
     const double clk_ghz = prop.clockRate * 1e-6;
-    printf("device %s  CUs %d  clock %.3f GHz\n", prop.name, cus, clk_ghz);
+    printf("device %s (%s)  CUs %d  clock %.3f GHz\n", prop.name, prop.gcnArchName, cus, clk_ghz);
     double *out;
     const int blocks_per_cu[] = {1, 2, 4};
     CHECK(hipMalloc(&out, sizeof(double) * 256 * cus * 8));
@@ -152,6 +225,12 @@ int main()
     // ~150 ms of fp64 FMAs first: the chip needs tens of ms to reach its sustained clock
     for (int r = 0; r < 300; ++r) hipLaunchKernelGGL(op_kernel<OP_FMA64>, dim3(cus * 4), dim3(256), 0, 0, out, 1.5);
     CHECK(hipDeviceSynchronize());
+    {   // the clock this run holds under fp64 load: a v_fma_f64 issues every 4 cycles per SIMD (four waves per SIMD)
+        const double ms = time_kernel([&]() { hipLaunchKernelGGL(op_kernel<OP_FMA64>, dim3(cus * 4), dim3(256), 0, 0, out, 1.5); }, 5);
+        const double cyc = ms * 1e-3 * clk_ghz * 1e9 / ((double)ITERS * UNROLL * 4);
+        printf("clock held under fp64 load: %.3f GHz (v_fma_f64 at %.2f nominal cycles, 4 real); cycles below are at the NOMINAL clock\n",
+               clk_ghz * 4.0 / cyc, cyc);
+    }
 
     printf("\n# issue rate: cycles per wave64 instruction per SIMD (at nominal clock), by waves/SIMD\n");
     printf("%-16s %10s %10s %10s\n", "op", "1 wave", "2 waves", "4 waves");
@@ -177,6 +256,37 @@ int main()
         if (op == OP_MIX_PAIR) printf("   <- cycles per PAIR-instruction group (13 VALU + rsq + 2 adds)");
         printf("\n");
     }
+
+    // rotation cost of the pair-symmetric fp64 sweep, in the units of pair_body_f64 above; v_fma_f64 once more right before
+    // them gives the clock these rows held (an fp64 FMA issues every 4 cycles per SIMD)
+    printf("\n# rotation cost: cycles per PAIR (14 VALU + rsq, sweep<double, 2, 4, 4> uniform off-diagonal) per SIMD at nominal clock\n");
+    printf("%-16s %10s %10s %10s\n", "op", "1 wave", "2 waves", "4 waves");
+    const char *rot_names[] = {"v_fma_f64", "pair_sym_f64", "pair_sym+bperm", "pair_sym+ldsrot"};
+    double fma_cyc4 = 4.0;
+    for (int row = 0; row < 4; ++row) {
+        printf("%-16s", rot_names[row]);
+        for (int bpc : blocks_per_cu) {
+            const int grid = cus * bpc;
+            auto launch = [&]() {
+                switch (row) {
+                case 0: hipLaunchKernelGGL(op_kernel<OP_FMA64>, dim3(grid), dim3(256), 0, 0, out, 1.5); break;
+                case 1: hipLaunchKernelGGL(sweep_rot_kernel<ROT_NONE>, dim3(grid), dim3(256), 0, 0, out, 1.5); break;
+                case 2: hipLaunchKernelGGL(sweep_rot_kernel<ROT_BPERMUTE>, dim3(grid), dim3(256), 0, 0, out, 1.5); break;
+                case 3: hipLaunchKernelGGL(sweep_rot_kernel<ROT_LDS>, dim3(grid), dim3(256), 0, 0, out, 1.5); break;
+                }
+            };
+            const double ms = time_kernel(launch, 5);
+            const double per_simd = row == 0 ? (double)ITERS * UNROLL * bpc : (double)ROT_SWEEPS * 64 * 16 * bpc;
+            const double cyc = ms * 1e-3 * clk_ghz * 1e9 / per_simd;
+            if (row == 0 && bpc == 4) fma_cyc4 = cyc;
+            printf(" %10.2f", cyc);
+        }
+        if (row == 2) printf("   <- + 2 ds_bpermute_b32 per pair");
+        if (row == 3) printf("   <- + 0.75 ds_read_b128 / ds_write_b128 per pair");
+        printf("\n");
+    }
+    printf("clock held (4 cycles per v_fma_f64 at 4 waves): %.3f GHz of %.3f nominal -> real cycles = nominal x %.3f\n",
+           clk_ghz * 4.0 / fma_cyc4, clk_ghz, 4.0 / fma_cyc4);
 
     // accuracy of v_rsq_f64 and of the corrected q^-1.5
     const int n = 1 << 20;
