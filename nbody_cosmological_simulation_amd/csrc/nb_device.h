@@ -20,12 +20,20 @@ __device__ __forceinline__ float mass_prod_f32(float mi, float mj, int mass_dt)
 
 // r2 exactly as the reference's fp32 tensors produce it: (dx*dx + dy*dy [+ dz*dz]) + eps2, one
 // rounding per operation, no fused multiply-add (simulation.py:86).
+// s_f32_exact: the sum of squares before eps2 joins it (the max-r2 searches take their distance bound from it: eps2
+// added and subtracted again would leave half an ulp of eps2 in place of a small separation).
 template <int D>
-__device__ __forceinline__ float r2_f32_exact(const float *d, float eps2)
+__device__ __forceinline__ float s_f32_exact(const float *d)
 {
     float s = __fadd_rn(__fmul_rn(d[0], d[0]), __fmul_rn(d[1], d[1]));
     if (D == 3) s = __fadd_rn(s, __fmul_rn(d[2], d[2]));
-    return __fadd_rn(s, eps2);
+    return s;
+}
+
+template <int D>
+__device__ __forceinline__ float r2_f32_exact(const float *d, float eps2)
+{
+    return __fadd_rn(s_f32_exact<D>(d), eps2);
 }
 
 // bin index = number of thresholds <= r2 (branch-free binary search over the LDS table)

@@ -419,16 +419,29 @@ r2max_kernel(const float *__restrict__ pos, ForceGeom g, float eps2, GridTables 
 
 // ------------------------------------------------------------------------------------------
 // K2 with pruning.  The pair with the largest r2 lies on the outside of the particle cloud, so a
-// brute-force scan of all N^2 pairs is wasteful.  Exactness argument (all quantities fp32, margins
-// 1e-5 >> the ~4e-7 rounding of r2 and rho):
+// brute-force scan of all N^2 pairs is wasteful.  Exactness argument (all quantities fp32; s = dx*dx + dy*dy [+ dz*dz]
+// is r2 before eps2 is added, s_f32_exact):
 //   * c = bounding-box centre, rho_i = |x_i - c|; for any pair dist(a,b) <= rho_a + rho_b <= rho_a + rho_max;
-//   * LB = r2 of a real pair found by two farthest-point hops (far -> g -> h), so max r2 >= LB;
-//   * hence both members of the maximal pair satisfy rho >= sqrt(LB - eps2) - rho_max (up to margins).
+//   * (g, h) = a real pair found by two farthest-point hops (far -> g -> h), s_gh its s, LB = s_gh + eps2 its r2;
+//   * fp32 addition of eps2 is monotone, so a pair whose r2 is strictly larger than LB has s > s_gh: its distance is
+//     at least sqrt(s_gh), and both of its members satisfy rho >= sqrt(s_gh) - rho_max;
+//   * a pair that only ties with LB need not be found: (g, h) attains the same fp32 value, and g and h always pass the
+//     test with their own s_gh (rho_g >= dist(g,h) - rho_h >= sqrt(s_gh) - rho_max).  So finite input never leaves the
+//     candidate list empty.
+// The margins (1e-5 on each of sqrt(s_gh), rho_i and rho_max) cover the ~2e-7 relative rounding of s and of the rhos.
+// They are RELATIVE to quantities that are measured directly: the bound is not sqrt(LB - eps2), whose subtraction
+// returns s_gh +- half an ulp of eps2 -- far more than any margin once the softening dwarfs the cloud (a cloud of
+// radius 1e-3 softenings used to lose every candidate).
+// Non-finite input: a NaN or infinite coordinate makes the diagonal of torch's r2 matrix NaN (inf - inf), so the
+// maximum is NaN (nan_flag).  Finite coordinates whose squares overflow leave s_gh or rho_max infinite: every particle
+// is kept then and the scan covers all pairs (the maximum is +inf, as torch's).
 // Candidates passing that test are compacted and scanned exhaustively with the exact r2 formula.
 // For a disk galaxy this keeps a few percent of the particles (~0.1 % of the pairs).
 // ------------------------------------------------------------------------------------------
-// Stage 1 of the bounding box: per-block min/max of every coordinate (+ a NaN flag) as ordered
+// Stage 1 of the bounding box: per-block min/max of every coordinate (+ a flag for NaN / infinite ones) as ordered
 // integer keys folded with atomics; the rho kernel decodes them (two launches, a few us each).
+constexpr float NB_F32_MAX = 3.402823466e+38f;    // !(|v| <= NB_F32_MAX): v is NaN or infinite
+
 __device__ __forceinline__ unsigned int order_key(float v)
 {
     const unsigned int u = __float_as_uint(v);
@@ -455,7 +468,7 @@ prune_bbox_kernel(const float *__restrict__ pos, int n, PruneState *__restrict__
 #pragma unroll
         for (int k = 0; k < D; ++k) {
             const float v = pos[(size_t)i * D + k];
-            bad |= (v != v);
+            bad |= !(fabsf(v) <= NB_F32_MAX);              // NaN or +-inf
             const unsigned int key = order_key(v);
             mn[k] = min(mn[k], key);
             mx[k] = max(mx[k], key);
@@ -553,15 +566,22 @@ prune_hop_kernel(const float *__restrict__ pos, int n, float eps2, const unsigne
 
 template <int D>
 __global__ void __launch_bounds__(NB_BLOCK)
-prune_compact_kernel(const float *__restrict__ pos, const float *__restrict__ rho, int n, float eps2,
-                     float *__restrict__ cand, PruneState *__restrict__ ps)
+prune_compact_kernel(const float *__restrict__ pos, const float *__restrict__ rho, int n, float *__restrict__ cand,
+                     PruneState *__restrict__ ps)
 {
     const int i = blockIdx.x * NB_BLOCK + threadIdx.x;
     if (i >= n) return;
-    const float lb = __uint_as_float((unsigned int)(ps->lb[1] >> 32));
+    // the second hop's pair g -> h (indices in the low words of lb[0] / lb[1]): its squared separation WITHOUT eps2
+    const int g = (int)(ps->lb[0] & 0xffffffffull), h = (int)(ps->lb[1] & 0xffffffffull);
+    float d[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) d[k] = __fsub_rn(pos[(size_t)h * D + k], pos[(size_t)g * D + k]);
+    const float s_pair = s_f32_exact<D>(d);
     const float rho_max = __uint_as_float((unsigned int)(ps->far >> 32));
-    const float need = sqrtf(fmaxf(lb - eps2, 0.0f)) * (1.0f - 1e-5f) - rho_max * (1.0f + 1e-5f);
-    if (rho[i] * (1.0f + 1e-5f) >= need) {
+    // finite coordinates whose squares overflow: no bound to be had (inf - inf), keep everyone -- the scan is then all pairs
+    const bool keep_all = !(s_pair <= NB_F32_MAX) || !(rho_max <= NB_F32_MAX);
+    const float need = sqrtf(s_pair) * (1.0f - 1e-5f) - rho_max * (1.0f + 1e-5f);
+    if (keep_all || rho[i] * (1.0f + 1e-5f) >= need) {
         const int slot = atomicAdd(&ps->count, 1);
 #pragma unroll
         for (int k = 0; k < D; ++k) cand[(size_t)slot * D + k] = pos[(size_t)i * D + k];
@@ -579,7 +599,7 @@ prune_scan_kernel(const float *__restrict__ cand, float eps2, const PruneState *
     const int m = ps->count;
     const int tid = threadIdx.x;
     const int ibase = blockIdx.x * NB_BLOCK;
-    if (ps->nan_flag) {                          // a NaN coordinate: torch's max() would be NaN
+    if (ps->nan_flag) {                          // a NaN / infinite coordinate: torch's max() would be NaN
         if (blockIdx.x == 0 && tid == 0) atomicMax(&tab->r2max_bits, 0x7fc00000u);
         return;
     }
@@ -996,11 +1016,13 @@ ens_r2max_tables_kernel(const float *__restrict__ pos, ForceGeom g, const float 
 
 // ------------------------------------------------------------------------------------------
 // Tracked max-r2 search (round 3): two launches per evaluation instead of six (+ tables).
-// Exactness argument as for the pruned search above, with the lower bound LB taken from the far pair of the LAST
-// evaluation re-evaluated at the new positions, a fixed centre c, and rho_M = (last measured rho_max) + twice its last
-// growth + 1e-4 of it as the bound on every rho: both members of the maximal pair satisfy rho >= sqrt(LB - eps2) - rho_M.  The filter pass
+// Exactness argument as for the pruned search above, with the pair (g, h) being the far pair of the LAST evaluation, its
+// s re-evaluated at the new positions (eps2 left out, as there), a fixed centre c, and rho_M = (last measured rho_max)
+// + twice its last growth + 1e-4 of it as the bound on every rho: both members of a pair with a larger r2 satisfy
+// rho >= sqrt(s_gh) - rho_M, and so do g and h themselves.  The filter pass
 // measures the actual rho_max; if it exceeds rho_M (a particle left the margin) the scan simply takes ALL particles
-// -- slower, still exact.  NaN coordinates poison the maximum exactly as torch's max() does.
+// -- slower, still exact.  NaN and infinite coordinates poison the maximum exactly as torch's max() does (the diagonal
+// holds inf - inf); where s_gh or rho_M overflows on finite coordinates every particle is a candidate.
 // ------------------------------------------------------------------------------------------
 template <int D>
 __global__ void __launch_bounds__(NB_BLOCK)
@@ -1014,8 +1036,11 @@ track_filter_kernel(const float *__restrict__ pos, int n, float eps2, float *__r
         float d[D];
 #pragma unroll
         for (int k = 0; k < D; ++k) d[k] = __fsub_rn(pos[(size_t)ps->pair_j * D + k], pos[(size_t)ps->pair_i * D + k]);
-        const float lb = r2_f32_exact<D>(d, eps2);
-        s_need = sqrtf(fmaxf(lb - eps2, 0.0f)) * (1.0f - 1e-5f) - ps->rho_m * (1.0f + 1e-5f);
+        const float s_pair = s_f32_exact<D>(d);            // the far pair's squared separation, eps2 left out (see above)
+        const float rho_m = ps->rho_m;
+        // finite coordinates whose squares overflow: no bound to be had, every particle passes (rho >= 0) and is scanned
+        const bool keep_all = !(s_pair <= NB_F32_MAX) || !(rho_m <= NB_F32_MAX);
+        s_need = keep_all ? 0.0f : sqrtf(s_pair) * (1.0f - 1e-5f) - rho_m * (1.0f + 1e-5f);
         s_nan = 0;
     }
     __syncthreads();
@@ -1027,7 +1052,7 @@ track_filter_kernel(const float *__restrict__ pos, int n, float eps2, float *__r
 #pragma unroll
         for (int k = 0; k < D; ++k) {
             x[k] = pos[(size_t)i * D + k];
-            bad |= (x[k] != x[k]);
+            bad |= !(fabsf(x[k]) <= NB_F32_MAX);           // NaN or +-inf
             const float d = x[k] - ps->c[k];
             s += d * d;
         }
@@ -1092,7 +1117,7 @@ __device__ __forceinline__ bool track_finish(unsigned long long best_i, unsigned
             const unsigned long long fi = atomicMax(&ps->best_i, 0ull), fj = atomicMax(&ps->best_j, 0ull);
             unsigned int bits = (unsigned int)(fi >> 32);
             if (m <= 0) bits = 0u;
-            if (nan_flag) bits = 0x7fc00000u;                     // a NaN coordinate: torch's max() would be NaN
+            if (nan_flag) bits = 0x7fc00000u;                     // a NaN / infinite coordinate: torch's max() would be NaN
             // a single particle (or none scanned): the diagonal pair r2 = eps2 is the maximum
             if (bits == 0u) bits = r2_order_bits(eps2);
             *bits_out = bits;
@@ -1344,7 +1369,7 @@ hipError_t nb_launch_r2max_pruned(const float *pos, int n, int dim, float eps2, 
         hipLaunchKernelGGL((prune_rho_kernel<D.value>), dim3(blocks), dim3(NB_BLOCK), 0, st, pos, n, rho, ps);
         hipLaunchKernelGGL((prune_hop_kernel<D.value>), dim3(blocks), dim3(NB_BLOCK), 0, st, pos, n, eps2, &ps->far, &ps->lb[0]);
         hipLaunchKernelGGL((prune_hop_kernel<D.value>), dim3(blocks), dim3(NB_BLOCK), 0, st, pos, n, eps2, &ps->lb[0], &ps->lb[1]);
-        hipLaunchKernelGGL((prune_compact_kernel<D.value>), dim3(blocks), dim3(NB_BLOCK), 0, st, pos, rho, n, eps2, cand, ps);
+        hipLaunchKernelGGL((prune_compact_kernel<D.value>), dim3(blocks), dim3(NB_BLOCK), 0, st, pos, rho, n, cand, ps);
         hipLaunchKernelGGL((prune_scan_kernel<D.value>), dim3(blocks), dim3(NB_BLOCK), 0, st, cand, eps2, ps, tab);
         return hipGetLastError();
     });

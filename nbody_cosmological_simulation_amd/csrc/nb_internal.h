@@ -67,7 +67,7 @@ struct PruneState {
     unsigned long long far;   // (rho bits << 32 | index) of the particle farthest from the box centre
     unsigned long long lb[2]; // (r2 bits << 32 | index): farthest partner of `far`, then of that partner
     int count;                // candidates kept
-    int nan_flag;             // a NaN coordinate was seen -> r2max is NaN
+    int nan_flag;             // a NaN or infinite coordinate was seen -> r2max is NaN
     // ---- tracked search (round 3): after a seeding evaluation every further one starts from its predecessor's result.
     // The farthest pair of the last evaluation, re-evaluated at the new positions, is the lower bound the two hops
     // used to find; the centre stays where the seeding evaluation put it (any fixed point serves the bound
