@@ -1,8 +1,99 @@
-// nb_device.h -- device-side helpers shared by the force kernels (nb_force.hip, nb_force_sym.hip).
+// nb_device.h -- device-side helpers shared by the kernels: the exact-arithmetic primitives that the bit-for-bit
+// contracts rest on, the per-member stop rule of the ensemble tick path, and the fp32 r2 / grid-bin helpers of the force
+// kernels.
 #pragma once
+#include <climits>
+
 #include "nb_internal.h"
 
 namespace nbdev {
+
+// ---- exact arithmetic: one correctly rounded operation each, never contracted whatever the build's flags ----------------
+template <typename T> __device__ __forceinline__ T mul_rn(T a, T b);
+template <> __device__ __forceinline__ float mul_rn<float>(float a, float b) { return __fmul_rn(a, b); }
+template <> __device__ __forceinline__ double mul_rn<double>(double a, double b) { return __dmul_rn(a, b); }
+template <typename T> __device__ __forceinline__ T add_rn(T a, T b);
+template <> __device__ __forceinline__ float add_rn<float>(float a, float b) { return __fadd_rn(a, b); }
+template <> __device__ __forceinline__ double add_rn<double>(double a, double b) { return __dadd_rn(a, b); }
+template <typename T> __device__ __forceinline__ T div_rn(T a, T b);
+template <> __device__ __forceinline__ float div_rn<float>(float a, float b) { return __fdiv_rn(a, b); }
+template <> __device__ __forceinline__ double div_rn<double>(double a, double b) { return __ddiv_rn(a, b); }
+// sqrtf, not __fsqrt_rn: the latter compiles to the bare v_sqrt_f32 -- 1 ulp -- on this toolchain, sqrtf carries the fix-up
+// to correct rounding.  Solo and batched diagnostics agree star by star only because both take THIS root.
+template <typename T> __device__ __forceinline__ T sqrt_rn(T x);
+template <> __device__ __forceinline__ float sqrt_rn<float>(float x) { return __builtin_sqrtf(x); }
+template <> __device__ __forceinline__ double sqrt_rn<double>(double x) { return __dsqrt_rn(x); }
+// torch semantics: `a + b * s` is two rounded operations (no fused multiply-add), with the Python scalar cast to the
+// tensor dtype first
+template <typename T> __device__ __forceinline__ T axpy_rn(T a, T b, T s) { return add_rn<T>(a, mul_rn<T>(b, s)); }
+
+// sort keys: radii are >= +0 or NaN, so their bit patterns order like the values; NaN goes last (torch.sort's rule)
+template <typename A> struct KeyOf;
+template <> struct KeyOf<float> {
+    typedef unsigned type;
+    static __device__ __forceinline__ unsigned make(float x) { return x != x ? 0xffffffffu : __float_as_uint(x); }
+    static __device__ __forceinline__ float back(unsigned k) { return __uint_as_float(k); }   // all-ones is a NaN
+};
+template <> struct KeyOf<double> {
+    typedef unsigned long long type;
+    static __device__ __forceinline__ unsigned long long make(double x)
+    { return x != x ? ~0ull : (unsigned long long)__double_as_longlong(x); }
+    static __device__ __forceinline__ double back(unsigned long long k) { return __longlong_as_double((long long)k); }
+};
+
+// the bit tests of the explosion watch (any exponent-all-ones value) and of the crash-point detector (NaN and Inf told
+// apart), side by side: two questions, not one
+__device__ __forceinline__ bool non_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+__device__ __forceinline__ bool non_finite(double x) { return ((unsigned int)__double2hiint(x) & 0x7ff00000u) == 0x7ff00000u; }
+__device__ __forceinline__ void classify(float x, bool &nan, bool &inf)
+{
+    const unsigned int u = __float_as_uint(x);
+    if ((u & 0x7f800000u) == 0x7f800000u) {
+        if (u & 0x007fffffu) nan = true; else inf = true;
+    }
+}
+__device__ __forceinline__ void classify(double x, bool &nan, bool &inf)
+{
+    const unsigned int hi = (unsigned int)__double2hiint(x);
+    if ((hi & 0x7ff00000u) == 0x7ff00000u) {
+        if ((hi & 0x000fffffu) | (unsigned int)__double2loint(x)) nan = true; else inf = true;
+    }
+}
+
+// ---- per-member stops of the ensemble tick path (nb_ens_run_members) -----------------------------------------------------
+// Every kernel of the tick path takes `stop` (device, one int per member, or null: no member ever stops) and the launch's
+// tick index t = ticks the call has already closed.  The kernels come in two instantiations, STOPS = false for a launch
+// without the array: its code is what it was before there were stops.  (One kernel with a run-time null test was measured
+// first, N = 1024 on an MI355X: the test sits in front of the loads of the other kernel arguments, a scalar-memory round
+// trip of its own in every launch, +0.3 to +0.9 us per launch.)  With STOPS a workgroup reads its member's stop once:
+// left = stop[b] - t ticks are still the member's.
+//   left <= 0   the member is done: the workgroup returns
+//   left == 1   this launch closes the member's last tick: it gets NB_KICK_CLOSE whatever the launch's mode is
+//   else        the launch's own mode
+// Where the positions ping-pong, a member on its last tick (left == 1) or just stopped (left == 0: budget 0, or halted by
+// the watch kernel behind the previous launch) also gets its positions carried into the second buffer, bit for bit, so
+// that both buffers hold a stopped member's final positions whatever the host swaps later: carry where left <= 1.
+// (The step kernels write that test as `STOPS && left <= 1`: the front end then drops the block from the instantiation
+// without stops, which keeps it the code of before instruction for instruction, not only byte for byte.)
+template <bool STOPS>
+__device__ __forceinline__ int ens_ticks_left(const int *__restrict__ stop, int b, int t)
+{
+    if constexpr (STOPS) return stop[b] - t;
+    else return INT_MAX;
+}
+// the kick mode of a member with `left` >= 1 ticks under a launch of mode `kick`
+__device__ __forceinline__ int ens_kick_mode(int left, int kick)
+{
+    return (left == 1 && kick != NB_KICK_NONE) ? NB_KICK_CLOSE : kick;
+}
+// the watch kernels behind a sampled tick t (nb_ens_watch.hip, nb_ens_crash.hip): the member has not stopped before this
+// tick and no earlier check halted it (halted: its reason / kind, 0 = none)
+__device__ __forceinline__ bool ens_still_running(const int *stop, const int *halted, int b, int t)
+{
+    return stop[b] >= t && halted[b] == 0;
+}
+
+// ---- the force kernels' helpers ------------------------------------------------------------------------------------------
 
 __device__ __forceinline__ float round_bf16(float x) { return (float)(__bf16)x; }
 __device__ __forceinline__ float round_f16(float x) { return (float)(_Float16)x; }

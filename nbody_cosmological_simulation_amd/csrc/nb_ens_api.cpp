@@ -3,7 +3,7 @@
 // a loop of solo handles issues B.  Host orchestration only, as in nb_api.cpp / nb_step.cpp.
 //
 // Layout: contiguous (B, N, D) positions (two buffers: they ping-pong as in the solo step), velocities, accelerations and
-// (B, N) masses in the storage type (fp64 under FLOAT64, else fp32), and a device array of NB_ENS_PARAM_WORDS scalars per
+// (B, N) masses in the storage type (fp64 under FLOAT64, else fp32), and a device array of one EnsScalars record per
 // member, cast on the host exactly as the solo launch casts them.  Nothing here is indexed by anything but the member.
 //
 // Grid modes (nb_ens_create_grid: INT8_SIM / INT4_SIM / CUSTOM, fp32 state) add, beside these: one GridTables and one level
@@ -17,12 +17,11 @@
 // once instead (nb_ens_energy.hip: two launches on the handle's stream, values at the project's bars rather than the
 // solo engine's bits), the latter between the ticks of a run into a history that is copied out once at the end.
 //
-// nb_ens_step, nb_ens_run_recorded and nb_ens_run_members issue ONE launch train (run_train).  The last gives every member
-// a stop tick of its own in a device array that every kernel of the tick path reads (nb_ensemble.hip) and that the
-// explosion watch (nb_ens_watch.hip) lowers on the device; the first two pass no array: no member ever stops, and the
-// kernels launched are the instantiations without stops.  nb_ens_run_crash_watched is the same train with every tick
-// sampled and the crash-point detector (nb_ens_crash.hip) in the watch's place; nb_ens_crash_measures is that kernel alone
-// on the resident state.
+// nb_ens_step issues ONE launch train (run_train) and returns; nb_ens_run_recorded, nb_ens_run_members and
+// nb_ens_run_crash_watched are argument checks in front of run_sampled: the same train with samples, the members' stop
+// ticks in a device array that every kernel of the tick path reads (nb_device.h) and a watch kernel lowers on the device
+// (nb_ens_watch.hip, nb_ens_crash.hip), and one wait.  The step and run_recorded pass no array: no member ever stops, and
+// the kernels launched are the instantiations without stops.  nb_ens_crash_measures is the detector's kernel alone.
 #include <algorithm>
 #include <cstddef>
 #include <cstring>
@@ -38,7 +37,7 @@ struct nb_ens {
     int hook = HOOK_NONE, lanes = 64;
     std::vector<double> G, eps2, dt;          // per member, as given
     std::vector<char> prm_host;               // what the device array holds (or is about to)
-    void *prm = nullptr;                      // device: members * NB_ENS_PARAM_WORDS elements of the storage type
+    void *prm = nullptr;                      // device: one EnsScalars of the storage type per member
     void *pos = nullptr, *pos_alt = nullptr, *vel = nullptr, *acc = nullptr, *mass = nullptr;
     bool have_pos = false, have_vel = false, have_mass = false, have_acc = false;
     int64_t force_launches = 0;               // batched force launches since creation (kick + drift launches not counted)
@@ -79,20 +78,20 @@ inline size_t el(const nb_ens *e) { return e->is_f64 ? 8 : 4; }
 inline size_t cnt_nd(const nb_ens *e) { return (size_t)e->cfg.members * e->cfg.n * e->cfg.dim; }
 inline size_t cnt_n(const nb_ens *e) { return (size_t)e->cfg.members * e->cfg.n; }
 
-// the casts of nb_launch_small_step / launch_s: fp64 (T)x; fp32 (float)G, (float)eps2, (float)(dt / 2), (float)dt
+// one EnsScalars<T> per member with the casts of nb_launch_small_step / launch_s: (T)G, (T)eps2, (T)(dt / 2), (T)dt
+template <typename T>
+void fill_params(nb_ens *e)
+{
+    for (size_t b = 0; b < e->G.size(); ++b) {
+        const EnsScalars<T> p = {(T)e->G[b], (T)e->eps2[b], (T)(e->dt[b] / 2), (T)e->dt[b]};
+        memcpy(e->prm_host.data() + b * sizeof p, &p, sizeof p);
+    }
+}
+
 int upload_params(nb_ens *e)
 {
-    const int B = e->cfg.members;
-    for (int b = 0; b < B; ++b) {
-        const double half_dt = e->dt[b] / 2;
-        if (e->is_f64) {
-            const double v[NB_ENS_PARAM_WORDS] = {e->G[b], e->eps2[b], half_dt, e->dt[b]};
-            memcpy(e->prm_host.data() + (size_t)b * sizeof v, v, sizeof v);
-        } else {
-            const float v[NB_ENS_PARAM_WORDS] = {(float)e->G[b], (float)e->eps2[b], (float)half_dt, (float)e->dt[b]};
-            memcpy(e->prm_host.data() + (size_t)b * sizeof v, v, sizeof v);
-        }
-    }
+    if (e->is_f64) fill_params<double>(e);
+    else fill_params<float>(e);
     // on the handle's stream, behind the launches that still read the old values; the wait keeps prm_host free to rewrite
     HIPCHK(hipMemcpyAsync(e->prm, e->prm_host.data(), e->prm_host.size(), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -273,6 +272,66 @@ int check_steppable(const nb_ens *e)
     return NB_OK;
 }
 
+// nsteps[0 .. members) are tick budgets: all >= 0, *nmax the largest
+int check_budgets(const nb_ens *e, const int32_t *nsteps, int32_t *nmax)
+{
+    if (!nsteps) return fail(NB_ERR_INVALID, "null nsteps");
+    *nmax = 0;
+    for (int b = 0; b < e->cfg.members; ++b) {
+        if (nsteps[b] < 0) return fail(NB_ERR_INVALID, "nsteps[%d] must be >= 0 (got %d)", b, nsteps[b]);
+        *nmax = std::max(*nmax, nsteps[b]);
+    }
+    return NB_OK;
+}
+
+// The recorded run behind nb_ens_run_recorded / _members / _crash_watched, arguments checked: `nmax` ticks of run_train
+// sampled every `every` (0: never) under `watch`.  budgets: the members' stop ticks, uploaded beside halt reasons of 0 and
+// read back into stop_tick / why -- or null: NO stop array is passed and the kernels without stops run.  WATCH_CRASH primes
+// the detector in front of the launches (dt; zeroed flags and measures, which a member that is never checked -- budget 0
+// -- reports; the previous positions) and reads flags / measures back.  history_out is the one wait; *samples is set last.
+int run_sampled(nb_ens *e, const int32_t *budgets, int32_t nmax, int32_t every, WatchMode watch, double *kinetic,
+                double *potential, int64_t capacity, int on_device, int32_t *samples, int32_t *stop_tick, int32_t *why,
+                int32_t *flags, double *measures)
+{
+    const size_t B = (size_t)e->cfg.members;
+    const int64_t S = every ? 1 + (int64_t)(nmax / every) : 0;
+    if (capacity < S && watch == WATCH_CRASH)
+        return fail(NB_ERR_INVALID, "capacity of %lld samples is below the %lld of %d ticks sampled every tick",
+                    (long long)capacity, (long long)S, nmax);
+    if (capacity < S)
+        return fail(NB_ERR_INVALID, "capacity of %lld samples is below the %lld of %d ticks sampled every %d",
+                    (long long)capacity, (long long)S, nmax, every);
+    DeviceGuard guard(e->cfg.device);
+    if (S)
+        if (int rc = energy_buffers(e, S)) return rc;
+    if (watch == WATCH_CRASH)
+        if (int rc = crash_buffers(e)) return rc;
+    const size_t stop_bytes = 2 * B * sizeof(int32_t);
+    if (budgets) {
+        if (!e->stops) HIPCHK(hipMalloc((void **)&e->stops, stop_bytes));
+        // stops_host is free to rewrite: every call that uploads it waits before it returns (e->dt: nb_ens_set_params waits too)
+        static_assert(NB_ENS_REASON_NONE == 0 && NB_ENS_CRASH_NONE == 0, "one initial value serves both watches");
+        e->stops_host.assign(2 * B, 0);
+        std::copy(budgets, budgets + B, e->stops_host.begin());
+        HIPCHK(hipMemcpyAsync(e->stops, e->stops_host.data(), stop_bytes, hipMemcpyHostToDevice, e->stream));
+    }
+    if (watch == WATCH_CRASH) {
+        HIPCHK(hipMemcpyAsync(e->dt_dev, e->dt.data(), B * sizeof(double), hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemsetAsync(e->crash_out, 0, B * (4 * sizeof(double) + sizeof(int32_t)), e->stream));
+        HIPCHK(hipMemcpyAsync(e->prev_pos, e->pos, cnt_nd(e) * el(e), hipMemcpyDeviceToDevice, e->stream));
+    }
+    if (int rc = run_train(e, nmax, every, budgets ? e->stops : nullptr, watch)) return rc;
+    if (budgets) HIPCHK(hipMemcpyAsync(e->stops_host.data(), e->stops, stop_bytes, hipMemcpyDeviceToHost, e->stream));
+    if (watch == WATCH_CRASH)
+        if (int rc = crash_out_async(e)) return rc;
+    if (int rc = history_out(e, S, kinetic, potential, on_device)) return rc;      // (waits, with S = 0 too)
+    if (budgets && stop_tick) std::copy(e->stops_host.begin(), e->stops_host.begin() + B, stop_tick);
+    if (budgets && why) std::copy(e->stops_host.begin() + B, e->stops_host.end(), why);
+    if (watch == WATCH_CRASH) crash_results(e, flags, measures);
+    if (samples) *samples = (int32_t)S;
+    return NB_OK;
+}
+
 // room for one batched evaluation of the diagnostics with `num_bins` bins (buffers grow, never shrink)
 int metrics_buffers(nb_ens *e, int num_bins)
 {
@@ -326,7 +385,7 @@ int create(nb_ens **out, const nb_ens_config *cfg, const int32_t *levels, const 
     e->G.assign(G, G + B);
     e->eps2.assign(softening_sq, softening_sq + B);
     e->dt.assign(dt, dt + B);
-    e->prm_host.resize((size_t)B * NB_ENS_PARAM_WORDS * el(e));
+    e->prm_host.resize((size_t)B * (f64 ? sizeof(EnsScalars<double>) : sizeof(EnsScalars<float>)));
     const size_t nd_bytes = cnt_nd(e) * el(e);
     hipError_t he = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
     if (he == hipSuccess) he = hipMalloc(&e->prm, e->prm_host.size());
@@ -512,7 +571,7 @@ int nb_ens_energies(nb_ens *e, double *kinetic, double *potential, int on_device
     return history_out(e, 1, kinetic, potential, on_device);
 }
 
-// run_train with samples; nothing waits on the stream before history_out
+// run_train with samples and no stop array
 int nb_ens_run_recorded(nb_ens *e, int32_t nsteps, int32_t every, double *kinetic, double *potential, int64_t capacity,
                         int on_device, int32_t *samples)
 {
@@ -520,54 +579,23 @@ int nb_ens_run_recorded(nb_ens *e, int32_t nsteps, int32_t every, double *kineti
     if (int rc = check_steppable(e)) return rc;
     if (nsteps < 0) return fail(NB_ERR_INVALID, "nsteps must be >= 0 (got %d)", nsteps);
     if (every < 1) return fail(NB_ERR_INVALID, "every must be >= 1 (got %d)", every);
-    const int64_t S = 1 + nsteps / every;
-    if (capacity < S)
-        return fail(NB_ERR_INVALID, "capacity of %lld samples is below the %lld of %d ticks sampled every %d",
-                    (long long)capacity, (long long)S, nsteps, every);
-    DeviceGuard guard(e->cfg.device);
-    if (int rc = energy_buffers(e, S)) return rc;
-    if (int rc = run_train(e, nsteps, every, nullptr, WATCH_NONE)) return rc;
-    if (samples) *samples = (int32_t)S;
-    return history_out(e, S, kinetic, potential, on_device);
+    return run_sampled(e, nullptr, nsteps, every, WATCH_NONE, kinetic, potential, capacity, on_device, samples, nullptr, nullptr,
+                       nullptr, nullptr);
 }
 
-// run_train with the members' budgets as their stop ticks (and the watch lowering them); one upload in front of the
-// launches, one read-back of stop ticks and reasons behind them, one wait
+// run_train with the members' budgets as their stop ticks (and the watch lowering them)
 int nb_ens_run_members(nb_ens *e, const int32_t *nsteps, int32_t every, int32_t watch, double *kinetic, double *potential,
                        int64_t capacity, int on_device, int32_t *samples, int32_t *stop_tick, int32_t *reason)
 {
     if (samples) *samples = 0;
     if (int rc = check_steppable(e)) return rc;
-    if (!nsteps) return fail(NB_ERR_INVALID, "null nsteps");
-    const int B = e->cfg.members;
     int32_t nmax = 0;
-    for (int b = 0; b < B; ++b) {
-        if (nsteps[b] < 0) return fail(NB_ERR_INVALID, "nsteps[%d] must be >= 0 (got %d)", b, nsteps[b]);
-        nmax = std::max(nmax, nsteps[b]);
-    }
+    if (int rc = check_budgets(e, nsteps, &nmax)) return rc;
     if (every < 0) return fail(NB_ERR_INVALID, "every must be >= 0 (got %d)", every);
     if (watch != 0 && watch != 1) return fail(NB_ERR_INVALID, "watch must be 0 or 1 (got %d)", watch);
     if (watch && every < 1) return fail(NB_ERR_INVALID, "the watch tests sampled ticks: it needs every >= 1");
-    const int64_t S = every ? 1 + nmax / every : 0;
-    if (capacity < S)
-        return fail(NB_ERR_INVALID, "capacity of %lld samples is below the %lld of %d ticks sampled every %d",
-                    (long long)capacity, (long long)S, nmax, every);
-    DeviceGuard guard(e->cfg.device);
-    if (S)
-        if (int rc = energy_buffers(e, S)) return rc;
-    const size_t bytes = 2 * (size_t)B * sizeof(int32_t);
-    if (!e->stops) HIPCHK(hipMalloc((void **)&e->stops, bytes));
-    // stops_host is free to rewrite: every call that uploads it waits before it returns
-    e->stops_host.assign(2 * (size_t)B, NB_ENS_REASON_NONE);
-    std::copy(nsteps, nsteps + B, e->stops_host.begin());
-    HIPCHK(hipMemcpyAsync(e->stops, e->stops_host.data(), bytes, hipMemcpyHostToDevice, e->stream));
-    if (int rc = run_train(e, nmax, every, e->stops, watch ? WATCH_EXPLOSION : WATCH_NONE)) return rc;
-    HIPCHK(hipMemcpyAsync(e->stops_host.data(), e->stops, bytes, hipMemcpyDeviceToHost, e->stream));
-    if (int rc = history_out(e, S, kinetic, potential, on_device)) return rc;      // (waits, with S = 0 too)
-    if (stop_tick) std::copy(e->stops_host.begin(), e->stops_host.begin() + B, stop_tick);
-    if (reason) std::copy(e->stops_host.begin() + B, e->stops_host.end(), reason);
-    if (samples) *samples = (int32_t)S;
-    return NB_OK;
+    return run_sampled(e, nsteps, nmax, every, watch ? WATCH_EXPLOSION : WATCH_NONE, kinetic, potential, capacity, on_device,
+                       samples, stop_tick, reason, nullptr, nullptr);
 }
 
 // the detector's kernel alone on the resident state: one launch, one copy-out, one wait
@@ -591,46 +619,16 @@ int nb_ens_crash_measures(nb_ens *e, const void *prev_pos, int on_device, int32_
     return NB_OK;
 }
 
-// nb_ens_run_members with every tick sampled and the crash-point detector as the watch: the previous positions primed and
-// the members' dt uploaded in front of the launches; stop ticks, kinds, flags and measures read back behind them; one wait
+// nb_ens_run_members with every tick sampled and the crash-point detector as the watch
 int nb_ens_run_crash_watched(nb_ens *e, const int32_t *nsteps, double *kinetic, double *potential, int64_t capacity,
                              int on_device, int32_t *samples, int32_t *stop_tick, int32_t *kind, int32_t *flags, double *measures)
 {
     if (samples) *samples = 0;
     if (int rc = check_steppable(e)) return rc;
-    if (!nsteps) return fail(NB_ERR_INVALID, "null nsteps");
-    const int B = e->cfg.members;
     int32_t nmax = 0;
-    for (int b = 0; b < B; ++b) {
-        if (nsteps[b] < 0) return fail(NB_ERR_INVALID, "nsteps[%d] must be >= 0 (got %d)", b, nsteps[b]);
-        nmax = std::max(nmax, nsteps[b]);
-    }
-    const int64_t S = 1 + (int64_t)nmax;
-    if (capacity < S)
-        return fail(NB_ERR_INVALID, "capacity of %lld samples is below the %lld of %d ticks sampled every tick",
-                    (long long)capacity, (long long)S, nmax);
-    DeviceGuard guard(e->cfg.device);
-    if (int rc = energy_buffers(e, S)) return rc;
-    if (int rc = crash_buffers(e)) return rc;
-    const size_t bytes = 2 * (size_t)B * sizeof(int32_t);
-    if (!e->stops) HIPCHK(hipMalloc((void **)&e->stops, bytes));
-    // stops_host is free to rewrite: every call that uploads it waits before it returns (e->dt: nb_ens_set_params waits too)
-    e->stops_host.assign(2 * (size_t)B, NB_ENS_CRASH_NONE);
-    std::copy(nsteps, nsteps + B, e->stops_host.begin());
-    HIPCHK(hipMemcpyAsync(e->stops, e->stops_host.data(), bytes, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->dt_dev, e->dt.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, e->stream));
-    // a member that is never checked (a budget of 0) reports no flags and measures of 0
-    HIPCHK(hipMemsetAsync(e->crash_out, 0, (size_t)B * (4 * sizeof(double) + sizeof(int32_t)), e->stream));
-    HIPCHK(hipMemcpyAsync(e->prev_pos, e->pos, cnt_nd(e) * el(e), hipMemcpyDeviceToDevice, e->stream));
-    if (int rc = run_train(e, nmax, 1, e->stops, WATCH_CRASH)) return rc;
-    HIPCHK(hipMemcpyAsync(e->stops_host.data(), e->stops, bytes, hipMemcpyDeviceToHost, e->stream));
-    if (int rc = crash_out_async(e)) return rc;
-    if (int rc = history_out(e, S, kinetic, potential, on_device)) return rc;      // (waits)
-    if (stop_tick) std::copy(e->stops_host.begin(), e->stops_host.begin() + B, stop_tick);
-    if (kind) std::copy(e->stops_host.begin() + B, e->stops_host.end(), kind);
-    crash_results(e, flags, measures);
-    if (samples) *samples = (int32_t)S;
-    return NB_OK;
+    if (int rc = check_budgets(e, nsteps, &nmax)) return rc;
+    return run_sampled(e, nsteps, nmax, 1, WATCH_CRASH, kinetic, potential, capacity, on_device, samples, stop_tick, kind, flags,
+                       measures);
 }
 
 // the diagnostics of every member from the resident state: one launch, two copies, one wait

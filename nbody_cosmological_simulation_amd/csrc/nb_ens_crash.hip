@@ -5,7 +5,7 @@
 // whether it has "crashed": eight whole-array reductions read back one by one and six criteria in a fixed order, two of
 // them about the motion since the previous tick.  Here the reductions and the decision are made on the device for every
 // member, behind the two energy launches of the tick, and the answer is a write to the member's entry of the stop array that
-// every later launch of the tick path reads (nb_ensemble.hip): the host never looks.
+// every later launch of the tick path reads (nb_device.h): the host never looks.
 //
 //   ens_crash_kernel<T, D>   grid (members), one workgroup of 256 threads per member.  Every thread walks the member's stars
 //       with stride 256: D positions, D previous positions, D velocities.  It keeps a NaN and an Inf flag (exponent and
@@ -27,36 +27,14 @@
 //
 // The kernel boundary is the only synchronisation: the energies were written by the launch in front, and the launches
 // behind this one read the stop it writes.
+#include "nb_device.h"
 #include "nb_dispatch.h"
-#include "nb_internal.h"
 
 namespace {
 
+using namespace nbdev;
+
 constexpr int EC_THREADS = 256, EC_WAVES = EC_THREADS / 64;
-
-__device__ __forceinline__ void classify(float x, bool &nan, bool &inf)
-{
-    const unsigned int u = __float_as_uint(x);
-    if ((u & 0x7f800000u) == 0x7f800000u) {
-        if (u & 0x007fffffu) nan = true; else inf = true;
-    }
-}
-__device__ __forceinline__ void classify(double x, bool &nan, bool &inf)
-{
-    const unsigned int hi = (unsigned int)__double2hiint(x);
-    if ((hi & 0x7ff00000u) == 0x7ff00000u) {
-        if ((hi & 0x000fffffu) | (unsigned int)__double2loint(x)) nan = true; else inf = true;
-    }
-}
-
-// never contracted, whatever the build's flags
-__device__ __forceinline__ float mul_rn(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ double mul_rn(double a, double b) { return __dmul_rn(a, b); }
-__device__ __forceinline__ float add_rn(float a, float b) { return __fadd_rn(a, b); }
-__device__ __forceinline__ double add_rn(double a, double b) { return __dadd_rn(a, b); }
-// (as nb_metrics.hip: sqrtf carries the fix-up to correct rounding, __fsqrt_rn is the bare 1-ulp instruction here)
-__device__ __forceinline__ float sqrt_rn(float x) { return __builtin_sqrtf(x); }
-__device__ __forceinline__ double sqrt_rn(double x) { return __dsqrt_rn(x); }
 
 template <typename T, int D>
 __device__ __forceinline__ T norm2(const T (&c)[D])
@@ -89,7 +67,7 @@ ens_crash_kernel(const T *__restrict__ pos, T *prev, const T *__restrict__ vel, 
     __shared__ int s_flag[EC_WAVES];
     const int b = blockIdx.x;                        // member: uniform per workgroup
     const bool watch = stop != nullptr;
-    if (watch && (stop[b] < t || kind[b] != NB_ENS_CRASH_NONE)) return;
+    if (watch && !ens_still_running(stop, kind, b, t)) return;
     const size_t o = (size_t)b * n * D;
     bool nan = false, inf = false;
     T m_disp2 = 0, m_absv = 0, m_speed2 = 0, m_rad2 = 0;

@@ -24,14 +24,6 @@ namespace {
 
 using namespace nbdev;
 
-// the per-member scalars nb_ens_api.cpp uploads (same layout as in nb_ensemble.hip)
-template <typename T>
-struct EnsScalars {
-    T G, eps2, half_dt, dt;
-};
-static_assert(sizeof(EnsScalars<double>) == NB_ENS_PARAM_WORDS * 8 && sizeof(EnsScalars<float>) == NB_ENS_PARAM_WORDS * 4,
-              "the host fills NB_ENS_PARAM_WORDS elements per member");
-
 constexpr int EE_TILE = NB_ENS_ENERGY_TILE;      // stars per tile = threads per workgroup
 constexpr int EE_WAVES = EE_TILE / 64;
 

@@ -15,7 +15,7 @@
 //            order), enc = (A)prefix, escape test
 //         7  one wave per bin (b = wave, wave + waves, ...): fp64 sum of the bin's vt and its count, lanes strided
 //            over the stars, then a fixed butterfly
-//       Keys are the bit patterns, NaN -> all-ones (KeyOf in nb_metrics.hip).  Padding up to P carries all-ones keys and
+//       Keys are the bit patterns, NaN -> all-ones (KeyOf, nb_device.h).  Padding up to P carries all-ones keys and
 //       indices >= N: it sorts after every NaN star and is never read as a star (positions >= N are skipped).
 //       vt, |v| and the bin index of every star cross threads through the member's slice of a global scratch buffer
 //       (written before a workgroup barrier, read after it); nothing else leaves the workgroup until the outputs.
@@ -27,44 +27,16 @@
 //   ens_metrics_kernel<float, 3>    VGPRs 74   static LDS 1160 B   scratch 0   occupancy 6
 //   ens_metrics_kernel<double, 2>   VGPRs 96   static LDS 1160 B   scratch 0   occupancy 5
 //   ens_metrics_kernel<double, 3>   VGPRs 96   static LDS 1160 B   scratch 0   occupancy 5
+#include "nb_device.h"
 #include "nb_dispatch.h"
-#include "nb_internal.h"
 
 namespace {
+
+using namespace nbdev;
 
 constexpr int EM_MAX_THREADS = 1024;
 constexpr int EM_WAVES = EM_MAX_THREADS / 64;
 constexpr int EM_SPT = 4;                        // stars (and sorted positions) per thread, at most
-
-// the per-member scalars nb_ens_api.cpp uploads (same layout as in nb_ensemble.hip)
-template <typename T>
-struct EnsScalars {
-    T G, eps2, half_dt, dt;
-};
-static_assert(sizeof(EnsScalars<double>) == NB_ENS_PARAM_WORDS * 8 && sizeof(EnsScalars<float>) == NB_ENS_PARAM_WORDS * 4,
-              "the host fills NB_ENS_PARAM_WORDS elements per member");
-
-template <typename A> __device__ __forceinline__ A sqrt_rn(A x);
-// (as nb_metrics.hip: sqrtf carries the fix-up to correct rounding, __fsqrt_rn is the bare 1-ulp instruction here)
-template <> __device__ __forceinline__ float sqrt_rn<float>(float x) { return __builtin_sqrtf(x); }
-template <> __device__ __forceinline__ double sqrt_rn<double>(double x) { return __dsqrt_rn(x); }
-template <typename A> __device__ __forceinline__ A div_rn(A a, A b);
-template <> __device__ __forceinline__ float div_rn<float>(float a, float b) { return __fdiv_rn(a, b); }
-template <> __device__ __forceinline__ double div_rn<double>(double a, double b) { return __ddiv_rn(a, b); }
-
-// sort keys: radii are >= +0 or NaN, so their bit patterns order like the values; NaN goes last
-template <typename A> struct KeyOf;
-template <> struct KeyOf<float> {
-    typedef unsigned type;
-    static __device__ __forceinline__ unsigned make(float x) { return x != x ? 0xffffffffu : __float_as_uint(x); }
-    static __device__ __forceinline__ float back(unsigned k) { return __uint_as_float(k); }   // all-ones is a NaN
-};
-template <> struct KeyOf<double> {
-    typedef unsigned long long type;
-    static __device__ __forceinline__ unsigned long long make(double x)
-    { return x != x ? ~0ull : (unsigned long long)__double_as_longlong(x); }
-    static __device__ __forceinline__ double back(unsigned long long k) { return __longlong_as_double((long long)k); }
-};
 
 struct SumOp {
     static __device__ __forceinline__ double apply(double a, double b) { return a + b; }

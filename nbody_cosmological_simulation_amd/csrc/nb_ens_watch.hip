@@ -3,7 +3,7 @@
 // The reference's stability sweep (stability_test.py:94-105) steps a system check_interval ticks, then asks
 // detect_explosion (:34-61) whether it has "exploded", and stops it there.  Here that question is answered on the device for
 // every member at every sampled tick, behind the two energy launches of the tick, and the answer is a write to the member's
-// entry of the stop array that every later launch of the tick path reads (nb_ensemble.hip): the host never looks.
+// entry of the stop array that every later launch of the tick path reads (nb_device.h): the host never looks.
 //
 //   ens_watch_kernel   grid (members), one workgroup per member.  A member that has stopped before this tick, or was
 //       halted, is skipped.  The others scan their n * D positions and velocities for a non-finite value (all exponent bits
@@ -13,15 +13,14 @@
 //
 // The kernel boundary is the only synchronisation: the energies were written by the launch in front, and the launches
 // behind this one read the stop it writes.
+#include "nb_device.h"
 #include "nb_dispatch.h"
-#include "nb_internal.h"
 
 namespace {
 
-constexpr int EW_THREADS = 256;
+using namespace nbdev;
 
-__device__ __forceinline__ bool non_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
-__device__ __forceinline__ bool non_finite(double x) { return ((unsigned int)__double2hiint(x) & 0x7ff00000u) == 0x7ff00000u; }
+constexpr int EW_THREADS = 256;
 
 template <typename T>
 __global__ void __launch_bounds__(EW_THREADS)
@@ -31,7 +30,7 @@ ens_watch_kernel(const T *__restrict__ pos, const T *__restrict__ vel, int count
 {
     __shared__ int s_bad[EW_THREADS / 64];
     const int b = blockIdx.x;                        // member: uniform per workgroup
-    if (stop[b] < t || reason[b] != 0) return;
+    if (!ens_still_running(stop, reason, b, t)) return;
     const size_t o = (size_t)b * count;
     bool bad = false;
     for (int k = threadIdx.x; k < count; k += EW_THREADS) {

@@ -10,16 +10,8 @@
 // (ens_grid_step_kernel); their max-r2 + tables launch is ens_r2max_tables_kernel (nb_force.hip) and the INT8 / INT4 force
 // snap ens_force_quant_finish_kernel (nb_misc.hip).
 //
-// Per-member stops (nb_ens_run_members): every kernel of the tick path takes `stop` (device, one int per member, or null:
-// no member ever stops) and the launch's tick index t = ticks the call has already closed.  The kernels come in two
-// instantiations, STOPS = false for a launch without the array: its code is what it was before there were stops.  (One
-// kernel with a run-time null test was measured first, N = 1024 on an MI355X: the test sits in front of the loads of the
-// other kernel arguments, a scalar-memory round trip of its own in every launch, +0.3 to +0.9 us per launch.)  With
-// STOPS a workgroup reads its member's stop once: left = stop[b] - t ticks are still the member's.  left <= 0: the member is done and the workgroup
-// returns; left == 1: this launch closes the member's last tick, so it gets NB_KICK_CLOSE whatever the launch's mode is;
-// else the launch's own mode.  Where the positions ping-pong, a member on its last tick (left == 1) or just stopped
-// (left == 0: budget 0, or halted by the watch kernel behind the previous launch) also gets its positions carried into
-// the second buffer, bit for bit, so that both buffers hold a stopped member's final positions whatever the host swaps later.
+// Per-member stops (nb_ens_run_members): every kernel of the tick path takes `stop` and the launch's tick index t and comes
+// in two instantiations, with and without the array; nb_device.h states the rule and implements it (ens_ticks_left).
 #include "nb_dispatch.h"
 #include "nb_small_body.h"
 #include "nb_internal.h"
@@ -27,14 +19,6 @@
 namespace {
 
 using namespace nbdev;
-
-// scalars of one member, already cast to T on the host as nb_launch_small_step casts the solo step's
-template <typename T>
-struct EnsScalars {
-    T G, eps2, half_dt, dt;
-};
-static_assert(sizeof(EnsScalars<double>) == NB_ENS_PARAM_WORDS * 8 && sizeof(EnsScalars<float>) == NB_ENS_PARAM_WORDS * 4,
-              "the host fills NB_ENS_PARAM_WORDS elements per member");
 
 // a stopped member's positions into the second buffer: this workgroup's own targets, nobody else writes or reads them there
 template <typename T, int D, int S, int BS>
@@ -54,13 +38,11 @@ ens_step_kernel(const T *__restrict__ pos_in, T *__restrict__ pos_out, T *__rest
     const int b = blockIdx.y;                        // member: uniform per workgroup
     const EnsScalars<T> p = prm[b];
     const size_t o = (size_t)b * n;
-    if constexpr (STOPS) {
-        const int left = stop[b] - t;
-        if (left <= 1) {
-            ens_carry_positions<T, D, S, BS>(pos_in + o * D, pos_out + o * D, n);
-            if (left <= 0) return;
-            if (do_kick != NB_KICK_NONE) do_kick = NB_KICK_CLOSE;
-        }
+    const int left = ens_ticks_left<STOPS>(stop, b, t);
+    if (STOPS && left <= 1) {
+        ens_carry_positions<T, D, S, BS>(pos_in + o * D, pos_out + o * D, n);
+        if (left <= 0) return;
+        do_kick = ens_kick_mode(left, do_kick);
     }
     small_step_body<T, D, HOOK, S, BS>(blockIdx.x, pos_in + o * D, pos_out + o * D, vel + o * D, acc + o * D, mass + o, n,
                                        p.G, p.eps2, p.half_dt, p.dt, do_kick, nullptr);
@@ -78,13 +60,11 @@ ens_grid_step_kernel(const float *__restrict__ pos_in, float *__restrict__ pos_o
     const int b = blockIdx.y;
     const EnsScalars<float> p = prm[b];
     const size_t o = (size_t)b * n;
-    if constexpr (STOPS) {
-        const int left = stop[b] - t;
-        if (left <= 1) {
-            if (!part) ens_carry_positions<float, D, S, BS>(pos_in + o * D, pos_out + o * D, n);   // (INT8 / INT4: no ping-pong)
-            if (left <= 0) return;
-            if (do_kick != NB_KICK_NONE) do_kick = NB_KICK_CLOSE;
-        }
+    const int left = ens_ticks_left<STOPS>(stop, b, t);
+    if (STOPS && left <= 1) {
+        if (!part) ens_carry_positions<float, D, S, BS>(pos_in + o * D, pos_out + o * D, n);   // (INT8 / INT4: no ping-pong)
+        if (left <= 0) return;
+        do_kick = ens_kick_mode(left, do_kick);
     }
     small_grid_body<D, S, false, BS>(blockIdx.x, pos_in + o * D, pos_out + o * D, vel + o * D, acc + o * D, mass + o, n, p.G,
                                      p.eps2, p.half_dt, p.dt, do_kick, tabs + b,
@@ -99,14 +79,13 @@ ens_kick_drift_kernel(T *__restrict__ pos, T *__restrict__ vel, const T *__restr
                       const EnsScalars<T> *__restrict__ prm, const int *__restrict__ stop, int t)
 {
     const int b = blockIdx.y;
-    if constexpr (STOPS)
-        if (stop[b] - t <= 0) return;                // the member opens no further tick
+    if (ens_ticks_left<STOPS>(stop, b, t) <= 0) return;      // the member opens no further tick
     const T half_dt = prm[b].half_dt, dt = prm[b].dt;
     const size_t o = (size_t)b * count;
     for (int k = blockIdx.x * EK_BLOCK + threadIdx.x; k < count; k += gridDim.x * EK_BLOCK) {
-        const T v = axpy_sep<T>(vel[o + k], acc[o + k], half_dt);
+        const T v = axpy_rn<T>(vel[o + k], acc[o + k], half_dt);
         vel[o + k] = v;
-        pos[o + k] = axpy_sep<T>(pos[o + k], v, dt);
+        pos[o + k] = axpy_rn<T>(pos[o + k], v, dt);
     }
 }
 

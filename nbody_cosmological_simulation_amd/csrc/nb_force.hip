@@ -959,15 +959,15 @@ grid_quantize_safe_tab_kernel(const float *__restrict__ in, float *__restrict__ 
 // Small systems (one launch instead of two per grid evaluation): every workgroup adds its part of the all-pairs
 // maximum; the LAST one to arrive (device-scope counter) reads the finished maximum and builds the tables.
 constexpr int NB_R2MAX_SPLIT = 8;
-template <int D, int R>
-__global__ void __launch_bounds__(NB_BLOCK)
-r2max_tables_kernel(const float *__restrict__ pos, ForceGeom g, float eps2, GridTables *__restrict__ tab, int levels,
-                    float G, float min_val, int allow_fast)
+
+// behind r2max_block, shared by the solo and the batched kernel: count this workgroup's arrival at *tab; the last of
+// `gridDim.x * gridDim.y` builds the tables from the finished maximum, the others return (*levels is read by the last only)
+__device__ __forceinline__ void r2max_last_builds_tables(GridTables *tab, const int *levels, float G, float eps2,
+                                                         float min_val, int allow_fast)
 {
     static_assert(NB_BLOCK == NB_LUT_MIN, "the last workgroup runs the single-block tables code");
     __shared__ unsigned int s_bits;
     __shared__ int s_mine;
-    r2max_block<D, R, NB_R2MAX_SPLIT>(pos, g, eps2, tab);
     if (threadIdx.x == 0) {
         __threadfence();
         const unsigned int total = gridDim.x * gridDim.y;
@@ -977,41 +977,37 @@ r2max_tables_kernel(const float *__restrict__ pos, ForceGeom g, float eps2, Grid
     }
     __syncthreads();
     if (!s_mine) return;
-    grid_tables_body<true>(tab, levels, G, eps2, min_val, nullptr, allow_fast, s_bits);
+    grid_tables_body<true>(tab, *levels, G, eps2, min_val, nullptr, allow_fast, s_bits);
+}
+
+template <int D, int R>
+__global__ void __launch_bounds__(NB_BLOCK)
+r2max_tables_kernel(const float *__restrict__ pos, ForceGeom g, float eps2, GridTables *__restrict__ tab, int levels,
+                    float G, float min_val, int allow_fast)
+{
+    r2max_block<D, R, NB_R2MAX_SPLIT>(pos, g, eps2, tab);
+    r2max_last_builds_tables(tab, &levels, G, eps2, min_val, allow_fast);
 }
 
 // The same for the B members of an ensemble (nb_ens handles) in one launch: blockIdx.z is the member, blockIdx.x / .y its
 // target block and source chunk as above, on the member's slice of the (B, N, D) positions.  Every member has its own
-// GridTables (maximum, arrival counter, tables), its own eps2 and G (prm: NB_ENS_PARAM_WORDS floats per member =
-// {G, eps2, dt / 2, dt}) and level count; the last workgroup OF A MEMBER to arrive builds that member's tables.  The maximum
-// is exact and the tables a function of it alone (grid_tables_body), so they are the tables a solo evaluation of the member
-// builds, however its workgroups were cut.  No workgroup waits for another.  All workgroups of a stopped member return
-// together (the test is on the member), so its arrival counter stays at rest.
+// GridTables (maximum, arrival counter, tables), its own eps2 and G (prm) and level count; the last workgroup OF A MEMBER to
+// arrive builds that member's tables.  The maximum is exact and the tables a function of it alone (grid_tables_body), so
+// they are the tables a solo evaluation of the member builds, however its workgroups were cut.  No workgroup waits for
+// another.  A stopped member (nb_device.h) takes no further evaluation, its tables stay its last one's; all its workgroups
+// return together (the test is on the member), so its arrival counter stays at rest.
 template <int D, bool STOPS>
 __global__ void __launch_bounds__(NB_BLOCK)
-ens_r2max_tables_kernel(const float *__restrict__ pos, ForceGeom g, const float *__restrict__ prm, GridTables *__restrict__ tabs,
-                        const int *__restrict__ levels, float min_val, int allow_fast, const int *__restrict__ stop, int t)
+ens_r2max_tables_kernel(const float *__restrict__ pos, ForceGeom g, const EnsScalars<float> *__restrict__ prm,
+                        GridTables *__restrict__ tabs, const int *__restrict__ levels, float min_val, int allow_fast,
+                        const int *__restrict__ stop, int t)
 {
-    static_assert(NB_BLOCK == NB_LUT_MIN, "the last workgroup runs the single-block tables code");
-    __shared__ unsigned int s_bits;
-    __shared__ int s_mine;
     const int b = blockIdx.z;
-    // a stopped member (nb_ensemble.hip: stop[b] - t ticks left; STOPS = false: no array, the code without stops) takes no
-    // further evaluation: its tables stay its last one's
-    if constexpr (STOPS)
-        if (stop[b] - t <= 0) return;
+    if (ens_ticks_left<STOPS>(stop, b, t) <= 0) return;
     GridTables *tab = tabs + b;
-    const float G = prm[b * NB_ENS_PARAM_WORDS], eps2 = prm[b * NB_ENS_PARAM_WORDS + 1];
+    const float G = prm[b].G, eps2 = prm[b].eps2;
     r2max_block<D, 1, NB_R2MAX_SPLIT>(pos + (size_t)b * g.n * D, g, eps2, tab);
-    if (threadIdx.x == 0) {
-        __threadfence();
-        const unsigned int total = gridDim.x * gridDim.y;
-        s_mine = (atomicAdd(&tab->blocks_done, 1u) == total - 1) ? 1 : 0;
-        s_bits = s_mine ? atomicMax(&tab->r2max_bits, 0u) : 0u;
-    }
-    __syncthreads();
-    if (!s_mine) return;
-    grid_tables_body<true>(tab, levels[b], G, eps2, min_val, nullptr, allow_fast, s_bits);
+    r2max_last_builds_tables(tab, levels + b, G, eps2, min_val, allow_fast);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1350,8 +1346,8 @@ hipError_t nb_launch_ens_r2max_tables(const float *pos, int members, int n, int 
     const dim3 grid(gx, g.nchunks, members);
     return nb::pick<2, 3>(dim, [&](auto D) {
         return nb::pick_bool(stop != nullptr, [&](auto ST) {
-            hipLaunchKernelGGL((ens_r2max_tables_kernel<D.value, ST.value>), grid, dim3(NB_BLOCK), 0, st, pos, g, (const float *)prm,
-                               tabs, levels, min_val, allow_fast, stop, t);
+            hipLaunchKernelGGL((ens_r2max_tables_kernel<D.value, ST.value>), grid, dim3(NB_BLOCK), 0, st, pos, g,
+                               (const EnsScalars<float> *)prm, tabs, levels, min_val, allow_fast, stop, t);
             return hipGetLastError();
         });
     });

@@ -31,9 +31,6 @@ namespace {
 // y0^3 underflows to exactly 0 (fp64: r2 ~ 1e300, y0^3 ~ 1e-450; fp32: r2 ~ 1e36, y0^3 ~ 1e-54), so
 // they contribute exactly nothing whatever their mass; in grid modes they fall into the last bin and
 // carry mass 0.  (fp32 pair arithmetic on fp64 storage: pad = 1e18, contributions ~1e-37, absorbed.)
-template <typename T> __device__ __forceinline__ T axpy_rn(T a, T b, T s);
-template <> __device__ __forceinline__ double axpy_rn<double>(double a, double b, double s) { return __dadd_rn(a, __dmul_rn(b, s)); }
-template <> __device__ __forceinline__ float axpy_rn<float>(float a, float b, float s) { return __fadd_rn(a, __fmul_rn(b, s)); }
 
 // x, y, (z), mass factor as padded component arrays; with KICK the opening half of a step rides
 // along: v += a*(dt/2); x += v*dt (simulation.py:132,135, separate mul/add roundings like torch).

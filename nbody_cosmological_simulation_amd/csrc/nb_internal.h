@@ -312,15 +312,20 @@ hipError_t nb_launch_small_step(const void *pos_in, void *pos_out, void *vel, vo
                                 unsigned long long *bin_out = nullptr /* HOOK_GRID: bin read-out (BINS instantiation) */);
 // ---- many small systems per launch (nb_ensemble.hip; host side nb_ens_api.cpp) -----------------------------------------
 // `members` systems of n particles in contiguous (members, n, dim) / (members, n) buffers of the storage type; prm: device,
-// NB_ENS_PARAM_WORDS elements of the storage type per member = {G, eps2, dt / 2, dt}, cast on the host exactly as
-// nb_launch_small_step casts the solo step's.  The body is the solo step's (nb_small_body.h), picked by
-// nb_small_block(n) and `lanes` as there; do_kick: NB_KICK_NONE / CLOSE / CLOSE_OPEN.
+// one EnsScalars of the storage type per member, cast on the host exactly as nb_launch_small_step casts the solo step's.
+// The body is the solo step's (nb_small_body.h), picked by nb_small_block(n) and `lanes` as there; do_kick: NB_KICK_NONE /
+// CLOSE / CLOSE_OPEN.
 // stop / t, on every launch of the tick path (nb_ens_run_members): stop is null (no member ever stops: the kernels'
 // instantiation without stops is launched) or device, one int
 // per member = the tick of the call at which the member stops; t = ticks the call has closed before this launch.  Member b
 // has stop[b] - t ticks left: none -> its workgroups return, one -> it only closes (NB_KICK_CLOSE) whatever do_kick says;
-// nb_ensemble.hip has the rule and what it does to the second position buffer.
-constexpr int NB_ENS_PARAM_WORDS = 4;
+// nb_device.h has the rule and what it does to the second position buffer.
+template <typename T>
+struct EnsScalars {                 // the scalars of one member: the ONE declaration, filled by nb_ens_api.cpp's upload_params
+    T G, eps2, half_dt, dt;
+};
+static_assert(sizeof(EnsScalars<double>) == 4 * sizeof(double) && sizeof(EnsScalars<float>) == 4 * sizeof(float),
+              "the device array is dense: one record per member, no padding");
 constexpr int NB_ENS_MAX_MEMBERS = 1024;
 hipError_t nb_launch_ens_step(const void *pos_in, void *pos_out, void *vel, void *acc, const void *mass, int members, int n,
                               int dim, int is_f64, int hook, const void *prm, int do_kick, int lanes, const int *stop, int t,
@@ -379,7 +384,7 @@ hipError_t nb_launch_ens_energy(const void *pos, const void *vel, const void *ma
 struct NbEnsMetricsArgs {
     const void *pos, *vel, *mass;   // device
     int members, n, dim, is_f64;
-    const void *prm;                // device, NB_ENS_PARAM_WORDS elements of the storage type per member
+    const void *prm;                // device, one EnsScalars of the storage type per member
     const double *max_radius;       // device, `members` entries (>= 0 or NaN), or null: each member's own radii.max()
     int num_bins;                   // rotation-curve bins (<= 255)
     int kth;                        // order statistic of the radii to report (min(int(N p / 100), N - 1))

@@ -13,21 +13,15 @@
 // keep index order.  Bin sums are added in a fixed order (one workgroup per bin), in fp64.  Per-particle arithmetic
 // follows torch op by op in the state's LOGICAL dtype A (fp32 state tensors: fp32 products, sums, sqrt, divide -- no
 // fma), so that bin membership and the escape test take the decisions the reference takes.
+#include "nb_device.h"
 #include "nb_dispatch.h"
-#include "nb_internal.h"
 
 namespace {
 
+using namespace nbdev;
+
 constexpr int MB = 256;              // threads per block
 constexpr int M_PART_BLOCKS = 256;   // stage-1 blocks of the O(N) reductions
-
-template <typename A> __device__ __forceinline__ A sqrt_rn(A x);
-// (__fsqrt_rn compiles to the bare v_sqrt_f32 -- 1 ulp -- on this toolchain; sqrtf carries the fix-up to correct rounding)
-template <> __device__ __forceinline__ float sqrt_rn<float>(float x) { return __builtin_sqrtf(x); }
-template <> __device__ __forceinline__ double sqrt_rn<double>(double x) { return __dsqrt_rn(x); }
-template <typename A> __device__ __forceinline__ A div_rn(A a, A b);
-template <> __device__ __forceinline__ float div_rn<float>(float a, float b) { return __fdiv_rn(a, b); }
-template <> __device__ __forceinline__ double div_rn<double>(double a, double b) { return __ddiv_rn(a, b); }
 
 // fixed-order block sum / max of doubles
 __device__ __forceinline__ double block_sum(double v, double *s)
@@ -147,20 +141,6 @@ metrics_finish_sums_kernel(const double *__restrict__ part, int nblocks, int n, 
         }
     }
 }
-
-// Sort keys: radii are >= +0 or NaN, so their bit patterns order like the values; NaN goes last (torch.sort's rule).
-template <typename A> struct KeyOf;
-template <> struct KeyOf<float> {
-    typedef unsigned type;
-    static __device__ __forceinline__ unsigned make(float x) { return x != x ? 0xffffffffu : __float_as_uint(x); }
-    static __device__ __forceinline__ float back(unsigned k) { return __uint_as_float(k); }   // all-ones is a NaN
-};
-template <> struct KeyOf<double> {
-    typedef unsigned long long type;
-    static __device__ __forceinline__ unsigned long long make(double x)
-    { return x != x ? ~0ull : (unsigned long long)__double_as_longlong(x); }
-    static __device__ __forceinline__ double back(unsigned long long k) { return __longlong_as_double((long long)k); }
-};
 
 // K3: distance from the centre of mass; sort keys of r and r_com; identity permutation
 template <typename S, typename A, int D>

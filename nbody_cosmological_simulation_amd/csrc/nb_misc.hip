@@ -8,6 +8,8 @@
 
 namespace {
 
+using namespace nbdev;
+
 constexpr int EW_BLOCK = 256;
 
 inline int ew_grid(int64_t count, int per_thread = 1)
@@ -17,11 +19,6 @@ inline int ew_grid(int64_t count, int per_thread = 1)
     if (b > 2048 * 8) b = 2048 * 8;
     return (int)b;
 }
-
-// torch semantics: `a + b * s` is two rounded operations (no fused multiply-add), with the
-// Python scalar cast to the tensor dtype first.
-__device__ __forceinline__ float axpy1(float a, float b, float s) { return __fadd_rn(a, __fmul_rn(b, s)); }
-__device__ __forceinline__ double axpy1(double a, double b, double s) { return __dadd_rn(a, __dmul_rn(b, s)); }
 
 // acc = sum_s partial[s] (fixed order -> reproducible); optional closing half kick v += a*h
 template <typename T>
@@ -36,14 +33,14 @@ reduce_kernel(const double *__restrict__ partial, int nchunks, int64_t count, T 
         const T a = (T)s;
         acc[idx] = a;
         if (do_kick == NB_KICK_CLOSE) {
-            vel[idx] = axpy1(vel[idx], a, half_dt);
+            vel[idx] = axpy_rn(vel[idx], a, half_dt);
         } else if (do_kick == NB_KICK_CLOSE_OPEN) {
             // closing kick of this step and the opening kick + drift of the next one (simulation.py:141,
             // then :132,:135 of the following step()): the same operations the separate launches perform
-            T v = axpy1(vel[idx], a, half_dt);
-            v = axpy1(v, a, half_dt);
+            T v = axpy_rn(vel[idx], a, half_dt);
+            v = axpy_rn(v, a, half_dt);
             vel[idx] = v;
-            pos[idx] = axpy1(pos[idx], v, dt);
+            pos[idx] = axpy_rn(pos[idx], v, dt);
         }
     }
 }
@@ -54,7 +51,7 @@ axpy_kernel(T *__restrict__ y, const T *__restrict__ x, T s, int64_t count)
 {
     for (int64_t idx = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; idx < count;
          idx += (int64_t)gridDim.x * EW_BLOCK)
-        y[idx] = axpy1(y[idx], x[idx], s);
+        y[idx] = axpy_rn(y[idx], x[idx], s);
 }
 
 // v += a*(dt/2); x += v*dt   (simulation.py:132,135)
@@ -65,9 +62,9 @@ kick_drift_kernel(T *__restrict__ pos, T *__restrict__ vel, const T *__restrict_
 {
     for (int64_t idx = (int64_t)blockIdx.x * EW_BLOCK + threadIdx.x; idx < count;
          idx += (int64_t)gridDim.x * EW_BLOCK) {
-        const T v = axpy1(vel[idx], acc[idx], half_dt);
+        const T v = axpy_rn(vel[idx], acc[idx], half_dt);
         vel[idx] = v;
-        pos[idx] = axpy1(pos[idx], v, dt);
+        pos[idx] = axpy_rn(pos[idx], v, dt);
     }
 }
 
@@ -90,7 +87,7 @@ kick_a32_kernel(double *__restrict__ pos, double *__restrict__ vel, const double
         if (DRIFT) {
             double x;
             if (v64) {
-                x = axpy1(pos[idx], v, dt);
+                x = axpy_rn(pos[idx], v, dt);
             } else {
                 const float u = __fmul_rn((float)v, ds);
                 x = p64 ? __dadd_rn(pos[idx], (double)u) : (double)__fadd_rn((float)pos[idx], u);
@@ -249,11 +246,15 @@ grid_quantize_kernel(const T *in, T *out /* may alias in */, int64_t count, int 
 // folds the stage-1 min/max partials itself (min/max are exact, so every block gets the same bounds), then
 // quantises its elements; optionally the closing half kick (simulation.py:141) and the next step's opening kick +
 // drift (:132,:135) ride along -- the same operations the separate launches perform.
-__global__ void __launch_bounds__(256)
-force_quant_finish_kernel(float *__restrict__ acc, int64_t count, int levels, const double *__restrict__ partials,
-                          int nblocks, double *__restrict__ mn_mx, int16_t *__restrict__ bins, float *__restrict__ vel,
-                          float *__restrict__ pos, float half_dt, float dt, int kick, float *__restrict__ packed, int np,
-                          int dim)
+struct ForceGrid {
+    float mn, range, lm1;
+    bool passthrough;
+};
+
+// the fold, shared by the solo and the batched kernel: `nblocks` {min, max} pairs -> the linear grid of `levels` values;
+// block 0 (blockIdx.x) also leaves {min, max} in out[0 .. 1]
+__device__ __forceinline__ ForceGrid force_grid_from_partials(const double *__restrict__ partials, int nblocks, int levels,
+                                                              double *__restrict__ out)
 {
     __shared__ double s_mn[4], s_mx[4];
     __shared__ double s_out[2];
@@ -266,24 +267,32 @@ force_quant_finish_kernel(float *__restrict__ acc, int64_t count, int levels, co
     if (threadIdx.x == 0) {
         s_out[0] = dmn;
         s_out[1] = dmx;
-        if (blockIdx.x == 0) { mn_mx[0] = dmn; mn_mx[1] = dmx; }
+        if (blockIdx.x == 0) { out[0] = dmn; out[1] = dmx; }
     }
     __syncthreads();
     const float mn = (float)s_out[0], mx = (float)s_out[1];
     const float range = __fsub_rn(mx, mn);
-    const bool passthrough = range < 1e-10f;
-    const float lm1 = (float)(levels - 1);
+    return {mn, range, (float)(levels - 1), range < 1e-10f};
+}
+
+__global__ void __launch_bounds__(256)
+force_quant_finish_kernel(float *__restrict__ acc, int64_t count, int levels, const double *__restrict__ partials,
+                          int nblocks, double *__restrict__ mn_mx, int16_t *__restrict__ bins, float *__restrict__ vel,
+                          float *__restrict__ pos, float half_dt, float dt, int kick, float *__restrict__ packed, int np,
+                          int dim)
+{
+    const ForceGrid g = force_grid_from_partials(partials, nblocks, levels, mn_mx);
     for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < count; idx += (int64_t)gridDim.x * 256) {
         int b = -1;
         float a = acc[idx];
-        if (!passthrough) a = lin_quant<float>(a, mn, range, lm1, &b);
+        if (!g.passthrough) a = lin_quant<float>(a, g.mn, g.range, g.lm1, &b);
         acc[idx] = a;
         if (bins) bins[idx] = (int16_t)b;
         if (kick != NB_KICK_NONE) {
-            float v = axpy1(vel[idx], a, half_dt);
+            float v = axpy_rn(vel[idx], a, half_dt);
             if (kick == NB_KICK_CLOSE_OPEN) {
-                v = axpy1(v, a, half_dt);
-                const float x = axpy1(pos[idx], v, dt);
+                v = axpy_rn(v, a, half_dt);
+                const float x = axpy_rn(pos[idx], v, dt);
                 pos[idx] = x;
                 // pair-symmetric path: the next evaluation's packed positions (component arrays) in the same pass
                 if (packed) packed[(size_t)(idx % dim) * np + idx / dim] = x;
@@ -295,53 +304,32 @@ force_quant_finish_kernel(float *__restrict__ acc, int64_t count, int levels, co
 
 // The same for the B members of an ensemble (nb_ens handles) in one launch: blockIdx.y is the member.  Every block folds
 // ITS member's nblocks partials (partials: members * nblocks pairs), block 0 of a member leaves {min, max} in
-// bounds[2 b], and the member's count = n * D forces are snapped and kicked with the member's own dt
-// (prm: NB_ENS_PARAM_WORDS floats per member = {G, eps2, (float)(dt / 2), (float)dt}, the casts of the solo launch).
+// bounds[2 b], and the member's count = n * D forces are snapped and kicked with the member's own dt.
+// Per-member stops (nb_device.h): a stopped member keeps its forces, bounds and state; one on its last tick only closes.
 template <bool STOPS>
 __global__ void __launch_bounds__(256)
 ens_force_quant_finish_kernel(float *__restrict__ acc, int count, int levels, const double *__restrict__ partials, int nblocks,
                               double *__restrict__ bounds, float *__restrict__ vel, float *__restrict__ pos,
-                              const float *__restrict__ prm, int kick, const int *__restrict__ stop, int t)
+                              const EnsScalars<float> *__restrict__ prm, int kick, const int *__restrict__ stop, int t)
 {
-    __shared__ double s_mn[4], s_mx[4];
-    __shared__ double s_out[2];
     const int m = blockIdx.y;
-    // per-member stops (nb_ensemble.hip; STOPS = false: no array, the code without stops): a stopped member keeps its
-    // forces, bounds and state; one on its last tick only closes
-    if constexpr (STOPS) {
-        const int left = stop[m] - t;
-        if (left <= 0) return;
-        if (left == 1 && kick != NB_KICK_NONE) kick = NB_KICK_CLOSE;
-    }
-    const double *mine = partials + (size_t)m * 2 * nblocks;
-    double dmn = __builtin_inf(), dmx = -__builtin_inf();
-    for (int w = threadIdx.x; w < nblocks; w += 256) {      // one pair per workgroup of the member's force launch
-        dmn = nan_min(dmn, mine[2 * w]);
-        dmx = nan_max(dmx, mine[2 * w + 1]);
-    }
-    minmax_fold<double>(dmn, dmx, s_mn, s_mx);
-    if (threadIdx.x == 0) {
-        s_out[0] = dmn;
-        s_out[1] = dmx;
-        if (blockIdx.x == 0) { bounds[2 * m] = dmn; bounds[2 * m + 1] = dmx; }
-    }
-    __syncthreads();
-    const float mn = (float)s_out[0], mx = (float)s_out[1];
-    const float range = __fsub_rn(mx, mn);
-    const bool passthrough = range < 1e-10f;
-    const float lm1 = (float)(levels - 1);
-    const float half_dt = prm[m * NB_ENS_PARAM_WORDS + 2], dt = prm[m * NB_ENS_PARAM_WORDS + 3];
+    const int left = ens_ticks_left<STOPS>(stop, m, t);
+    if (left <= 0) return;
+    kick = ens_kick_mode(left, kick);
+    // one pair per workgroup of the member's force launch
+    const ForceGrid g = force_grid_from_partials(partials + (size_t)m * 2 * nblocks, nblocks, levels, bounds + 2 * m);
+    const float half_dt = prm[m].half_dt, dt = prm[m].dt;
     const size_t o = (size_t)m * count;
     for (int k = blockIdx.x * 256 + threadIdx.x; k < count; k += gridDim.x * 256) {
         const size_t idx = o + k;
         float a = acc[idx];
-        if (!passthrough) a = lin_quant<float>(a, mn, range, lm1, nullptr);
+        if (!g.passthrough) a = lin_quant<float>(a, g.mn, g.range, g.lm1, nullptr);
         acc[idx] = a;
         if (kick != NB_KICK_NONE) {
-            float v = axpy1(vel[idx], a, half_dt);
+            float v = axpy_rn(vel[idx], a, half_dt);
             if (kick == NB_KICK_CLOSE_OPEN) {
-                v = axpy1(v, a, half_dt);
-                pos[idx] = axpy1(pos[idx], v, dt);
+                v = axpy_rn(v, a, half_dt);
+                pos[idx] = axpy_rn(pos[idx], v, dt);
             }
             vel[idx] = v;
         }
@@ -682,7 +670,7 @@ hipError_t nb_launch_ens_force_quant_finish(float *acc, int members, int count, 
     gx = gx > 2048 ? 2048 : gx;
     return nb::pick_bool(stop != nullptr, [&](auto ST) {
         hipLaunchKernelGGL(ens_force_quant_finish_kernel<ST.value>, dim3(gx, members), dim3(256), 0, st, acc, count, levels, partials,
-                           nblocks, bounds, vel, pos, (const float *)prm, kick, stop, t);
+                           nblocks, bounds, vel, pos, (const EnsScalars<float> *)prm, kick, stop, t);
         return hipGetLastError();
     });
 }

@@ -25,7 +25,7 @@ namespace {
 
 using namespace nbdev;
 
-// the pair loop, butterfly and kicks (and SM_TILE, inv_r3_*, axpy_sep): nb_small_body.h, shared with the batched steps of
+// the pair loop, butterfly and kicks (and SM_TILE, inv_r3_*): nb_small_body.h, shared with the batched steps of
 // nb_ensemble.hip -- small_step_body for the cast hooks, small_grid_body for the grid hook
 
 // do_kick: an NbKick mode, | NB_KICK_OPEN_ON_READ (nb_internal.h); the drifted positions go to pos_out

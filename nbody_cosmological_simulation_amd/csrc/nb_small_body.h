@@ -31,10 +31,6 @@ __device__ __forceinline__ float inv_r3_f(float q)
     return __builtin_fmaf(v * e, 1.5f, v);
 }
 
-template <typename T> __device__ __forceinline__ T axpy_sep(T a, T b, T s);      // a + b*s, two roundings like torch
-template <> __device__ __forceinline__ double axpy_sep<double>(double a, double b, double s) { return __dadd_rn(a, __dmul_rn(b, s)); }
-template <> __device__ __forceinline__ float axpy_sep<float>(float a, float b, float s) { return __fadd_rn(a, __fmul_rn(b, s)); }
-
 // One workgroup of the step: targets [blk * BS / S, (blk + 1) * BS / S) of ONE system of n particles against all of its
 // sources.  The pointers are that system's own arrays ((n, D) row-major; mass (n)); the scalars are already cast to T.
 // do_kick: an NbKick mode, | NB_KICK_OPEN_ON_READ (nb_internal.h); the drifted positions go to pos_out.
@@ -129,18 +125,18 @@ __device__ __forceinline__ void small_step_body(int blk, const T *pos_in, T *pos
             const int kmode = do_kick & NB_KICK_MODE_MASK;
             if (kmode != NB_KICK_NONE) {
                 T v = vel[idx];
-                if (do_kick & NB_KICK_OPEN_ON_READ) v = axpy_sep<T>(v, a_prev, half_dt);     // this step's opening kick, deferred (see below)
-                v = axpy_sep<T>(v, ak, half_dt);                          // closing kick (simulation.py:141)
+                if (do_kick & NB_KICK_OPEN_ON_READ) v = axpy_rn<T>(v, a_prev, half_dt);     // this step's opening kick, deferred (see below)
+                v = axpy_rn<T>(v, ak, half_dt);                          // closing kick (simulation.py:141)
                 if (kmode == NB_KICK_CLOSE_OPEN) {
-                    v = axpy_sep<T>(v, ak, half_dt);                      // next step's opening kick (:132)
-                    pos_out[idx] = axpy_sep<T>(xi[k], v, dt);             // ... and drift (:135)
+                    v = axpy_rn<T>(v, ak, half_dt);                      // next step's opening kick (:132)
+                    pos_out[idx] = axpy_rn<T>(xi[k], v, dt);             // ... and drift (:135)
                 } else if (kmode == NB_KICK_CLOSE_SPEC) {
                     // last step of a native call: velocities stay at the closing kick (what a reader must see), but the
                     // positions the NEXT step would drift to go to pos_out -- if the next nb_step finds the state
                     // untouched it takes them and applies its opening kick here on read (NB_KICK_OPEN_ON_READ): a Python loop of
                     // step() costs one launch per step instead of two
-                    const T vo = axpy_sep<T>(v, ak, half_dt);
-                    pos_out[idx] = axpy_sep<T>(xi[k], vo, dt);
+                    const T vo = axpy_rn<T>(v, ak, half_dt);
+                    pos_out[idx] = axpy_rn<T>(xi[k], vo, dt);
                 }
                 vel[idx] = v;
             }
@@ -341,18 +337,18 @@ __device__ __forceinline__ void small_grid_body(int blk, const float *pos_in, fl
             const int kmode = do_kick & NB_KICK_MODE_MASK;
             if (kmode != NB_KICK_NONE) {
                 T v = vel[idx];
-                if (do_kick & NB_KICK_OPEN_ON_READ) v = axpy_sep<T>(v, a_prev, half_dt);     // this step's opening kick, deferred (see below)
-                v = axpy_sep<T>(v, ak, half_dt);                          // closing kick (simulation.py:141)
+                if (do_kick & NB_KICK_OPEN_ON_READ) v = axpy_rn<T>(v, a_prev, half_dt);     // this step's opening kick, deferred (see below)
+                v = axpy_rn<T>(v, ak, half_dt);                          // closing kick (simulation.py:141)
                 if (kmode == NB_KICK_CLOSE_OPEN) {
-                    v = axpy_sep<T>(v, ak, half_dt);                      // next step's opening kick (:132)
-                    pos_out[idx] = axpy_sep<T>(xi[k], v, dt);             // ... and drift (:135)
+                    v = axpy_rn<T>(v, ak, half_dt);                      // next step's opening kick (:132)
+                    pos_out[idx] = axpy_rn<T>(xi[k], v, dt);             // ... and drift (:135)
                 } else if (kmode == NB_KICK_CLOSE_SPEC) {
                     // last step of a native call: velocities stay at the closing kick (what a reader must see), but the
                     // positions the NEXT step would drift to go to pos_out -- if the next nb_step finds the state
                     // untouched it takes them and applies its opening kick here on read (NB_KICK_OPEN_ON_READ): a Python loop of
                     // step() costs one launch per step instead of two
-                    const T vo = axpy_sep<T>(v, ak, half_dt);
-                    pos_out[idx] = axpy_sep<T>(xi[k], vo, dt);
+                    const T vo = axpy_rn<T>(v, ak, half_dt);
+                    pos_out[idx] = axpy_rn<T>(xi[k], vo, dt);
                 }
                 vel[idx] = v;
             }

@@ -117,17 +117,32 @@ def state_dtype(precision_mode) -> torch.dtype:
     return torch.float64 if precision_mode == PrecisionMode.FLOAT64 else torch.float32
 
 
+def _scalar_or_list(value, noun, kind, what, check=None, loose=False):
+    """An argument that is one value for all members or one per member -> a Python scalar or a list.  Tensors and numpy
+    arrays / scalars go through tolist(), lists, tuples and other Sequences (range and the like) become lists.  Every
+    entry must be a `kind` (numbers.Integral or numbers.Real) and no bool, else TypeError "`noun` must be `what`, got
+    <type>"; `check(entry)` follows each entry's type test.  loose (the constructors' G / softening / dt, as they have
+    always been read): only tensors, lists and tuples count as sequences and float() alone judges their entries."""
+    if isinstance(value, torch.Tensor) or not loose and type(value).__module__ == "numpy" and hasattr(value, "tolist"):
+        value = value.tolist()
+    elif isinstance(value, (list, tuple)) or not loose and isinstance(value, Sequence) and not isinstance(value, (str, bytes)):
+        value = list(value)
+    for v in (value if not loose else []) if isinstance(value, list) else [value]:
+        if isinstance(v, bool) or not isinstance(v, kind):
+            raise TypeError(f"{noun} must be {what}, got {type(v).__name__}")
+        if check is not None:
+            check(v)
+    return value
+
+
 def _param_list(name, value, members):
     """A float, or a sequence of `members` floats -> list of floats (members None: any length)."""
-    if isinstance(value, torch.Tensor):
-        value = value.tolist()
-    if isinstance(value, (list, tuple)):
+    value = _scalar_or_list(value, name, numbers.Real, "a float or a sequence of floats", loose=True)
+    if isinstance(value, list):
         out = [float(v) for v in value]
         if members is not None and len(out) != members:
             raise ValueError(f"{name} has {len(out)} entries for {members} members")
         return out
-    if isinstance(value, bool) or not isinstance(value, numbers.Real):
-        raise TypeError(f"{name} must be a float or a sequence of floats, got {type(value).__name__}")
     return None if members is None else [float(value)] * members
 
 
@@ -182,15 +197,8 @@ def _level_list(value):
     """custom_levels as given -> None, an int, or a list of ints (entries type-checked, not yet range- or length-checked)."""
     if value is None:
         return None
-    if isinstance(value, torch.Tensor) or type(value).__module__ == "numpy" and hasattr(value, "tolist"):
-        value = value.tolist()                # tensors and numpy arrays / scalars -> Python ints (or lists of them)
-    elif isinstance(value, Sequence) and not isinstance(value, (str, bytes)):
-        value = list(value)                   # range and the like
-    entries = value if isinstance(value, (list, tuple)) else [value]
-    for v in entries:
-        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
-            raise TypeError(f"custom_levels must be an int or a sequence of ints, got {type(v).__name__}")
-    return [int(v) for v in value] if isinstance(value, (list, tuple)) else int(value)
+    value = _scalar_or_list(value, "custom_levels", numbers.Integral, "an int or a sequence of ints")
+    return [int(v) for v in value] if isinstance(value, list) else int(value)
 
 
 def check_grid_arguments(positions, velocities, masses, precision_mode=PrecisionMode.INT8_SIM, custom_levels=None, G=0.001,
@@ -259,14 +267,7 @@ def check_member_ticks_arguments(num_ticks, every, members):
         raise ValueError(f"members must be >= 1, got {members}")
     if every is not None and (isinstance(every, bool) or not isinstance(every, numbers.Integral)):
         raise TypeError(f"every must be None or an int, got {type(every).__name__}")
-    if isinstance(num_ticks, torch.Tensor) or type(num_ticks).__module__ == "numpy" and hasattr(num_ticks, "tolist"):
-        num_ticks = num_ticks.tolist()            # tensors and numpy arrays / scalars -> Python numbers (or lists of them)
-    elif isinstance(num_ticks, Sequence) and not isinstance(num_ticks, (str, bytes)):
-        num_ticks = list(num_ticks)
-    entries = num_ticks if isinstance(num_ticks, list) else [num_ticks]
-    for v in entries:
-        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
-            raise TypeError(f"num_ticks must be an int or a sequence of ints, got {type(v).__name__}")
+    num_ticks = _scalar_or_list(num_ticks, "num_ticks", numbers.Integral, "an int or a sequence of ints")
     if isinstance(num_ticks, list) and len(num_ticks) != members:
         raise ValueError(f"num_ticks has {len(num_ticks)} entries for {members} members")
     budgets = [int(v) for v in num_ticks] if isinstance(num_ticks, list) else [int(num_ticks)] * members
@@ -364,17 +365,12 @@ def check_metrics_arguments(num_bins, max_radius, percentile, members):
     if percentile != percentile:
         raise ValueError("percentile is NaN")
     if max_radius is not None:
-        if isinstance(max_radius, torch.Tensor) or type(max_radius).__module__ == "numpy" and hasattr(max_radius, "tolist"):
-            max_radius = max_radius.tolist()
-        elif isinstance(max_radius, Sequence) and not isinstance(max_radius, (str, bytes)):
-            max_radius = list(max_radius)
-        entries = max_radius if isinstance(max_radius, (list, tuple)) else [max_radius]
-        for v in entries:
-            if isinstance(v, bool) or not isinstance(v, numbers.Real):
-                raise TypeError(f"max_radius must be None, a number or a sequence of numbers, got {type(v).__name__}")
+        def not_negative(v):
             if v < 0:
                 raise ValueError(f"max_radius must be >= 0, got {v}")
-        if not isinstance(max_radius, (list, tuple)):
+        max_radius = _scalar_or_list(max_radius, "max_radius", numbers.Real, "None, a number or a sequence of numbers",
+                                     check=not_negative)
+        if not isinstance(max_radius, list):
             max_radius = [max_radius] * members
         elif len(max_radius) != members:
             raise ValueError(f"max_radius has {len(max_radius)} entries for {members} members")
@@ -596,17 +592,28 @@ class GalaxyEnsemble:
         after every `every`-th tick of this call.  One native call; nothing is copied to the host in between.  The
         trajectory is bit-identical to run(num_ticks)."""
         offsets = check_record_arguments(num_ticks, every, self.num_members)
-        S, B = len(offsets), self.num_members
-        ke = torch.empty((S, B), dtype=torch.float64, device=self.device)
-        pe = torch.empty((S, B), dtype=torch.float64, device=self.device)
+        return self._recorded_call("nb_ens_run_recorded", (int(num_ticks), int(every)), offsets, advance=int(num_ticks))
+
+    def _recorded_call(self, entry, head, offsets, tail=(), advance=None, own=None):
+        """One recorded native run: `entry`(handle, *head, kinetic, potential, capacity, on_device, &samples, *tail) with
+        room for one sample per offset (`offsets` None or empty: no buffers), the sample count checked, the clocks
+        advanced by `advance` / `own` (_advance; None: the caller does it).  Returns the EnergyHistory at the absolute
+        ticks, or None without samples."""
+        S, B = len(offsets or ()), self.num_members
+        ke = pe = None
+        if S:
+            ke = torch.empty((S, B), dtype=torch.float64, device=self.device)
+            pe = torch.empty((S, B), dtype=torch.float64, device=self.device)
         got = C.c_int32()
-        N.check(N.lib().nb_ens_run_recorded(self._handle, int(num_ticks), int(every), C.c_void_p(ke.data_ptr()),
-                                            C.c_void_p(pe.data_ptr()), S, int(self.device.type == "cuda"), C.byref(got)))
+        N.check(getattr(N.lib(), entry)(
+            self._handle, *head, C.c_void_p(ke.data_ptr()) if S else None, C.c_void_p(pe.data_ptr()) if S else None, S,
+            int(self.device.type == "cuda"), C.byref(got), *tail))
         if got.value != S:
-            raise RuntimeError(f"nb_ens_run_recorded wrote {got.value} samples, expected {S}")
-        ticks = [self.tick + o for o in offsets]
-        self._advance(int(num_ticks))
-        return EnergyHistory(ticks, ke, pe)
+            raise RuntimeError(f"{entry} wrote {got.value} samples, expected {S}")
+        history = EnergyHistory([self.tick + o for o in offsets], ke, pe) if S else None
+        if advance is not None:
+            self._advance(advance, own=own)
+        return history
 
     def _advance(self, ticks, own=None):
         """The clocks after a call: `tick` by `ticks`, every member's by the same or by its `own`."""
@@ -627,22 +634,11 @@ class GalaxyEnsemble:
         """The native call behind run_members / run_watched: (EnergyHistory or None, stop ticks, reasons)."""
         import numpy as np
         B = self.num_members
-        S = len(offsets) if offsets is not None else 0
-        ke = pe = None
-        if S:
-            ke = torch.empty((S, B), dtype=torch.float64, device=self.device)
-            pe = torch.empty((S, B), dtype=torch.float64, device=self.device)
-        got = C.c_int32()
         stop, reason = np.zeros(B, np.int32), np.zeros(B, np.int32)
-        N.check(N.lib().nb_ens_run_members(
-            self._handle, (C.c_int32 * B)(*budgets), int(every or 0), int(bool(watch)),
-            C.c_void_p(ke.data_ptr()) if S else None, C.c_void_p(pe.data_ptr()) if S else None, S,
-            int(self.device.type == "cuda"), C.byref(got), stop.ctypes.data_as(C.POINTER(C.c_int32)),
-            reason.ctypes.data_as(C.POINTER(C.c_int32))))
-        if got.value != S:
-            raise RuntimeError(f"nb_ens_run_members wrote {got.value} samples, expected {S}")
-        history = EnergyHistory([self.tick + o for o in offsets], ke, pe) if S else None
-        self._advance(max(budgets), own=stop)
+        pi32 = C.POINTER(C.c_int32)
+        history = self._recorded_call("nb_ens_run_members", ((C.c_int32 * B)(*budgets), int(every or 0), int(bool(watch))),
+                                      offsets, (stop.ctypes.data_as(pi32), reason.ctypes.data_as(pi32)),
+                                      advance=max(budgets), own=stop)
         return history, stop.astype(np.int64), reason.astype(np.int64)
 
     def run_members(self, num_ticks, every=None):
@@ -679,21 +675,13 @@ class GalaxyEnsemble:
         nothing is read back before the end of the call."""
         import numpy as np
         budgets, offsets = check_member_ticks_arguments(max_ticks, 1, self.num_members)
-        B, S = self.num_members, len(offsets)
-        on_device = int(self.device.type == "cuda")
-        ke = torch.empty((S, B), dtype=torch.float64, device=self.device)
-        pe = torch.empty((S, B), dtype=torch.float64, device=self.device)
-        got = C.c_int32()
+        B = self.num_members
         stop, kind, flags = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
         meas = np.zeros((B, 4), np.float64)
         pi32 = C.POINTER(C.c_int32)
-        N.check(N.lib().nb_ens_run_crash_watched(
-            self._handle, (C.c_int32 * B)(*budgets), C.c_void_p(ke.data_ptr()), C.c_void_p(pe.data_ptr()), S, on_device,
-            C.byref(got), stop.ctypes.data_as(pi32), kind.ctypes.data_as(pi32), flags.ctypes.data_as(pi32),
-            meas.ctypes.data_as(C.POINTER(C.c_double))))
-        if got.value != S:
-            raise RuntimeError(f"nb_ens_run_crash_watched wrote {got.value} samples, expected {S}")
-        history = EnergyHistory([self.tick + o for o in offsets], ke, pe)
+        history = self._recorded_call("nb_ens_run_crash_watched", ((C.c_int32 * B)(*budgets),), offsets,
+                                      (stop.ctypes.data_as(pi32), kind.ctypes.data_as(pi32), flags.ctypes.data_as(pi32),
+                                       meas.ctypes.data_as(C.POINTER(C.c_double))))
         return self._crash_report(budgets, stop, kind, flags, meas, history)
 
     def _crash_report(self, budgets, stop, kind, flags, meas, history) -> CrashPointReport:
