@@ -15,7 +15,8 @@
 //   data and the J accumulators rotate by one lane (ds_bpermute_b32: the LDS crossbar, no VALU
 //   cycles), so every lane meets every J particle once and the accumulators return home.
 //   (fp64, 2-D, R = 4: by default the LDS hand-off of nb_force_sym_kernel.h -- a position ring staged once per
-//   workgroup and wave-private accumulator mailboxes -- replaces the rotation; NB_SYM_ROT=0 keeps it.)
+//   workgroup and wave-private accumulator mailboxes -- replaces the rotation; NB_SYM_ROT=0 keeps it, NB_SYM_ROT=2
+//   moves the accumulators with DPP moves in the VALU instead of the mailboxes.)
 //   J == I (diagonal tile) is evaluated one-sided, so each ordered pair is counted once.
 //   A workgroup = four waves = four consecutive target tiles (a "super-row") walking the SAME
 //   source tiles in step; after each source tile the four waves' column sums are added through
@@ -394,10 +395,13 @@ hipError_t nb_launch_force_sym_f64(const double *packed, const SymWork *work, in
                                    double *colslab, int np, int dim, int r, int uniform, int pa_f32, double eps2,
                                    hipStream_t st, NbKernelEvents ev, int rowsplit, int ldsrot)
 {
-    // LDS hand-off in place of the lane rotation (NB_SYM_ROT): the shapes it is instantiated for, others keep the rotation
+    // LDS (1) or DPP (2) hand-off in place of the lane rotation (NB_SYM_ROT): the shapes they are instantiated for, others
+    // keep the rotation
     if (ldsrot && dim == 2 && r == 4 && !pa_f32)
         return nb::pick_bool(rowsplit, [&](auto RS) {
-            return launch_sym_ldsrot<RS.value>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, st, ev);
+            if (ldsrot == SYM_ROT_DPP)
+                return launch_sym_ldsrot<RS.value, SYM_ROT_DPP>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, st, ev);
+            return launch_sym_ldsrot<RS.value, SYM_ROT_LDS>(packed, work, nwork, rowslab, colslab, np, uniform, eps2, st, ev);
         });
     if (rowsplit) {      // row-split work items (nb_plan.cpp): their own instantiations
         if (dim != 2 || r != 4) return hipErrorInvalidValue;

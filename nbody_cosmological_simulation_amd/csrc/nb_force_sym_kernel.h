@@ -137,7 +137,7 @@ template <int R, int RJ> struct BinDbg<R, RJ, true> {
     }
 };
 
-// ---- LDS hand-off (LDSROT = true instantiations: fp64, D = 2, R = 4, no hook) -------------------------------------
+// ---- LDS hand-off (ROT = SYM_ROT_LDS instantiations: fp64, D = 2, R = 4, no hook) ---------------------------------
 // The register rotation costs 32 ds_bpermute_b32 per step of 16 pairs (two per fp64 value: four positions and four
 // accumulator halves per source slot), each with its own address and data VGPR reads and its own LDS queue entry.  The
 // hand-off moves the same values with 12 wide LDS instructions per step:
@@ -161,6 +161,32 @@ struct LdsRot {
     const d2 *mail_r;       // mail[0][(lane + 1) & 63]
 };
 
+// ---- DPP hand-off (ROT = SYM_ROT_DPP: the same shapes as the LDS hand-off) -----------------------------------------
+// The mailbox is two thirds of the hand-off's LDS instructions (per step and slot a ds_write_b128, a fence pair, a
+// ds_read_b128 and a wait) for passing 16 bytes to the neighbouring lane.  GFX9 can do that in the VALU: a v_mov_b32 with
+// the DPP control wave_rol:1 hands every lane the operand of lane (lane + 1) & 63 -- the mailbox's direction, checked
+// on the card by tools/microbench.hip.  DPP moves are 32 bits wide, so an accumulator pair {aj_x, aj_y} takes four, in
+// place; the positions (and mass factors) still come from the ring.  Full row and bank masks and all 64 lanes active
+// (every sweep<> call sits in wave-uniform control flow; padding particles are real lanes), so no lane keeps a stale
+// value.  Through the builtin, so that the compiler places the wait state a DPP read of a fresh VALU result needs.
+// Same values, same arithmetic, same order: results are bit for bit those of the other two hand-offs.
+// SYM_ROT_DPPALL moves the positions (and mass factors) the same way and touches no LDS in the step loop: 32 (40) moves
+// per step.  Priced by tools/microbench.hip only; force_sym_kernel does not instantiate it.
+enum { SYM_ROT_LANES = 0,   // ds_bpermute_b32 rotation of every source value (all shapes)
+       SYM_ROT_LDS = 1,     // LDS ring + mailboxes (LdsRot)
+       SYM_ROT_DPP = 2,     // LDS ring + accumulators by DPP
+       SYM_ROT_DPPALL = 3 };
+
+constexpr int DPP_WAVE_ROL1 = 0x134;     // DPP_WF_RL1: lane l reads lane (l + 1) & 63
+__device__ __forceinline__ double dpp_rol1(double v)
+{
+    const long long b = __double_as_longlong(v);
+    int lo = (int)(b & 0xffffffffll), hi = (int)(b >> 32);
+    lo = __builtin_amdgcn_update_dpp(lo, lo, DPP_WAVE_ROL1, 0xf, 0xf, false);
+    hi = __builtin_amdgcn_update_dpp(hi, hi, DPP_WAVE_ROL1, 0xf, 0xf, false);
+    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+
 // One sweep of a target tile (R particles per lane) against RJ source slots: `nsteps` rotation steps (64 = all
 // lanes), R*RJ pairs per lane per step, J data rotating by one lane per step.  RJ = R covers the whole
 // source tile; D = 3 sweeps it in two halves (RJ = 2) to stay inside 128 VGPRs with R = 4 targets.
@@ -168,15 +194,18 @@ struct LdsRot {
 // UNIFORM: all masses equal -> the mass factor is applied once to the finished sums
 //          (reduce_sym_kernel), saving both mass multiplies and the rotation of the masses.
 // HOOK:    precision hook applied to the fp32 r2 (HOOK_NONE for fp64); EST: grid bins by estimate.
-// LDSROT:  the source data come from the LDS ring and the accumulators travel through the mailbox `lr` (see LdsRot)
-//          instead of rotating through ds_bpermute_b32; xj / gj hold the current step's values either way.
-template <typename T, int D, int R, int RJ, bool DIAG, bool UNIFORM, int HOOK, int EST, bool BINS = false, bool LDSROT = false>
+// ROT:     how the source data move on by one lane per step (SYM_ROT_*): ds_bpermute_b32 on everything; or the source
+//          positions from the LDS ring of `lr` with the accumulators through its mailbox (SYM_ROT_LDS, see LdsRot) or
+//          through DPP moves (SYM_ROT_DPP); or everything through DPP moves (SYM_ROT_DPPALL).  xj / gj hold the current
+//          step's values in every mode.
+template <typename T, int D, int R, int RJ, bool DIAG, bool UNIFORM, int HOOK, int EST, bool BINS = false, int ROT = SYM_ROT_LANES>
 __device__ __forceinline__ void sweep(const T (&xi)[R][D], const T (&gi)[R], T (&ai)[R][D], T (&xj)[RJ][D],
                                       T (&gj)[RJ], T (&aj)[RJ][D], T eps2, int rot_addr, const GridArgs &ga,
                                       int nsteps, BinDbg<R, RJ, BINS> &bd, const LdsRot lr = LdsRot{})
 {
-    static_assert(!LDSROT || (std::is_same_v<T, double> && D == 2 && R == 4 && RJ == 4 && HOOK == HOOK_NONE && !BINS),
-                  "LDS hand-off: fp64, 2-D, four targets per lane, no hook, no bin read-out");
+    static_assert(ROT == SYM_ROT_LANES || (std::is_same_v<T, double> && D == 2 && R == 4 && RJ == 4 && HOOK == HOOK_NONE && !BINS),
+                  "LDS and DPP hand-offs: fp64, 2-D, four targets per lane, no hook, no bin read-out");
+    constexpr bool LDSROT = ROT == SYM_ROT_LDS || ROT == SYM_ROT_DPP;      // positions from the ring
     T c15 = (T)1.5, c1875 = (T)1.875;
     if constexpr (std::is_same_v<T, double>) asm volatile("" : "+v"(c15), "+s"(c1875));
 #pragma unroll 1
@@ -292,7 +321,10 @@ __device__ __forceinline__ void sweep(const T (&xi)[R][D], const T (&gi)[R], T (
                 xj[rj][0] = nx.x;
                 xj[rj][1] = nx.y;
                 if (!UNIFORM) gj[rj] = lr.ring_g[rj * 128 + s + 1];
-                if (!DIAG) {
+                if constexpr (!DIAG && ROT == SYM_ROT_DPP) {
+                    aj[rj][0] = dpp_rol1(aj[rj][0]);
+                    aj[rj][1] = dpp_rol1(aj[rj][1]);
+                } else if constexpr (!DIAG) {
                     lr.mail_w[rj * 64] = d2{aj[rj][0], aj[rj][1]};
                     // the wave's LDS instructions complete in order; the fences keep the compiler from reordering them
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -301,6 +333,13 @@ __device__ __forceinline__ void sweep(const T (&xi)[R][D], const T (&gi)[R], T (
                     aj[rj][0] = na.x;
                     aj[rj][1] = na.y;
                 }
+            } else if constexpr (ROT == SYM_ROT_DPPALL) {
+#pragma unroll
+                for (int k = 0; k < D; ++k) {
+                    xj[rj][k] = dpp_rol1(xj[rj][k]);
+                    if (!DIAG) aj[rj][k] = dpp_rol1(aj[rj][k]);
+                }
+                if (!UNIFORM) gj[rj] = dpp_rol1(gj[rj]);
             } else {
 #pragma unroll
                 for (int k = 0; k < D; ++k) {
@@ -503,12 +542,12 @@ __device__ unsigned long long nb_wg_trace_buf[NB_WG_TRACE_MAX][8];
 // (The general-mass row-split instantiations need 134-140 VGPRs: three waves per SIMD instead of spilling.)
 // BINS (nb_force_sym_bins.hip only): the same body with the bin read-out of BinDbg; bin_out = {s1[n], s2[n],
 // {table-free pairs, table pairs}} as unsigned 64-bit integers, added with atomics (integer sums: order-free).
-// LDSROT (fp64, D = 2, R = 4, HOOK_NONE, never with BINS): the LDS hand-off of LdsRot in place of the lane rotation.  A
-// separate instantiation picked by the launcher, like RSPLIT.  118-126 VGPRs, except the general-mass row-split one, which
-// like its rotation twin runs three waves per SIMD (156 VGPRs; bounded to four waves it spills 37 around the sweeps):
-// profiles/rotation_exchange_resources.txt.
+// ROT (SYM_ROT_LDS / SYM_ROT_DPP: fp64, D = 2, R = 4, HOOK_NONE, never with BINS): the LDS hand-off of LdsRot, or the ring
+// with the accumulators by DPP, in place of the lane rotation.  Separate instantiations picked by the launcher, like
+// RSPLIT.  114-126 VGPRs, except the general-mass row-split ones, which like their rotation twin run three waves per SIMD
+// (bounded to four waves they spill around the sweeps): profiles/rotation_exchange_resources.txt, profiles/dpp_rotation_ab.txt.
 template <typename T, int D, int R, bool UNIFORM, int HOOK, int LPC = NB_LUT_MIN, bool BINS = false, bool RSPLIT = false,
-          bool LDSROT = false>
+          int ROT = SYM_ROT_LANES>
 __global__ void __launch_bounds__(NB_BLOCK, BINS ? 2 : ((HOOK == HOOK_GRID && LPC > NB_LUT_MIN) || (RSPLIT && !UNIFORM) ? 3 : 4))
 force_sym_kernel(const T *__restrict__ packed, const SymWork *__restrict__ work, double *__restrict__ rowslab,
                  T *__restrict__ colslab, int np, T eps2, const GridTables *__restrict__ tab, float gfac, float g_newton,
@@ -520,10 +559,13 @@ force_sym_kernel(const T *__restrict__ packed, const SymWork *__restrict__ work,
     constexpr int RJ = (NB_GRID_GENERAL_PACKED == 2 && F32_ && HOOK == HOOK_GRID && !UNIFORM && R == 4 && D == 2) ? 2 : sym_rj(D, R);
     constexpr int W = NB_BLOCK / 64;
     constexpr bool F32 = std::is_same_v<T, float>;
+    static_assert(ROT == SYM_ROT_LANES || ROT == SYM_ROT_LDS || ROT == SYM_ROT_DPP, "hand-offs force_sym_kernel instantiates");
+    constexpr bool LDSROT = ROT != SYM_ROT_LANES;       // the source tile's positions come from the LDS ring
     alignas(LDSROT ? 16 : alignof(T)) __shared__ T s_aj[W][RJ][D][64];
     // LDS hand-off: the source tile's positions (and mass factors) as rings, staged once per source tile by the whole
     // workgroup; the waves' mailboxes reuse s_aj (wave w owns s_aj[w] = mail[w][RJ][64] of 16 bytes until it leaves its
-    // column sums there after the sweep).  16 + 8 (+ 4) KiB per workgroup.
+    // column sums there after the sweep; SYM_ROT_DPP has no mailbox and only the column sums go there).  16 + 8 (+ 4) KiB
+    // per workgroup.
     static_assert(!LDSROT || (!F32_ && D == 2 && R == 4 && HOOK == HOOK_NONE && !BINS), "LDS hand-off: fp64, 2-D, R = 4, no hook");
     static_assert(!LDSROT || sizeof(s_aj) == sizeof(d2) * W * RJ * 64, "the mailboxes reuse the column buffer");
     __shared__ d2 s_ring[LDSROT ? RJ : 1][LDSROT ? 128 : 1];
@@ -638,8 +680,10 @@ force_sym_kernel(const T *__restrict__ packed, const SymWork *__restrict__ work,
     };
     LdsRot lr{};
     if constexpr (LDSROT) {
+        constexpr bool MAIL = ROT == SYM_ROT_LDS;       // SYM_ROT_DPP: no mailbox, no address registers for it
         d2 *mail = reinterpret_cast<d2 *>(&s_aj[wave][0][0][0]);
-        lr = LdsRot{&s_ring[0][lane + wk_s_begin], &s_ring_g[0][UNIFORM ? 0 : lane + wk_s_begin], mail + lane, mail + ((lane + 1) & 63)};
+        lr = LdsRot{&s_ring[0][lane + wk_s_begin], &s_ring_g[0][UNIFORM ? 0 : lane + wk_s_begin], MAIL ? mail + lane : nullptr,
+                    MAIL ? mail + ((lane + 1) & 63) : nullptr};
         if (wk.jt_begin < wk.jt_end) stage_ring(wk.jt_begin);
         __syncthreads();
     }
@@ -734,8 +778,8 @@ force_sym_kernel(const T *__restrict__ packed, const SymWork *__restrict__ work,
                     for (int k = 0; k < D; ++k) ai[r][k] = F32 ? (T)0 : (T)row_ref(r, k);
 #define NB_SWEEP(EE)                                                                                                  \
     do {                                                                                                                 \
-        if (diag) sweep<T, D, R, RJ, true, UNIFORM, HOOK, EE, BINS, LDSROT>(xi, gi, ai, xj, gj, aj, eps2, rot_addr, ga, wk_s_count, bd, lr); \
-        else sweep<T, D, R, RJ, false, UNIFORM, HOOK, EE, BINS, LDSROT>(xi, gi, ai, xj, gj, aj, eps2, rot_addr, ga, wk_s_count, bd, lr);     \
+        if (diag) sweep<T, D, R, RJ, true, UNIFORM, HOOK, EE, BINS, ROT>(xi, gi, ai, xj, gj, aj, eps2, rot_addr, ga, wk_s_count, bd, lr); \
+        else sweep<T, D, R, RJ, false, UNIFORM, HOOK, EE, BINS, ROT>(xi, gi, ai, xj, gj, aj, eps2, rot_addr, ga, wk_s_count, bd, lr);     \
     } while (0)
                 if (HOOK == HOOK_GRID && degenerate) NB_SWEEP(GRID_DEGENERATE);
                 else if (HOOK == HOOK_GRID && fast && eps2 < (T)0.01) NB_SWEEP(GRID_FAST_CLAMP);
@@ -887,13 +931,13 @@ hipError_t launch_sym_rowsplit(const double *packed, const SymWork *work, int nw
     return hipGetLastError();
 }
 
-// LDS hand-off instantiations (fp64, D = 2, R = 4, no hook; classic and row-split work items): see LdsRot
-template <bool RSPLIT>
+// LDS and DPP hand-off instantiations (fp64, D = 2, R = 4, no hook; classic and row-split work items): see LdsRot
+template <bool RSPLIT, int ROT>
 hipError_t launch_sym_ldsrot(const double *packed, const SymWork *work, int nwork, double *rowslab, double *colslab, int np,
                              int uniform, double eps2, hipStream_t st, NbKernelEvents ev)
 {
     return nb::pick_bool(uniform, [&](auto U) {
-        hipExtLaunchKernelGGL((force_sym_kernel<double, 2, 4, U.value, HOOK_NONE, NB_LUT_MIN, false, RSPLIT, true>), dim3(nwork),
+        hipExtLaunchKernelGGL((force_sym_kernel<double, 2, 4, U.value, HOOK_NONE, NB_LUT_MIN, false, RSPLIT, ROT>), dim3(nwork),
                               dim3(NB_BLOCK), 0, st, ev.start, ev.stop, 0, packed, work, rowslab, colslab, np, eps2, nullptr, 1.0f,
                               0.0f, nullptr, 0);
         return hipGetLastError();

@@ -26,7 +26,7 @@ NbKnobs nb_read_knobs()
     k.tail_pieces = env_int("NB_SYM_TAIL", 0);
     if (k.tail_pieces != 2 && k.tail_pieces != 4 && k.tail_pieces != 8 && k.tail_pieces != 16) k.tail_pieces = 0;
     k.sym_rot = env_int("NB_SYM_ROT", -1);
-    if (k.sym_rot != 0 && k.sym_rot != 1) k.sym_rot = -1;
+    if (k.sym_rot < 0 || k.sym_rot > 2) k.sym_rot = -1;
     k.r_onesided = env_int("NB_R", 0);
     k.no_prune = getenv("NB_NO_PRUNE") != nullptr;
     k.no_track = env_int("NB_NO_TRACK", 0) != 0;

@@ -10,10 +10,11 @@
 
 #include "nb_internal.h"
 
-// What an unset NB_SYM_ROT means (NbKnobs::sym_rot): the LDS hand-off, by the same-card A/B of profiles/rotation_exchange_ab.txt
-// (N = 65 536 FLOAT64 step 1188 -> 1158 us, five alternating runs each, ranges disjoint)
+// What an unset NB_SYM_ROT means (NbKnobs::sym_rot): the LDS ring with the accumulators moved by DPP, by the same-card A/Bs
+// of profiles/rotation_exchange_ab.txt (lane rotation -> ring + mailboxes: N = 65 536 FLOAT64 step 1188 -> 1158 us) and
+// profiles/dpp_rotation_ab.txt (mailboxes -> DPP: 1138.7 -> 1117.6 us); five alternating runs each, ranges disjoint
 #ifndef NB_SYM_ROT_DEFAULT
-#define NB_SYM_ROT_DEFAULT 1
+#define NB_SYM_ROT_DEFAULT 2
 #endif
 
 // Tuning / test knobs, read from the environment ONCE per handle (nb_create) -- never inside a step.
@@ -24,7 +25,7 @@ struct NbKnobs {
     int sym_split = 0;     // NB_SYM_SPLIT: cut EVERY sweep into 1 ... 16 pieces; 0 = the plan's own choice
     int sym_rowsplit = -1; // NB_SYM_ROWSPLIT: row-split work items (fp64, 2-D, R = 4): -1 = the plan's choice, 0 = never, n = always, n step pieces
     int tail_pieces = 0;   // NB_SYM_TAIL: pieces per sweep of the tail-smoothed super-rows (4 or 8); 0 = auto
-    int sym_rot = -1;      // NB_SYM_ROT: source hand-off of the fp64, 2-D, R = 4 sweep: 0 = lane rotation (ds_bpermute), 1 = LDS ring + mailboxes; -1 = default (NB_SYM_ROT_DEFAULT)
+    int sym_rot = -1;      // NB_SYM_ROT: source hand-off of the fp64, 2-D, R = 4 sweep: 0 = lane rotation (ds_bpermute), 1 = LDS ring + mailboxes, 2 = LDS ring + accumulators by DPP; -1 = default (NB_SYM_ROT_DEFAULT)
     int r_onesided = 0;    // NB_R: targets per thread of the one-sided fp64 kernel
     bool no_prune = false;   // NB_NO_PRUNE: all-pairs max-r2 scan at any N
     bool no_track = false;   // NB_NO_TRACK: every grid evaluation searches its farthest pair from scratch (A/B of round 3's tracked search)

@@ -1,11 +1,13 @@
 // microbench.hip -- instruction-rate and accuracy probes that size the force kernel's budget
 // on gfx950 (DESIGN.md "instruction budget").  Not part of the library; built by
 // csrc/Makefile target `tools`, run on the GPU box:  ./microbench.bin > gpurun_out/microbench.txt
+// (`./microbench.bin rot 3`: only the DPP value check and the rotation-cost table, three times)
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "../nb_force_sym_kernel.h"     // sweep<>, inv_r3_sym, LdsRot: the rotation-cost rows run the library's own pair loop
@@ -113,8 +115,11 @@ __global__ void __launch_bounds__(256) pair_kernel(double *out, double seed)
 // masses, off-diagonal: 14 VALU + rsq per pair, 16 pairs per step).  ROT_BPERMUTE and ROT_LDS run the library's own sweep<>
 // (two ds_bpermute_b32 per pair, or the LDS hand-off of LdsRot: 0.75 wide LDS instructions per pair); ROT_NONE is the same
 // pair body with the source data and accumulators staying where they are (made opaque to the compiler once per slot, so
-// that nothing is hoisted: no instruction is emitted for that).
-enum { ROT_NONE, ROT_BPERMUTE, ROT_LDS };
+// that nothing is hoisted: no instruction is emitted for that).  ROT_DPP keeps the ring for the positions and moves the
+// accumulators with DPP (SYM_ROT_DPP: one v_mov_b32_dpp per pair, 0.25 ds_read_b128); ROT_DPPALL moves the positions by
+// DPP too (SYM_ROT_DPPALL: two v_mov_b32_dpp per pair, no LDS instruction in the step loop).
+enum { ROT_NONE, ROT_BPERMUTE, ROT_LDS, ROT_DPP, ROT_DPPALL };
+constexpr int rot_mode(int m) { return m == ROT_LDS ? SYM_ROT_LDS : m == ROT_DPP ? SYM_ROT_DPP : m == ROT_DPPALL ? SYM_ROT_DPPALL : SYM_ROT_LANES; }
 constexpr int ROT_SWEEPS = 64;      // sweeps of 64 steps per launch: 65 536 pairs per lane
 
 template <int MODE>
@@ -135,7 +140,7 @@ __global__ void __launch_bounds__(256, 4) sweep_rot_kernel(double *out, double s
             ai[r][k] = aj[r][k] = 0.0;
         }
     }
-    if (MODE == ROT_LDS) {      // the ring as force_sym_kernel stages it: 64 entries per slot, repeated
+    if (MODE == ROT_LDS || MODE == ROT_DPP) {      // the ring as force_sym_kernel stages it: 64 entries per slot, repeated
         const int r = threadIdx.x >> 6;
         const d2 v = {0.25 + lane * 2e-3 + 0.75 * r, 0.25 + lane * 2e-3 + 0.75 * r + 0.125};
         s_ring[r][lane] = v;
@@ -169,7 +174,7 @@ __global__ void __launch_bounds__(256, 4) sweep_rot_kernel(double *out, double s
                 }
             }
         } else {
-            sweep<double, D, R, R, false, true, HOOK_NONE, 0, false, MODE == ROT_LDS>(xi, gi, ai, xj, gj, aj, eps2, rot_addr, ga, 64, bd, lr);
+            sweep<double, D, R, R, false, true, HOOK_NONE, 0, false, rot_mode(MODE)>(xi, gi, ai, xj, gj, aj, eps2, rot_addr, ga, 64, bd, lr);
         }
     }
     double s = 0;
@@ -178,6 +183,63 @@ __global__ void __launch_bounds__(256, 4) sweep_rot_kernel(double *out, double s
 #pragma unroll
         for (int k = 0; k < D; ++k) s += ai[r][k] + aj[r][k];
     out[blockIdx.x * blockDim.x + threadIdx.x] = s;
+}
+
+// ---- does dpp_rol1 (nb_force_sym_kernel.h) hand lane l the value of lane (l + 1) & 63, as the mailbox read does, bit for
+// bit?  One wave; after `rotations` rotations lane l writes what it holds.
+__global__ void __launch_bounds__(64) dpp_rol_check_kernel(const double *in, double *out, int rotations)
+{
+    double v = in[threadIdx.x];
+    for (int r = 0; r < rotations; ++r) v = dpp_rol1(v);
+    out[threadIdx.x] = v;
+}
+
+static bool dpp_rol_check()
+{
+    // two patterns per lane: the lane id in both words (direction), and fp64 values that a move through an fp64 ALU
+    // could alter -- a NaN with a payload (quiet and signalling), -0.0, a denormal, infinities, ordinary numbers
+    unsigned long long hin[2][64], hout[64];
+    for (int l = 0; l < 64; ++l) {
+        hin[0][l] = ((unsigned long long)(0x1000 + l) << 32) | (unsigned)l;
+        unsigned long long b;
+        switch (l % 8) {
+        case 0: b = 0x7ff8dead0000beefull; break;                     // quiet NaN with a payload
+        case 1: b = 0x7ff0000000c0ffeeull; break;                     // signalling NaN
+        case 2: b = 0x8000000000000000ull; break;                     // -0.0
+        case 3: b = 0x0000000000000123ull; break;                     // denormal
+        case 4: b = 0xfff0000000000000ull; break;                     // -inf
+        case 5: b = 0xfff8000000000001ull; break;                     // negative NaN
+        default: { const double d = 1.0 / 3.0 + l; __builtin_memcpy(&b, &d, 8); }
+        }
+        hin[1][l] = b + ((unsigned long long)l << 8);                 // distinct in every lane (the payload / mantissa bits)
+    }
+    double *din, *dout;
+    CHECK(hipMalloc(&din, 64 * 8));
+    CHECK(hipMalloc(&dout, 64 * 8));
+    bool ok = true;
+    for (int pat = 0; pat < 2; ++pat) {
+        CHECK(hipMemcpy(din, hin[pat], 64 * 8, hipMemcpyHostToDevice));
+        const int rots[] = {1, 64, 21};
+        for (int nr : rots) {
+            hipLaunchKernelGGL(dpp_rol_check_kernel, dim3(1), dim3(64), 0, 0, din, dout, nr);
+            CHECK(hipMemcpy(hout, dout, 64 * 8, hipMemcpyDeviceToHost));
+            int bad = 0;
+            for (int l = 0; l < 64; ++l) bad += hout[l] != hin[pat][(l + nr) & 63];
+            printf("dpp wave_rol:1 check, pattern %d, %2d rotation(s): lane l holds lane (l + %d) & 63 bit for bit: %s", pat, nr, nr & 63,
+                   bad ? "FAIL" : "pass");
+            if (bad) {
+                int from_prev = 0;
+                for (int l = 0; l < 64; ++l) from_prev += hout[l] == hin[pat][(l - nr) & 63];
+                printf(" (%d lanes wrong; %d lanes hold lane (l - %d) & 63; lane 0 holds %016llx)", bad, from_prev, nr & 63, hout[0]);
+                ok = false;
+            }
+            printf("\n");
+        }
+    }
+    CHECK(hipFree(din));
+    CHECK(hipFree(dout));
+    printf("dpp wave_rol:1 value check: %s\n", ok ? "PASS" : "FAIL");
+    return ok;
 }
 
 __global__ void rsq_accuracy_kernel(const double *x, double *y_rsq, double *y_r3, int n)
@@ -211,8 +273,12 @@ double time_kernel(K launch, int reps)
     return ms / reps;
 }
 
-int main()
+// ./microbench.bin            every table once
+// ./microbench.bin rot [K]    the DPP value check and the rotation-cost table K times (its own spread), nothing else
+int main(int argc, char **argv)
 {
+    const bool rot_only = argc > 1 && !strcmp(argv[1], "rot");
+    const int rot_reps = rot_only && argc > 2 ? atoi(argv[2]) : 1;
     hipDeviceProp_t prop;
     CHECK(hipGetDeviceProperties(&prop, 0));
     const int cus = prop.multiProcessorCount;
@@ -232,9 +298,9 @@ int main()
                clk_ghz * 4.0 / cyc, cyc);
     }
 
-    printf("\n# issue rate: cycles per wave64 instruction per SIMD (at nominal clock), by waves/SIMD\n");
-    printf("%-16s %10s %10s %10s\n", "op", "1 wave", "2 waves", "4 waves");
-    for (int op = 0; op <= OP_MIX_PAIR; ++op) {
+    if (!rot_only) printf("\n# issue rate: cycles per wave64 instruction per SIMD (at nominal clock), by waves/SIMD\n");
+    if (!rot_only) printf("%-16s %10s %10s %10s\n", "op", "1 wave", "2 waves", "4 waves");
+    for (int op = 0; op <= OP_MIX_PAIR && !rot_only; ++op) {
         printf("%-16s", OP_NAMES[op]);
         for (int bpc : blocks_per_cu) {
             const int grid = cus * bpc;   // 256 threads = 4 waves = 1 wave per SIMD per block
@@ -259,34 +325,43 @@ int main()
 
     // rotation cost of the pair-symmetric fp64 sweep, in the units of pair_body_f64 above; v_fma_f64 once more right before
     // them gives the clock these rows held (an fp64 FMA issues every 4 cycles per SIMD)
-    printf("\n# rotation cost: cycles per PAIR (14 VALU + rsq, sweep<double, 2, 4, 4> uniform off-diagonal) per SIMD at nominal clock\n");
-    printf("%-16s %10s %10s %10s\n", "op", "1 wave", "2 waves", "4 waves");
-    const char *rot_names[] = {"v_fma_f64", "pair_sym_f64", "pair_sym+bperm", "pair_sym+ldsrot"};
+    printf("\n");
+    const bool dpp_ok = dpp_rol_check();
+    const char *rot_names[] = {"v_fma_f64", "pair_sym_f64", "pair_sym+bperm", "pair_sym+ldsrot", "pair_sym+dpp", "pair_sym+dppall"};
     double fma_cyc4 = 4.0;
-    for (int row = 0; row < 4; ++row) {
-        printf("%-16s", rot_names[row]);
-        for (int bpc : blocks_per_cu) {
-            const int grid = cus * bpc;
-            auto launch = [&]() {
-                switch (row) {
-                case 0: hipLaunchKernelGGL(op_kernel<OP_FMA64>, dim3(grid), dim3(256), 0, 0, out, 1.5); break;
-                case 1: hipLaunchKernelGGL(sweep_rot_kernel<ROT_NONE>, dim3(grid), dim3(256), 0, 0, out, 1.5); break;
-                case 2: hipLaunchKernelGGL(sweep_rot_kernel<ROT_BPERMUTE>, dim3(grid), dim3(256), 0, 0, out, 1.5); break;
-                case 3: hipLaunchKernelGGL(sweep_rot_kernel<ROT_LDS>, dim3(grid), dim3(256), 0, 0, out, 1.5); break;
-                }
-            };
-            const double ms = time_kernel(launch, 5);
-            const double per_simd = row == 0 ? (double)ITERS * UNROLL * bpc : (double)ROT_SWEEPS * 64 * 16 * bpc;
-            const double cyc = ms * 1e-3 * clk_ghz * 1e9 / per_simd;
-            if (row == 0 && bpc == 4) fma_cyc4 = cyc;
-            printf(" %10.2f", cyc);
+    for (int rep = 0; rep < rot_reps; ++rep) {
+        printf("\n# rotation cost: cycles per PAIR (14 VALU + rsq, sweep<double, 2, 4, 4> uniform off-diagonal) per SIMD at nominal clock\n");
+        printf("%-16s %10s %10s %10s\n", "op", "1 wave", "2 waves", "4 waves");
+        for (int row = 0; row < 6; ++row) {
+            printf("%-16s", rot_names[row]);
+            for (int bpc : blocks_per_cu) {
+                const int grid = cus * bpc;
+                auto launch = [&]() {
+                    switch (row) {
+                    case 0: hipLaunchKernelGGL(op_kernel<OP_FMA64>, dim3(grid), dim3(256), 0, 0, out, 1.5); break;
+                    case 1: hipLaunchKernelGGL(sweep_rot_kernel<ROT_NONE>, dim3(grid), dim3(256), 0, 0, out, 1.5); break;
+                    case 2: hipLaunchKernelGGL(sweep_rot_kernel<ROT_BPERMUTE>, dim3(grid), dim3(256), 0, 0, out, 1.5); break;
+                    case 3: hipLaunchKernelGGL(sweep_rot_kernel<ROT_LDS>, dim3(grid), dim3(256), 0, 0, out, 1.5); break;
+                    case 4: hipLaunchKernelGGL(sweep_rot_kernel<ROT_DPP>, dim3(grid), dim3(256), 0, 0, out, 1.5); break;
+                    case 5: hipLaunchKernelGGL(sweep_rot_kernel<ROT_DPPALL>, dim3(grid), dim3(256), 0, 0, out, 1.5); break;
+                    }
+                };
+                const double ms = time_kernel(launch, 5);
+                const double per_simd = row == 0 ? (double)ITERS * UNROLL * bpc : (double)ROT_SWEEPS * 64 * 16 * bpc;
+                const double cyc = ms * 1e-3 * clk_ghz * 1e9 / per_simd;
+                if (row == 0 && bpc == 4) fma_cyc4 = cyc;
+                printf(" %10.2f", cyc);
+            }
+            if (row == 2) printf("   <- + 2 ds_bpermute_b32 per pair");
+            if (row == 3) printf("   <- + 0.75 ds_read_b128 / ds_write_b128 per pair");
+            if (row == 4) printf("   <- + 0.25 ds_read_b128 + 1 v_mov_b32_dpp per pair");
+            if (row == 5) printf("   <- + 2 v_mov_b32_dpp per pair");
+            printf("\n");
         }
-        if (row == 2) printf("   <- + 2 ds_bpermute_b32 per pair");
-        if (row == 3) printf("   <- + 0.75 ds_read_b128 / ds_write_b128 per pair");
-        printf("\n");
+        printf("clock held (4 cycles per v_fma_f64 at 4 waves): %.3f GHz of %.3f nominal -> real cycles = nominal x %.3f\n",
+               clk_ghz * 4.0 / fma_cyc4, clk_ghz, 4.0 / fma_cyc4);
     }
-    printf("clock held (4 cycles per v_fma_f64 at 4 waves): %.3f GHz of %.3f nominal -> real cycles = nominal x %.3f\n",
-           clk_ghz * 4.0 / fma_cyc4, clk_ghz, 4.0 / fma_cyc4);
+    if (rot_only) return dpp_ok ? 0 : 1;
 
     // accuracy of v_rsq_f64 and of the corrected q^-1.5
     const int n = 1 << 20;
