@@ -321,8 +321,11 @@ int nb_quant_bins_rows(nb_sim *s, int32_t i0, int32_t i1, int16_t *d2bins);
  * per lane (path 1) / lanes per target (path 3), [2] 1 if the uniform-mass packed kernel did the work, [3] 1 if the
  * tables enabled the table-free pair path, [4] pair evaluations binned by the table-free estimate alone, [5] pair
  * evaluations binned through a threshold table, [6] grid levels.  Degenerate grids (values pass through, no bins),
- * the generic per-pair path and handles with a communicator return NB_ERR_UNSUPPORTED.  The forces are recomputed
- * (same values); velocities and positions are not touched. */
+ * the generic per-pair path and handles with a communicator return NB_ERR_UNSUPPORTED.  A read-only call: the pair
+ * sums of the extra evaluation go to a scratch buffer and no force quantisation follows, so positions, velocities,
+ * accelerations (values and dtype), the force bins and bounds nb_quant_debug reports and nb_force_kernel_name are what
+ * the last evaluation left, and the steps that follow are bit-identical to those of a handle that was never read.  The
+ * grid tables are rebuilt from the same positions (same values). */
 int nb_quant_bin_sums(nb_sim *s, int32_t which, int64_t *sum_k, int64_t *sum_kw, double info[8]);
 
 /* ---- tensor-level hooks (quantization.py module functions used by override subclasses) -- */

@@ -394,7 +394,9 @@ int reduce_and_exchange(nb_sim *s, const EvalRequest &rq, Eval &e, EvalResult *r
     const nb_config &c = s->cfg;
     const int64_t cnt = nd(s);
     const bool p2p = e.multi && (e.x64 ? p2p_use_x64(s, cnt) : p2p_use(s, cnt));
-    void *red_out = p2p ? nb_p2p_data() : s->acc;
+    // a bin read-out (nb_quant_bin_sums) is an observer: its sums go to the staging buffer, never over the accelerations
+    // the next opening kick reads
+    void *red_out = p2p ? nb_p2p_data() : (rq.bins ? s->staging : s->acc);
     if (e.x64 && !p2p && !s->sums64) HIPCHK(hipMalloc((void **)&s->sums64, (size_t)cnt * sizeof(double)));
     double *sums64 = e.x64 ? (p2p ? (double *)nb_p2p_data() : s->sums64) : nullptr;
     if (p2p)
@@ -494,6 +496,9 @@ int force_eval(nb_sim *s, EvalRequest rq, EvalResult *result)
     if (e.shard && rq.kick) return fail(NB_ERR_INVALID, "NB_FLAG_NO_COMM handles cannot step");
     if (e.generic) return force_eval_generic(s, rq, e, res);
     s->last_generic = false;
+    // the bins are decided in the pair loop: a read-out stops at the sums (reduce_and_exchange sends them to the staging
+    // buffer) and leaves the force bounds, the force bins and the accelerations' dtype to the evaluation they belong to
+    if (rq.bins) e.fq = e.red_mm = false;
     if (e.hook == HOOK_GRID)
         if (int rc = grid_prepare(s, e, false)) return rc;
     if (int rc = launch_pairs(s, rq, e)) return rc;
@@ -508,6 +513,7 @@ int force_eval(nb_sim *s, EvalRequest rq, EvalResult *result)
             snprintf(res->site, sizeof res->site, "axpy");
         }
     }
+    if (rq.bins) return NB_OK;
     s->logical[3] = acc_logical_dtype(s);
     s->have_acc = true;
     return NB_OK;
@@ -737,10 +743,14 @@ int energy_eval(nb_sim *s, double *kinetic, double *potential)
 }
 
 // Quant-bin read-out (nb_quant_bin_sums).  Runs the evaluation once more on the CURRENT positions with the BINS
-// instantiation of whichever grid-mode pair loop the production path uses here -- same launch sequence (max-r2, tables,
-// uniform / general pair of launches, reduction, force quantisation: the forces are simply recomputed), same control
-// flow inside the pair loop -- and returns, per particle p, s1 = sum_q k(p, q) and s2 = sum_q k(p, q) ((q mod 65521) + 1)
-// over ALL q including p itself (the reference's N x N bin matrix has k = 0 on the diagonal).
+// instantiation of whichever grid-mode pair loop the production path uses here -- same launch sequence up to the sums
+// (max-r2, tables, uniform / general pair of launches, reduction), same control flow inside the pair loop -- and returns,
+// per particle p, s1 = sum_q k(p, q) and s2 = sum_q k(p, q) ((q mod 65521) + 1) over ALL q including p itself (the
+// reference's N x N bin matrix has k = 0 on the diagonal).
+// An observer: the sums land in the staging buffer and there is no force quantisation, so the accelerations (the tiled
+// path sums in another order than the small step: its values differ in the last bits), their dtype, the force bins and
+// bounds, last_kernel and the tracked search's seed flag are what the last evaluation left.  The grid tables are rebuilt
+// from the same positions (the same values); the tracked search's candidate state moves on as under any evaluation.
 int bin_sums_eval(nb_sim *s, int which, int64_t *sum_k, int64_t *sum_kw, double info[8])
 {
     const nb_config &c = s->cfg;
@@ -753,6 +763,8 @@ int bin_sums_eval(nb_sim *s, int which, int64_t *sum_k, int64_t *sum_kw, double 
     HIPCHK(hipMemsetAsync(s->bin_out, 0, words * sizeof(unsigned long long), s->stream));
     const bool last_small = strcmp(s->last_kernel, "small_step_kernel") == 0;
     const bool want_small = which == 2 || (which == 0 && last_small);
+    const bool seeded = s->prune_seeded;
+    const char *const last_kernel = s->last_kernel;
     int path = 0, shape = 0;
     if (want_small) {
         if (!small_ok(s)) return fail(NB_ERR_INVALID, "quant-bin read-out: the one-launch small-system step does not apply to this handle "
@@ -760,7 +772,9 @@ int bin_sums_eval(nb_sim *s, int which, int64_t *sum_k, int64_t *sum_kw, double 
         // what step_small launches for one step, force only (do_kick = 0), forces into the staging buffer
         const int lanes = s->knobs.small_lanes ? s->knobs.small_lanes : nb_small_lanes(c.n);
         if (!s->pos_alt) HIPCHK(hipMalloc(&s->pos_alt, (size_t)nd(s) * 4));
-        if (int rc = grid_prepare(s, resolve_eval(s), true)) return rc;
+        const int rc = grid_prepare(s, resolve_eval(s), true);
+        s->prune_seeded = seeded;
+        if (rc) return rc;
         HIPCHK(nb_launch_small_step(s->pos, s->pos_alt, s->vel, s->staging, s->mass, c.n, c.dim, 0, HOOK_GRID, c.G, c.softening_sq,
                                     c.dt / 2, c.dt, NB_KICK_NONE, lanes, s->stream, s->tab, nullptr, s->bin_out));
         path = 3;
@@ -768,11 +782,14 @@ int bin_sums_eval(nb_sim *s, int which, int64_t *sum_k, int64_t *sum_kw, double 
     } else {
         EvalRequest rq;
         rq.bins = true;
-        if (int rc = force_eval(s, rq)) return rc;
+        const int rc = force_eval(s, rq);
+        // a search the read-out seeded is run again by the next evaluation: the flag stays the last evaluation's
+        s->prune_seeded = seeded;
         const bool sym = strncmp(s->last_kernel, "force_sym_kernel", 16) == 0;
+        s->last_kernel = last_kernel;                // the read-out does not change what the last evaluation ran on
+        if (rc) return rc;
         path = sym ? 1 : 2;
         shape = sym ? s->sym.r : 0;
-        if (last_small) s->last_kernel = "small_step_kernel";       // the read-out does not change what the steps run on
     }
     std::vector<unsigned long long> host(words);
     GridTables *ht = new GridTables;

@@ -397,10 +397,22 @@ class GalaxySimulation:
 
     def spin_up(self, evaluations: int):
         """Re-evaluate the forces `evaluations` times without touching the state (the result is
-        bit-identical every time): lets the GPU reach its sustained clock before a timed region."""
+        bit-identical every time): lets the GPU reach its sustained clock before a timed region.
+
+        The evaluations run on the tiled path of `_compute_accelerations`, whose sums differ in the last bits from those
+        of the one-launch step small systems take, so the device's accelerations -- what the next opening kick reads --
+        are held aside and put back, values and dtype: positions, velocities, accelerations, the cached tensors and the
+        trajectory are those of a simulation that never spun up.  (force_kernel_name() and, in the grid modes,
+        quant_debug() then describe the spin-up evaluation of the same positions.)"""
+        count = max(0, int(evaluations))
+        if count == 0 or self._empty:
+            return
         self._flush(("positions", "masses"))
-        for _ in range(max(0, int(evaluations))):
+        held = self._download("accelerations")
+        for _ in range(count):
             N.check(N.lib().nb_compute_accelerations(self._handle))
+        N.check(N.lib().nb_set_accelerations(self._handle, C.c_void_p(held.data_ptr()), _TORCH_TO_NB[held.dtype],
+                                             int(held.device.type == "cuda")))
 
     def kernel_time(self):
         """(total_ms, launches) of the force kernel since the last call (needs profile=True)."""
