@@ -60,6 +60,50 @@ __device__ __forceinline__ void classify(double x, bool &nan, bool &inf)
     }
 }
 
+// ---- far coordinates: moved where a pair loop's copy is staged, never per pair -------------------------
+// Upstream's G / r2 ** 1.5 is exactly 0 once r2 has overflowed to +inf; the kernels' rsqrt-based q^(-3/2) and q^(-1/2) are
+// inf * 0 = NaN there.  So the COPY of a coordinate that a pair loop reads (the packed arrays, an LDS tile, the target
+// registers; never the state) is moved when it lies beyond +-L: star p's far coordinate goes to the slot +-far_slot(p), the
+// way the spread padding is placed.  Slots lie above L and above every padding coordinate (fp32: L 1.2e18, padding 1e18,
+// slots 1.5e18 .. 4.5e18; fp64: L 1.2e153, spread padding up to 1.03e153, slots 1.5e153 .. 3e153) and below
+// sqrt(MAX / (4 D)), D = 3 (5.32e18, 3.87e153), so r2 = sum of D squares of differences <= 2 max-slot stays finite.  A
+// star beyond L is at least 2e17 (2e152) from every star inside L and every slot is at least 3e17 (3e152) from every
+// star inside L and from the padding: far past the distance where r^3 overflows (fp32 7e12, fp64 5.6e102), so the factor
+// is 0 upstream and underflows to exactly 0 here, before and after the move.  Two stars beyond L get different slots:
+//   fp64  1.5e153 + 1e146 p (p mod 1.5e7): any two slots are >= 1e146 apart, factor exactly 0
+//   fp32  1.5e18 + 2e15 (p mod 1500) + 1e12 (p / 1500 mod 2000): exactly 0 unless p = p' (mod 1500); then the two stars
+//         are >= 7e11 apart (1e12 less the rounding to fp32) and their mutual factor is at most (7e11)^-3 (upstream: 0) -- never the O(1) factor that
+//         two stars clamped onto one value would get from their other coordinates
+// What is lost: two stars beyond L whose true separation is below the r^3 overflow distance (fp32 numbers there are
+// 1.4e11 and more apart, so that means equal or neighbouring values; fp64: equal values) interact upstream and not here.
+// NaN stays NaN and +-inf stays +-inf (the comparisons are false for NaN).  L: NB_FAR_F64 / NB_FAR_F32 (nb_internal.h), by
+// the type of the PAIR arithmetic, not of the storage; lim = +inf switches the staging off.
+template <typename T> __device__ __forceinline__ T far_slot(int p);
+template <> __device__ __forceinline__ float far_slot<float>(int p)
+{
+    return (float)(1.5e18 + 2e15 * (double)(p % 1500) + 1e12 * (double)((p / 1500) % 2000));
+}
+template <> __device__ __forceinline__ double far_slot<double>(int p) { return 1.5e153 + 1e146 * (double)(p % 15000000); }
+// the slot follows the pair arithmetic like the limit does: fp64 storage under the fp32 limit takes the fp32 slots
+template <typename T> __device__ __forceinline__ T far_slot_for(T lim, int p)
+{
+    if constexpr (sizeof(T) == 4) return far_slot<float>(p);
+    else return lim < (T)1e100 ? (T)far_slot<float>(p) : far_slot<double>(p);
+}
+// star p's coordinate x as the pair loop is to see it (the same value wherever star p is staged, as target or as source)
+template <typename T> __device__ __forceinline__ T stage_far(T x, T lim, int p)
+{
+    if (x > lim && !non_finite(x)) return far_slot_for<T>(lim, p);
+    if (x < -lim && !non_finite(x)) return -far_slot_for<T>(lim, p);
+    return x;
+}
+// the same for a potential-energy kernel, where upstream's masked diagonal makes the sum NaN as soon as one coordinate is
+// infinite (dist_ii = sqrt(inf - inf)): +-inf becomes NaN, which every pair of that star then carries into the sum
+template <typename T> __device__ __forceinline__ T stage_far_pe(T x, T lim, int p)
+{
+    return non_finite(x) ? (T)__builtin_nanf("") : stage_far<T>(x, lim, p);
+}
+
 // ---- per-member stops of the ensemble tick path (nb_ens_run_members) -----------------------------------------------------
 // Every kernel of the tick path takes `stop` (device, one int per member, or null: no member ever stops) and the launch's
 // tick index t = ticks the call has already closed.  The kernels come in two instantiations, STOPS = false for a launch

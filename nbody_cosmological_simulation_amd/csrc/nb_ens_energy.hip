@@ -61,9 +61,12 @@ ens_energy_partials_kernel(const T *__restrict__ pos, const T *__restrict__ vel 
 
     const int j0 = tj * EE_TILE;
     const int cnt = min(EE_TILE, n - j0);            // >= 1: tj < ntiles
+    // the pair loop's copies (stage_far_pe, nb_device.h): an infinite coordinate becomes NaN, as upstream's masked diagonal
+    // makes the energy; the fp64 term's q^(-1/2) = y0 (1 + e / 2) needs a finite q, so far coordinates move to the star's slot
+    constexpr T FAR = sizeof(T) == 8 ? (T)NB_FAR_F64 : (T)__builtin_inff();
     if (tid < cnt) {
 #pragma unroll
-        for (int k = 0; k < D; ++k) sx[k][tid] = p[(size_t)(j0 + tid) * D + k];
+        for (int k = 0; k < D; ++k) sx[k][tid] = stage_far_pe<T>(p[(size_t)(j0 + tid) * D + k], FAR, j0 + tid);
         sm[tid] = m[j0 + tid];
     }
     const int i = ti * EE_TILE + tid;
@@ -71,7 +74,7 @@ ens_energy_partials_kernel(const T *__restrict__ pos, const T *__restrict__ vel 
     const int ic = live ? i : n - 1;
     T xi[D];
 #pragma unroll
-    for (int k = 0; k < D; ++k) xi[k] = p[(size_t)ic * D + k];
+    for (int k = 0; k < D; ++k) xi[k] = stage_far_pe<T>(p[(size_t)ic * D + k], FAR, ic);
     const T mi = m[ic];
     __syncthreads();
 

@@ -96,6 +96,9 @@ force_f64_kernel(const double *__restrict__ pos, const double *__restrict__ mass
                  double *__restrict__ partial, ForceGeom g, double G, double eps2, float eps2_f)
 {
     __shared__ double sj[D + 1][NB_TJ];
+    // targets and source tiles are the pair loop's own copies: a coordinate beyond +-FAR is moved to the star's slot
+    // (stage_far, nb_device.h); the fp32 limit and slots wherever r2 is formed in or cast to fp32
+    constexpr double FAR = (PAIR < 0 && QHOOK < 0) ? NB_FAR_F64 : (double)NB_FAR_F32;
 
     const int tid = threadIdx.x;
     const int ibase = blockIdx.x * (NB_BLOCK * R);
@@ -108,7 +111,7 @@ force_f64_kernel(const double *__restrict__ pos, const double *__restrict__ mass
         i = i < g.n ? i : g.n - 1;
 #pragma unroll
         for (int k = 0; k < D; ++k) {
-            xi[r][k] = pos[(size_t)i * D + k];
+            xi[r][k] = stage_far<double>(pos[(size_t)i * D + k], FAR, i);
             acc[r][k] = 0.0;
         }
     }
@@ -121,7 +124,7 @@ force_f64_kernel(const double *__restrict__ pos, const double *__restrict__ mass
             int j = jt + tid;
             j = j < j_hi ? j : j_hi - 1;
 #pragma unroll
-            for (int k = 0; k < D; ++k) sj[k][tid] = pos[(size_t)j * D + k];
+            for (int k = 0; k < D; ++k) sj[k][tid] = stage_far<double>(pos[(size_t)j * D + k], FAR, j);
             sj[D][tid] = (QHOOK >= 0) ? mass[j] : G * mass[j];
         }
         __syncthreads();
@@ -225,6 +228,9 @@ force_f32_kernel(const float *__restrict__ pos, const float *__restrict__ mass,
         est_kmax = tab->levels - 2;
     }
 
+    // the pair loop's copies: a coordinate beyond +-FAR is moved to the star's slot (stage_far, nb_device.h); not in the grid modes,
+    // whose tables come from the unclamped maximum of r2
+    const float FAR = (HOOK == HOOK_GRID) ? __builtin_inff() : NB_FAR_F32;
     float xi[R][D];
     double acc[R][D];
     long long b1[BINS ? R : 1], b2[BINS ? R : 1], bcount = 0;
@@ -234,7 +240,7 @@ force_f32_kernel(const float *__restrict__ pos, const float *__restrict__ mass,
         i = i < g.n ? i : g.n - 1;
 #pragma unroll
         for (int k = 0; k < D; ++k) {
-            xi[r][k] = pos[(size_t)i * D + k];
+            xi[r][k] = stage_far<float>(pos[(size_t)i * D + k], FAR, i);
             acc[r][k] = 0.0;
         }
         if constexpr (BINS) b1[r] = b2[r] = 0;
@@ -248,7 +254,7 @@ force_f32_kernel(const float *__restrict__ pos, const float *__restrict__ mass,
             int j = jt + tid;
             j = j < j_hi ? j : j_hi - 1;
 #pragma unroll
-            for (int k = 0; k < D; ++k) sj[k][tid] = pos[(size_t)j * D + k];
+            for (int k = 0; k < D; ++k) sj[k][tid] = stage_far<float>(pos[(size_t)j * D + k], FAR, j);
             sj[D][tid] = mass[j];
         }
         __syncthreads();

@@ -39,10 +39,13 @@ namespace {
 // which the multi-GPU / force-quantising paths cannot fuse into their reduction.
 // spread != 0 (potential energy with uniform masses, where no mass factor silences the padding): padding particle
 // number k sits at pad * (1 + k) along x, so pad-pad pairs are as far apart as pad-real ones.
+// far_lim: in the packed copy -- never in pos[] -- a coordinate beyond +-far_lim moves to the star's slot (stage_far,
+// nb_device.h; +inf: off); far_pe: the copy feeds a potential-energy kernel, where an infinite coordinate becomes NaN.
 template <typename T, int D, int KICK>
 __global__ void __launch_bounds__(NB_BLOCK)
 pack_kernel(T *__restrict__ pos, T *__restrict__ vel, const T *__restrict__ acc, const T *__restrict__ mass,
-            T *__restrict__ packed, int n, int np, T half_dt, T dt, T gfac, T pad, int p_begin, int p_end, int spread)
+            T *__restrict__ packed, int n, int np, T half_dt, T dt, T gfac, T pad, int p_begin, int p_end, int spread,
+            T far_lim, int far_pe)
 {
     const int p = p_begin + blockIdx.x * NB_BLOCK + threadIdx.x;
     if (p >= p_end) return;
@@ -59,7 +62,7 @@ pack_kernel(T *__restrict__ pos, T *__restrict__ vel, const T *__restrict__ acc,
                 vel[idx] = v;
                 pos[idx] = x;
             }
-            packed[(size_t)k * np + p] = x;
+            packed[(size_t)k * np + p] = far_pe ? stage_far_pe<T>(x, far_lim, p) : stage_far<T>(x, far_lim, p);
         }
         packed[(size_t)D * np + p] = gfac * mass[p];
     } else {
@@ -86,7 +89,7 @@ reduce_sym_kernel(const double *__restrict__ rowslab, const T *__restrict__ cols
                   const int *__restrict__ col_upto, int tile_b, int n, int np,
                   double scale, T *__restrict__ acc, T *__restrict__ vel, T half_dt, int do_kick,
                   T *__restrict__ pos, T *__restrict__ packed, T dt, int blk0, double *__restrict__ sums64,
-                  double *__restrict__ mm_part, T *__restrict__ pos_next)
+                  double *__restrict__ mm_part, T *__restrict__ pos_next, T far_lim)
 {
     __shared__ double s_part[NB_RED_WAVES][D][64];
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
@@ -153,7 +156,7 @@ reduce_sym_kernel(const double *__restrict__ rowslab, const T *__restrict__ cols
                     const T x = axpy_rn<T>(pos[idx], v, dt);
                     vel[idx] = v;
                     pos[idx] = x;
-                    packed[(size_t)k * np + p] = x;
+                    packed[(size_t)k * np + p] = stage_far<T>(x, far_lim, p);     // the pair loop's copy only (pack_kernel)
                 } else {
                     // last step of a native call: the state stays at the closing kick (what a reader must see); the
                     // positions the NEXT step drifts to go to pos_next and, packed, to the force kernel's input.  The next
@@ -162,7 +165,7 @@ reduce_sym_kernel(const double *__restrict__ rowslab, const T *__restrict__ cols
                     const T vo = axpy_rn<T>(v, a, half_dt);
                     const T x = axpy_rn<T>(pos[idx], vo, dt);
                     pos_next[idx] = x;
-                    packed[(size_t)k * np + p] = x;
+                    packed[(size_t)k * np + p] = stage_far<T>(x, far_lim, p);
                 }
             }
         }
@@ -369,13 +372,14 @@ potential_sym_kernel(const T *__restrict__ packed, const SymWork *__restrict__ w
 
 hipError_t nb_launch_pack(void *pos, void *vel, const void *acc, const void *mass, void *packed, int n, int np,
                           int dim, int is_f64, int kick, double half_dt, double dt, double gfac, int f32_pairs,
-                          hipStream_t st, int p_begin, int p_end, int spread_pad)
+                          hipStream_t st, int p_begin, int p_end, int spread_pad, int far)
 {
     if (p_end < 0) p_end = np;
     if (p_end <= p_begin) return hipSuccess;
     // padding coordinate: far enough that r^-3 vanishes, close enough that r2 stays finite in the
     // arithmetic the pair loop uses (fp32 pair arithmetic on fp64 storage needs the fp32 value)
     const double pad = (is_f64 && !f32_pairs) ? 1e150 : 1e18;
+    const double far_lim = nb_far_limit(far, is_f64 && !f32_pairs);
     const int grid = (p_end - p_begin + NB_BLOCK - 1) / NB_BLOCK;
     const int k = (kick == NB_PACK_CLOSE_OPEN || kick == NB_PACK_OPEN) ? kick : NB_PACK_NONE;
     return nb::pick<2, 3>(dim, [&](auto D) {
@@ -384,7 +388,7 @@ hipError_t nb_launch_pack(void *pos, void *vel, const void *acc, const void *mas
             return nb::pick<NB_PACK_NONE, NB_PACK_OPEN, NB_PACK_CLOSE_OPEN>(k, [&](auto K) {
                 hipLaunchKernelGGL((pack_kernel<T, D.value, K.value>), dim3(grid), dim3(NB_BLOCK), 0, st, (T *)pos, (T *)vel,
                                    (const T *)acc, (const T *)mass, (T *)packed, n, np, (T)half_dt, (T)dt, (T)gfac, (T)pad, p_begin,
-                                   p_end, spread_pad);
+                                   p_end, spread_pad, (T)far_lim, far == NB_FAR_PE ? 1 : 0);
                 return hipGetLastError();
             });
         });
@@ -467,8 +471,9 @@ hipError_t nb_launch_reduce_sym(const double *rowslab, const void *colslab, cons
                                 const int *row_nslots, const int *col_upto, int tile_b, int n,
                                 int np, int dim, int is_f64, double scale, void *acc, void *vel, double half_dt,
                                 int do_kick, void *pos, void *packed, double dt, hipStream_t st, int p_begin, int p_end,
-                                double *sums64, double *mm_part, void *pos_next)
+                                double *sums64, double *mm_part, void *pos_next, int far)
 {
+    const double far_lim = nb_far_limit(far, is_f64);      // a fused repack runs on settled dtypes: fp64 pairs on fp64 storage
     if ((do_kick & NB_KICK_MODE_MASK) == NB_KICK_CLOSE_SPEC && !pos_next) return hipErrorInvalidValue;
     if (p_end < 0 || p_end > n) p_end = n;
     if (p_end <= p_begin) return hipSuccess;
@@ -479,7 +484,7 @@ hipError_t nb_launch_reduce_sym(const double *rowslab, const void *colslab, cons
             using T = typename decltype(real)::type;
             hipLaunchKernelGGL((reduce_sym_kernel<T, D.value>), dim3(grid), dim3(64 * NB_RED_WAVES), 0, st, rowslab,
                                (const T *)colslab, row_slot0, row_nslots, col_upto, tile_b, n, np, scale, (T *)acc, (T *)vel,
-                               (T)half_dt, do_kick, (T *)pos, (T *)packed, (T)dt, blk0, sums64, mm_part, (T *)pos_next);
+                               (T)half_dt, do_kick, (T *)pos, (T *)packed, (T)dt, blk0, sums64, mm_part, (T *)pos_next, (T)far_lim);
             return hipGetLastError();
         });
     });

@@ -128,11 +128,25 @@ struct NbKernelEvents {
     hipEvent_t start = nullptr, stop = nullptr;
 };
 
+// Staging of far coordinates in the copies a pair loop reads (stage_far, nb_device.h): off in the grid
+// modes, whose tables are built from the unclamped maximum of r2; on for the forces; on, with +-inf turned into NaN, for the
+// potential energy.  nb_far_limit: the limit for fp64 or fp32 PAIR arithmetic (+inf: off).
+enum NbFar { NB_FAR_OFF = 0, NB_FAR_FORCE = 1, NB_FAR_PE = 2 };
+constexpr double NB_FAR_F64 = 1.2e153;   // > the spread padding's 1.03e153, < the first slot 1.5e153 (far_slot, nb_device.h)
+constexpr float NB_FAR_F32 = 1.2e18f;    // > the padding's 1e18, < the first slot 1.5e18
+inline double nb_far_limit(int far, bool f64_pairs)
+{
+    if (far == NB_FAR_OFF) return __builtin_inf();
+    if (far == NB_FAR_PE && !f64_pairs) return __builtin_inf();      // fp32 energy terms are 1 / sqrt(inf) = 0, as upstream's
+    return f64_pairs ? NB_FAR_F64 : (double)NB_FAR_F32;
+}
+
 // pack positions + mass factors into padded component arrays
 hipError_t nb_launch_pack(void *pos, void *vel, const void *acc, const void *mass, void *packed, int n, int np,
                           int dim, int is_f64, int kick /* NbPackKick */, double half_dt, double dt, double gfac, int f32_pairs,
                           hipStream_t st, int p_begin = 0, int p_end = -1 /* packed entries [p_begin, p_end); -1 = np */,
-                          int spread_pad = 0 /* padding particles at distinct far positions (uniform-mass potential energy) */);
+                          int spread_pad = 0 /* padding particles at distinct far positions (uniform-mass potential energy) */,
+                          int far = NB_FAR_FORCE /* NbFar */);
 hipError_t nb_launch_force_sym_f64(const double *packed, const SymWork *work, int nwork, double *rowslab,
                                    double *colslab, int np, int dim, int r, int uniform, int pa_f32, double eps2,
                                    hipStream_t st, NbKernelEvents ev = {}, int rowsplit = 0 /* row-split work items (nb_plan.cpp) */,
@@ -153,7 +167,7 @@ hipError_t nb_launch_reduce_sym(const double *rowslab, const void *colslab, cons
                                 int p_begin = 0, int p_end = -1 /* particles [p_begin, p_end); -1 = n */,
                                 double *sums64 = nullptr /* instead of acc / kicks: the unscaled, unrounded fp64 sums */,
                                 double *mm_part = nullptr /* per-workgroup {min, max} of the forces written (whole-range launches) */,
-                                void *pos_next = nullptr /* NB_KICK_CLOSE_SPEC */);
+                                void *pos_next = nullptr /* NB_KICK_CLOSE_SPEC */, int far = NB_FAR_FORCE /* NbFar: the repack */);
 // fp32 state, multi-GPU: acc = (float)(sums64 * scale) after the ranks' fp64 sums were added (force quantisation follows)
 hipError_t nb_launch_finish_sums64(const double *sums64, double scale, float *acc, int64_t count, hipStream_t st);
 
@@ -280,6 +294,7 @@ struct NbP2PKick {
     double scale;                  //   result = (float)(sum * scale)
     void *vel, *pos, *packed;      // storage type of the force vector; packed may be null (one-sided kernels)
     double half_dt, dt;
+    double far_lim;                // saturation of the repacked coordinates (nb_far_limit; read with a mode only)
 };
 hipError_t nb_p2p_allreduce(void *dst, size_t count, int is_f64, double timeout_s, hipStream_t st,
                             const NbP2PKick *kick = nullptr);

@@ -469,9 +469,13 @@ potential_kernel(const T *__restrict__ pos, const T *__restrict__ mass, ForceGeo
     const int tid = threadIdx.x;
     const int i = blockIdx.x * NB_BLOCK + tid;
     const int ic = i < g.n ? i : g.n - 1;
+    // the pair loop's copies of the coordinates (stage_far_pe, nb_device.h): an infinite one becomes NaN -- upstream's masked
+    // diagonal makes the energy NaN then -- and the fp64 terms' q^(-1/2) = y0 (1 + ...) needs a finite q: far coordinates
+    // move to the star's slot (the fp32 terms divide by a root and need no limit)
+    constexpr T FAR = (PA_F32 || sizeof(T) == 4) ? (T)__builtin_inff() : (T)NB_FAR_F64;
     T xi[D];
 #pragma unroll
-    for (int k = 0; k < D; ++k) xi[k] = pos[(size_t)ic * D + k];
+    for (int k = 0; k < D; ++k) xi[k] = nbdev::stage_far_pe<T>(pos[(size_t)ic * D + k], FAR, ic);
     const T mi = (i < g.n) ? mass[ic] : (T)0;
 
     const int j_lo = g.j_begin + blockIdx.y * g.chunk_len;
@@ -485,7 +489,7 @@ potential_kernel(const T *__restrict__ pos, const T *__restrict__ mass, ForceGeo
             int j = jt + tid;
             j = j < j_hi ? j : j_hi - 1;
 #pragma unroll
-            for (int k = 0; k < D; ++k) sj[k][tid] = pos[(size_t)j * D + k];
+            for (int k = 0; k < D; ++k) sj[k][tid] = nbdev::stage_far_pe<T>(pos[(size_t)j * D + k], FAR, j);
             sj[D][tid] = mass[j];
         }
         __syncthreads();

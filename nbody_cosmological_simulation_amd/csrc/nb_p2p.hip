@@ -23,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include "nb_device.h"
 #include "nb_internal.h"
 
 namespace {
@@ -61,6 +62,7 @@ struct P2PArgs {
     int kick, dim, np;
     void *vel, *pos, *packed;
     double half_dt, dt;
+    double far_lim;             // stage_far limit of the repacked coordinates (+inf: off)
     int f64_to_f32;             // the units are fp64 sums; dst / vel / pos / packed are fp32: result = (float)(sum * scale)
     double scale;
 };
@@ -166,7 +168,7 @@ __device__ __forceinline__ void p2p_leapfrog(const P2PArgs &a, long long e, T f)
             x = (T)__fadd_rn((float)pos[e], __fmul_rn((float)v, (float)a.dt));
         }
         pos[e] = x;
-        if (a.packed) ((T *)a.packed)[(size_t)(e % a.dim) * a.np + e / a.dim] = x;
+        if (a.packed) ((T *)a.packed)[(size_t)(e % a.dim) * a.np + e / a.dim] = nbdev::stage_far<T>(x, (T)a.far_lim, (int)(e / a.dim));
     }
     vel[e] = v;
 }
@@ -336,12 +338,12 @@ size_t nb_p2p_handle_bytes() { return sizeof(hipIpcMemHandle_t); }
 static void p2p_set_kick(P2PArgs &a, const NbP2PKick *k)
 {
     a.kick = NB_KICK_NONE; a.dim = 1; a.np = 0; a.vel = a.pos = a.packed = nullptr; a.half_dt = a.dt = 0.0;
-    a.f64_to_f32 = 0; a.scale = 1.0;
+    a.f64_to_f32 = 0; a.scale = 1.0; a.far_lim = __builtin_inf();
     if (k) {
         a.f64_to_f32 = k->f64_to_f32; a.scale = k->scale;
         if (k->mode != NB_KICK_NONE) {
             a.kick = k->mode; a.dim = k->dim; a.np = k->np; a.vel = k->vel; a.pos = k->pos; a.packed = k->packed;
-            a.half_dt = k->half_dt; a.dt = k->dt;
+            a.half_dt = k->half_dt; a.dt = k->dt; a.far_lim = k->far_lim;
         }
     }
 }

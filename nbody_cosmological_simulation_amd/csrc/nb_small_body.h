@@ -50,9 +50,16 @@ __device__ __forceinline__ void small_step_body(int blk, const T *pos_in, T *pos
     const int i_raw = blk * TG + grp;
     const bool live = i_raw < n;
     const int i = live ? i_raw : n - 1;
-    T xi[D];
+    // xi: the state (the drift below starts from it); xc and the LDS tile: the pair loop's copies, a coordinate beyond
+    // +-FAR moved to the star's slot (stage_far, nb_device.h): a runaway star's r2 stays finite and its factor underflows
+    // to 0 like the padding's
+    constexpr T FAR = F64 ? (T)NB_FAR_F64 : (T)NB_FAR_F32;
+    T xi[D], xc[D];
 #pragma unroll
-    for (int k = 0; k < D; ++k) xi[k] = pos_in[(size_t)i * D + k];
+    for (int k = 0; k < D; ++k) {
+        xi[k] = pos_in[(size_t)i * D + k];
+        xc[k] = stage_far<T>(xi[k], FAR, i);
+    }
     double a[D];
 #pragma unroll
     for (int k = 0; k < D; ++k) a[k] = 0.0;
@@ -68,7 +75,7 @@ __device__ __forceinline__ void small_step_body(int blk, const T *pos_in, T *pos
             const int j = j0 + t;
             if (j < n) {
 #pragma unroll
-                for (int k = 0; k < D; ++k) sx[k][t] = pos_in[(size_t)j * D + k];
+                for (int k = 0; k < D; ++k) sx[k][t] = stage_far<T>(pos_in[(size_t)j * D + k], FAR, j);
                 sg[t] = F64 ? (T)(G * mass[j]) : mass[j];
             } else {
 #pragma unroll
@@ -83,7 +90,7 @@ __device__ __forceinline__ void small_step_body(int blk, const T *pos_in, T *pos
             T d[D];
             if constexpr (F64) {
 #pragma unroll
-                for (int k = 0; k < D; ++k) d[k] = sx[k][jj] - xi[k];
+                for (int k = 0; k < D; ++k) d[k] = sx[k][jj] - xc[k];
                 double q = __builtin_fma(d[D - 1], d[D - 1], eps2);
 #pragma unroll
                 for (int k = D - 2; k >= 0; --k) q = __builtin_fma(d[k], d[k], q);
@@ -92,7 +99,7 @@ __device__ __forceinline__ void small_step_body(int blk, const T *pos_in, T *pos
                 for (int k = 0; k < D; ++k) a[k] = __builtin_fma(w, d[k], a[k]);
             } else {
 #pragma unroll
-                for (int k = 0; k < D; ++k) d[k] = __fsub_rn(sx[k][jj], xi[k]);
+                for (int k = 0; k < D; ++k) d[k] = __fsub_rn(sx[k][jj], xc[k]);
                 float q = r2_f32_exact<D>(d, eps2);
                 if (HOOK == HOOK_BF16) q = round_bf16(q);
                 if (HOOK == HOOK_F16) q = round_f16(q);

@@ -359,7 +359,7 @@ int launch_pairs(nb_sim *s, const EvalRequest &rq, const Eval &e)
         // the packed mass factor carries G, except in grid modes, whose table already does (simulation.py:101)
         const double gfac = s->is_f64 ? c.G : (grid ? 1.0 : (double)(float)c.G);
         HIPCHK(nb_launch_pack(s->pos, s->vel, s->acc, s->mass, sp.packed, c.n, sp.np, c.dim, s->is_f64, NB_PACK_NONE, 0.0, 0.0,
-                              gfac, pa_f32, s->stream));
+                              gfac, pa_f32, s->stream, 0, -1, 0, grid ? NB_FAR_OFF : NB_FAR_FORCE));
     }
     if (int rc = prof_begin(s, &slot, false)) return rc;
     if (s->is_f64) {
@@ -426,7 +426,8 @@ int reduce_and_exchange(nb_sim *s, const EvalRequest &rq, Eval &e, EvalResult *r
         if (rq.open_on_read) kmode |= NB_KICK_OPEN_ON_READ;
         HIPCHK(nb_launch_reduce_sym(sp.rowslab, sp.colslab, sp.row_slot0, sp.row_nslots, sp.col_upto, sp.tile_b, c.n, sp.np,
                                     c.dim, s->is_f64, e.scale, red_out, s->vel, c.dt / 2, kmode, s->pos, sp.packed, c.dt,
-                                    s->stream, 0, -1, sums64, e.red_mm ? s->scalars + 8 : nullptr, s->pos_alt));
+                                    s->stream, 0, -1, sums64, e.red_mm ? s->scalars + 8 : nullptr, s->pos_alt,
+                                    grid_mode(c.mode) ? NB_FAR_OFF : NB_FAR_FORCE));
         site_set(res, "reduce_sym", kmode);
         if (spec) { s->spec_open = true; s->spec_kind = 2; s->spec_dt = c.dt; }
     }
@@ -443,6 +444,7 @@ int reduce_and_exchange(nb_sim *s, const EvalRequest &rq, Eval &e, EvalResult *r
             kk.dim = c.dim; kk.np = e.used_sym ? s->sym.np : 0;
             kk.vel = s->vel; kk.pos = s->pos; kk.packed = e.used_sym ? (void *)s->sym.packed : nullptr;
             kk.half_dt = c.dt / 2; kk.dt = c.dt;
+            kk.far_lim = nb_far_limit(grid_mode(c.mode) ? NB_FAR_OFF : NB_FAR_FORCE, s->is_f64);
             e.kicked = true;
             res->opened = rq.open_next;
         }
@@ -690,7 +692,7 @@ int energy_eval(nb_sim *s, double *kinetic, double *potential)
             pe_uniform = s->mass_uniform;
             if (s->spec_kind == 2) s->spec_open = false;      // `packed` (the speculative next positions with it) is rewritten here
             HIPCHK(nb_launch_pack(s->pos, s->vel, s->acc, s->mass, sp.packed, c.n, sp.np, c.dim, s->is_f64, 0, 0.0, 0.0,
-                                  1.0, s->is_f64 && s->logical[0] != NB_F64, s->stream, 0, -1, pe_uniform ? 1 : 0));
+                                  1.0, s->is_f64 && s->logical[0] != NB_F64, s->stream, 0, -1, pe_uniform ? 1 : 0, NB_FAR_PE));
             HIPCHK(nb_launch_potential_sym(sp.packed, sp.work, sp.nwork, s->scratch, sp.np, c.dim, sp.r, s->is_f64,
                                            s->logical[0] != NB_F64, s->logical[2], c.softening_sq, pe_uniform ? 1 : 0,
                                            s->stream));

@@ -470,6 +470,18 @@ double nbo_kinetic_energy(int n, int d, int V, const double *vel, int M, const d
     return rnd(T, scalar_mul(T, 0.5) * sum);
 }
 
+/* the masked diagonal of simulation.py:189-190, (m_i m_i * 0) / dist_ii: NaN for a star with a non-finite coordinate
+ * (dist_ii is NaN) or a mass whose square is not finite */
+static int pe_diagonal_is_nan(int n, int d, const double *pos, int MP, const double *mass)
+{
+    for (int i = 0; i < n; ++i) {
+        if (!isfinite(rnd(MP, mass[i] * mass[i]))) return 1;
+        for (int k = 0; k < d; ++k)
+            if (!isfinite(pos[(long)i * d + k])) return 1;
+    }
+    return 0;
+}
+
 /* simulation.py:176-192 ; partial over sources j in [j0,j1) (pairs i<j). */
 double nbo_potential_energy(int n, int d, int P, const double *pos, int M, const double *mass,
                             double G, double eps2_py, int j0, int j1)
@@ -500,6 +512,9 @@ double nbo_potential_energy(int n, int d, int P, const double *pos, int M, const
      * which is NaN where dist == 0 -- on the whole diagonal when the softening rounds to zero in the positions'
      * dtype (softening 0, or 1e-4 with float16 positions).  For a non-zero softening dist > 0 everywhere. */
     if (n > 0 && j0 == 0 && scalar_as(P, eps2_py) == 0.0) return NAN;
+    /* ... and where dist is NaN: a star with a NaN or infinite coordinate has diff = x - x = NaN against itself, so its
+     * masked diagonal entry is 0 / NaN; a mass whose square is not finite gives (inf or NaN) * 0 there (g23). */
+    if (j0 == 0 && pe_diagonal_is_nan(n, d, pos, MP, mass)) return NAN;
     total = rnd(T, total);
     return rnd(T, scalar_mul(T, -G) * total);
 }
@@ -655,6 +670,7 @@ double nbo_potential_energy_f64_fast(int n, int d, const double *pos, const doub
         }
         total += part;
     }
+    if (pe_diagonal_is_nan(n, d, pos, NBO_F64, mass)) return NAN;
     return -G * total;
 }
 

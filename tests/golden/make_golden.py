@@ -38,6 +38,7 @@ What is captured:
       stored g13 / g16 positions: what nb_quant_bin_sums reads out of the production pair loops.
   G21 the reference against ITSELF under a reversed summation order (its own code on the flipped particle order): noise
       floor of the grid-mode trajectories (N = 1024 / 4096, three steps) and of INT8 / INT4 on half-typed state.
+  G23 edge values (tests/edge_cases.py: NaN / infinite / runaway coordinates, massless stars, a NaN mass) at N = 48.
   G7  half-typed state (float16 / bfloat16 tensors) through the cast modes and FLOAT64: energies before
       and after the promotion, state after three steps.
 
@@ -1067,7 +1068,41 @@ def g14():
     print("G14", out)
 
 
+def g23_edge_values():
+    """Edge values through the stock class: every kind of tests/edge_cases.py (NaN / infinite / runaway coordinates,
+    two runaways on one side, massless stars, a NaN mass) at N = 48, edge star n - 1, in 2-D and 3-D, fp32 and fp64 inputs, all seven modes.
+    Per (dim, input dtype) group: the inputs of every kind, and per (kind, mode) the accelerations, both energies and
+    the state after two steps, stacked along the first axis in the order of `cases`."""
+    sys.path.insert(0, os.path.dirname(OUT))
+    import edge_cases as E
+    n = 48
+    out = {"kinds": np.array(E.KINDS), "modes": np.array([m.value for m in MODES])}
+    for dim in (2, 3):
+        for f64 in (False, True):
+            grp = f"d{dim}/{'f64' if f64 else 'f32'}"
+            ins = [E.make(kind, n, dim, 23 + dim, f64, idx=E.variants(kind, n, every_index=False)[0]) for kind in E.KINDS]
+            for k, name in enumerate(("pos", "vel", "mass")):
+                out[f"{grp}/{name}"] = np.stack([c[k] for c in ins])
+            rec = {key: [] for key in ("acc0", "e0", "pos2", "vel2", "e2")}
+            for pos, vel, mass, _ in ins:
+                for mode in MODES:
+                    sim = ref_sim.GalaxySimulation(torch.from_numpy(pos.copy()), torch.from_numpy(vel.copy()),
+                                                   torch.from_numpy(mass.copy()), precision_mode=mode, G=0.001, dt=0.01,
+                                                   softening=0.1)
+                    rec["acc0"].append(npy(sim.accelerations).astype(np.float64))
+                    rec["e0"].append([sim.get_kinetic_energy(), sim.get_potential_energy()])
+                    sim.step()
+                    sim.step()
+                    rec["pos2"].append(npy(sim.positions).astype(np.float64))
+                    rec["vel2"].append(npy(sim.velocities).astype(np.float64))
+                    rec["e2"].append([sim.get_kinetic_energy(), sim.get_potential_energy()])
+            for key, rows in rec.items():
+                out[f"{grp}/{key}"] = np.array(rows, np.float64)
+    np.savez_compressed(os.path.join(OUT, "g23_edge_values.npz"), **out)
+    print("G23 done")
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g1c", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21"]
+    which = sys.argv[1:] or ["g1", "g1c", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20", "g21", "g23_edge_values"]
     for w in which:
         globals()[w]()

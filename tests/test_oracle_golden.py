@@ -384,6 +384,62 @@ def test_g9_degenerate_systems(idx):
     _g9_check(lambda p, v, m, mode: O.OracleSim(p, v, m, mode), str(g["cases"][idx]), g)
 
 
+G23_GROUPS = [(dim, f64) for dim in (2, 3) for f64 in (False, True)]
+
+
+@pytest.mark.parametrize("kind_idx", range(10))
+@pytest.mark.parametrize("dim,f64", G23_GROUPS, ids=[f"d{d}-{'f64' if f else 'f32'}" for d, f in G23_GROUPS])
+def test_g23_edge_values(dim, f64, kind_idx):
+    """NaN / infinite / runaway coordinates, massless stars and a NaN mass (tests/edge_cases.py) through the stock class
+    at N = 48, every mode (reference run, g23): the oracle puts NaN, +inf and -inf where the reference does and agrees on
+    the finite values at g9's bars.  The inputs are the stored ones; edge_cases.make must still produce them."""
+    import edge_cases as E
+    g = load_golden("g23_edge_values.npz")
+    kind = E.KINDS[kind_idx]
+    assert list(g["kinds"]) == list(E.KINDS) and list(g["modes"]) == MODES
+    grp = f"d{dim}/{'f64' if f64 else 'f32'}"
+    pos, vel, mass = (g[f"{grp}/{name}"][kind_idx] for name in ("pos", "vel", "mass"))
+    again = E.make(kind, 48, dim, 23 + dim, f64, idx=E.variants(kind, 48, every_index=False)[0])
+    for a, b in zip((pos, vel, mass), again[:3]):
+        assert a.dtype == b.dtype and np.array_equal(a, b, equal_nan=True), (kind, grp)
+    for m, mode in enumerate(MODES):
+        row = kind_idx * len(MODES) + m
+        sim = O.OracleSim(pos, vel, mass, mode)
+        m64 = mode == "float64"
+        what = f"{grp} {mode}"
+        E.compare(sim.accelerations, g[f"{grp}/acc0"][row], 1e-13 if m64 else 2e-6, kind, what + " acc0")
+        E.compare([sim.get_kinetic_energy(), sim.get_potential_energy()], g[f"{grp}/e0"][row], 2e-6, kind, what + " e0")
+        sim.run(2)
+        E.compare(sim.positions, g[f"{grp}/pos2"][row], 1e-13 if m64 else 1e-6, kind, what + " pos2")
+        if kind in E.FAR_KINDS:      # the far coordinate is the array maximum: the other stars on their own
+            rest = np.delete(np.arange(48), list(again[3]))
+            E.compare(np.asarray(sim.positions)[rest], g[f"{grp}/pos2"][row][rest], 1e-13 if m64 else 1e-6, kind, what + " pos2 rest")
+        E.compare(sim.velocities, g[f"{grp}/vel2"][row], 1e-12 if m64 else 1e-6, kind, what + " vel2")
+        E.compare([sim.get_kinetic_energy(), sim.get_potential_energy()], g[f"{grp}/e2"][row], 1e-12 if m64 else 2e-6, kind,
+                  what + " e2")
+
+
+def test_edge_compare_counts_what_it_leaves_out():
+    """compare() fails when the engine misses a NaN the oracle has (an edge value written where nothing reads it), when
+    an infinity has the wrong sign, and when a finite value is off; the inf-coord allowance covers forces only."""
+    import edge_cases as E
+    ref = np.array([[1.0, np.nan], [np.inf, -2.0], [-np.inf, 0.5]])
+    assert E.compare(ref.copy(), ref, 1e-13, "nan-coord") == 0.0
+    for at, value in (((0, 1), 3.0), ((1, 0), -np.inf), ((2, 0), np.nan), ((0, 0), np.nan), ((2, 1), 0.5 + 1e-12)):
+        got = ref.copy()
+        got[at] = value
+        with pytest.raises(AssertionError):
+            E.compare(got, ref, 1e-13, "nan-coord")
+    got = ref.copy()
+    got[0, 0] = np.nan                                  # NaN where the oracle is finite: forces of inf-coord only
+    assert E.compare(got, ref, 1e-13, "inf-coord", from_forces=True) == 0.0
+    with pytest.raises(AssertionError):
+        E.compare(got, ref, 1e-13, "inf-coord")
+    got[0, 1] = 1.0                                     # ... and never finite where the oracle is NaN
+    with pytest.raises(AssertionError):
+        E.compare(got, ref, 1e-13, "inf-coord", from_forces=True)
+
+
 def _g10_check(fns, g, name):
     """fns: (quantize_distance_squared, quantize_force, grid_quantize_safe, grid_quantize) taking numpy arrays."""
     qd2, qf, safe, lin = fns
