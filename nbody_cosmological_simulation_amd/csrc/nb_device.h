@@ -137,6 +137,51 @@ __device__ __forceinline__ bool ens_still_running(const int *stop, const int *ha
     return stop[b] >= t && halted[b] == 0;
 }
 
+// ---- workgroup reductions and the arrival count (the grid's bounds, nb_grid.hip) -----------------------------------------
+// Integer max / min, and fmaxf of values that are never NaN, do not depend on the order of the operands: whatever order
+// the lanes, the waves and the workgroups are folded in, the result has the same bits.
+struct MaxOp {
+    static __device__ __forceinline__ unsigned int apply(unsigned int a, unsigned int b) { return max(a, b); }
+    static __device__ __forceinline__ unsigned long long apply(unsigned long long a, unsigned long long b) { return b > a ? b : a; }
+    static __device__ __forceinline__ float apply(float a, float b) { return fmaxf(a, b); }
+};
+struct MinOp {
+    static __device__ __forceinline__ unsigned int apply(unsigned int a, unsigned int b) { return min(a, b); }
+};
+// Op over the WAVES * 64 threads of the workgroup (all of them call it): butterfly inside the wave, one slot per wave,
+// thread 0 folds the slots in wave order and hands the result to use(result): the result exists on THREAD 0 ONLY, and
+// what is done with it (the workgroup's one atomic, as a rule) stands in the same branch as the fold.  Contains one
+// barrier, between the slot stores and the fold; the caller owes a barrier before it writes `slots` again.
+template <typename Op, int WAVES, typename T, typename F>
+__device__ __forceinline__ void block_reduce_t0(T v, T *slots, F &&use)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = Op::apply(v, __shfl_xor(v, off, 64));
+    if ((threadIdx.x & 63) == 0) slots[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        v = slots[0];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) v = Op::apply(v, slots[w]);
+        use(v);
+    }
+}
+
+// "The last workgroup to arrive does the rest": every thread of every workgroup calls it once per launch when the
+// workgroup's results are written (behind a barrier of the caller's where more than thread 0 wrote them); thread 0 fences
+// and counts the arrival at *counter, and the answer -- true in the one workgroup that arrives as number `total`, which
+// then sees what all the others wrote -- is block-uniform (one barrier inside).  The last workgroup puts *counter back.
+__device__ __forceinline__ bool last_block_arrives(unsigned int *counter, unsigned int total)
+{
+    __shared__ int s_last;
+    if (threadIdx.x == 0) {
+        __threadfence();
+        s_last = (atomicAdd(counter, 1u) == total - 1) ? 1 : 0;
+    }
+    __syncthreads();
+    return s_last != 0;
+}
+
 // ---- the force kernels' helpers ------------------------------------------------------------------------------------------
 
 __device__ __forceinline__ float round_bf16(float x) { return (float)(__bf16)x; }

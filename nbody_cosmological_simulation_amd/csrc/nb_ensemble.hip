@@ -7,7 +7,7 @@
 // its member's slice of contiguous (B, N, D) / (B, N) buffers with the member's own scalars.  No arithmetic crosses
 // members, and a member's sums are rounded in the solo order (same lanes per target, same workgroup size).
 // The grid modes (INT8 / INT4 / CUSTOM) run small_grid_body the same way, each member with its own tables
-// (ens_grid_step_kernel); their max-r2 + tables launch is ens_r2max_tables_kernel (nb_force.hip) and the INT8 / INT4 force
+// (ens_grid_step_kernel); their max-r2 + tables launch is ens_r2max_tables_kernel (nb_grid.hip) and the INT8 / INT4 force
 // snap ens_force_quant_finish_kernel (nb_misc.hip).
 //
 // Per-member stops (nb_ens_run_members): every kernel of the tick path takes `stop` and the launch's tick index t and comes

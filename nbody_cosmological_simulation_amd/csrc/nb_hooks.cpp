@@ -4,7 +4,7 @@
 //     overrides of the reference call once per step on an N x N tensor;
 //   * the diagnostics of metrics.py:25-156 on caller tensors (nb_metrics_tensors) and on a handle's resident state
 //     (nb_metrics).
-// Kernels: nb_misc.hip / nb_force.hip (hooks), nb_metrics.hip + nb_sort.hip (diagnostics).
+// Kernels: nb_misc.hip / nb_grid.hip (hooks), nb_metrics.hip + nb_sort.hip (diagnostics).
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
@@ -169,7 +169,7 @@ int nb_grid_quantize_safe(int device, const void *in, void *out, int64_t count, 
         // (five short launches: below ~2 M elements the three library calls per element are quicker -- measured
         // 21.8 vs 30.4 us at 1024 x 1024, 200 vs 55 us at 4096 x 4096)
         if (dtype == NB_F32 && levels <= NB_MAX_LUT && count >= (int64_t)1 << 21 && !slow_hook) {
-            // plain min / max (log is monotone), tables for these bounds, one lookup pass (nb_force.hip)
+            // plain min / max (log is monotone), tables for these bounds, one lookup pass (nb_grid.hip)
             GridTables *tab = (GridTables *)((char *)sc + (((2 + 2 * NB_MINMAX_BLOCKS) * sizeof(double) + 255) & ~(size_t)255));
             HIPCHK(nb_launch_minmax_generic(din, 0, count, 0, 0.0, sc, sc + 2, st));
             HIPCHK(nb_launch_grid_quantize_safe_tab((const float *)din, (float *)dout, count, levels, (float)min_val, sc, tab, st));

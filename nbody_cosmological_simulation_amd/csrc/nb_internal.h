@@ -1,5 +1,5 @@
 // nb_internal.h -- shared declarations between the C-ABI layer (nb_api.cpp) and the HIP
-// kernels (nb_force.hip, nb_misc.hip).  gfx950 only; no portability layer.
+// kernels (nb_force.hip, nb_grid.hip, nb_misc.hip).  gfx950 only; no portability layer.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -60,7 +60,7 @@ inline int nb_lut_pad(int levels)
 }
 inline size_t nb_lut_lds_bytes(int levels) { return 2 * (size_t)(nb_lut_pad(levels) + 1) * sizeof(float); }
 
-// Scratch of the pruned max-r2 search (nb_force.hip "K2 with pruning").
+// Scratch of the pruned max-r2 search (nb_grid.hip "K2 with pruning"; prune_rearm there puts it back to rest).
 struct PruneState {
     unsigned int box_min[3];  // ordered-integer keys of the coordinate minima / maxima (bounding box)
     unsigned int box_max[3];

@@ -166,7 +166,7 @@ __device__ __forceinline__ void small_step_body(int blk, const T *pos_in, T *pos
 }
 
 // The grid hook (INT8 / INT4 / CUSTOM up to NB_LUT_MIN levels; fp32 state): the same workgroup of the step with the
-// evaluation's tables (*tab: nb_force.hip grid_tables_body) staged in LDS and a pair's factor taken table-free when no
+// evaluation's tables (*tab: nb_grid.hip grid_tables_body) staged in LDS and a pair's factor taken table-free when no
 // pair of its WAVE sits on a bin edge -- so a pair's factor depends on which pairs share its wave,
 // and every caller keeps the lane layout: BS threads, S lanes per target, four sources per lane and iteration.
 // BINS: the same body with the quant-bin read-out -- per-target integer checksums s1 = sum_j k,
@@ -184,7 +184,7 @@ __device__ __forceinline__ void small_grid_body(int blk, const float *pos_in, fl
     constexpr int TG = BS / S;                       // targets per workgroup
     __shared__ T sx[D][SM_TILE];
     __shared__ T sg[SM_TILE];                        // G * m_j (fp32: the reference's (1/p * G) * m_j order is kept below)
-    // grid hook (INT8 / INT4 / CUSTOM up to 256 levels): the evaluation's tables (nb_force.hip grid_tables_kernel)
+    // grid hook (INT8 / INT4 / CUSTOM up to 256 levels): the evaluation's tables (nb_grid.hip grid_tables_kernel)
     __shared__ float s_thr[NB_LUT_MIN + 1], s_lut[NB_LUT_MIN + 1];
     const int tid = threadIdx.x;
     bool g_fast = false, g_est = false, g_deg = false;

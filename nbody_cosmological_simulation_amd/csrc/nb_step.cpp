@@ -287,7 +287,7 @@ int force_eval_generic(nb_sim *s, const EvalRequest &rq, const Eval &e, EvalResu
 // This evaluation's grid (fp32 storage, HOOK_GRID): the maximum of r2 over all pairs, then the threshold / factor tables.
 // tab->r2max_bits is 0 here: zeroed at creation, put back by grid_tables_kernel after each use.
 //   tracked   after a seeding evaluation: the farthest pair of the predecessor gives the lower bound, so two launches
-//             (filter, scan + tables) replace the search (exact either way, nb_force.hip).  Single GPU or every rank
+//             (filter, scan + tables) replace the search (exact either way, nb_grid.hip).  Single GPU or every rank
 //             redundantly; not for comm-less shards, whose first evaluation is their only one.
 //   small     the one-launch step's all-pairs pass; up to small_fuse_tables_max_n the same launch builds the tables
 //             (measured, INT4: N = 1024 22.5 -> 18.6 us per step; N = 3000 30.8 vs 31.7: there the fused kernel's

@@ -4,7 +4,7 @@ Reference: quantization.py:10-189.  The enum, the string helpers and the functio
 signatures/defaults are identical; the tensor-in/tensor-out functions run as HIP kernels
 through the C-ABI (include/nbody_amd.h: nb_quantize_distance_squared, nb_quantize_force,
 nb_grid_quantize, nb_grid_quantize_safe).  Inside GalaxySimulation the same hooks are fused
-into the pair loop (csrc/nb_force.hip); these standalone versions exist for the subclasses
+into the pair loop (csrc/nb_force.hip, the grid's tables from csrc/nb_grid.hip); these standalone versions exist for the subclasses
 that override `_compute_accelerations` (sensitivity_test.py:55-76 and its clones).
 
 No CPU fallback: without the HIP library / a GPU these functions raise.

@@ -14,7 +14,7 @@ What may be skipped, and why (every mask is computed from the reference alone):
   linear grid     nothing: only IEEE add, sub, mul, div, round, min and max are involved.
 
 The placement indices MIRROR nb_launch_minmax_generic and ew_grid (csrc/nb_misc.hip) and
-nb_launch_grid_quantize_safe_tab (csrc/nb_force.hip); test_oracle_golden.py reads the constants out of those sources,
+nb_launch_grid_quantize_safe_tab (csrc/nb_grid.hip); test_oracle_golden.py reads the constants out of those sources,
 so a change of the launch shape shows up as a failing precondition test and not as a placement that silently tests
 nothing.
 """

@@ -1,6 +1,6 @@
 """The tensor-level precision hooks (quantize_distance_squared, quantize_force, _grid_quantize, _grid_quantize_safe:
 csrc/nb_hooks.cpp, the min/max, cast and quantise kernels of csrc/nb_misc.hip, grid_quantize_safe_tab_kernel of
-csrc/nb_force.hip) element by element.
+csrc/nb_grid.hip) element by element.
 
 The max-norm bars of test_gpu_parity.py cannot see a small element that lands in the wrong bin next to a maximum of
 5e4.  Here every element is compared:

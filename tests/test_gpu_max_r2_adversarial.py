@@ -1,4 +1,4 @@
-"""The pruned and the tracked max-r2 search (nb_force.hip) on clouds that are tight against the softening, and on
+"""The pruned and the tracked max-r2 search (nb_grid.hip) on clouds that are tight against the softening, and on
 non-finite input.
 
 The grid modes need the fp32 maximum of r2 = (dx*dx + dy*dy [+ dz*dz]) + eps2 over all pairs.  Above N = 3072 (fp32
@@ -142,14 +142,14 @@ CASES = _cases()
 ORACLE_CASES = {("ring", 1e-3, 0.1, 2, 0.0), ("ball", 1e-3, 1.0, 3, 0.0), ("two", 1e-3, 1.0, 2, 1000.0)}
 
 
-def _make(nb, monkeypatch, pos, mode, soft, no_prune):
+def _make(nb, monkeypatch, pos, mode, soft, no_prune, levels=None):
     if no_prune:
         monkeypatch.setenv("NB_NO_PRUNE", "1")          # read when the handle is created
     else:
         monkeypatch.delenv("NB_NO_PRUNE", raising=False)
     n, d = pos.shape
     sim = nb.GalaxySimulation(T(pos), torch.zeros(n, d), torch.ones(n), precision_mode=nb.PrecisionMode(mode), G=G,
-                              softening=soft)
+                              softening=soft, custom_levels=levels)
     monkeypatch.delenv("NB_NO_PRUNE", raising=False)
     assert sim.force_kernel_name() != "small_step_kernel"
     return sim
@@ -186,6 +186,31 @@ def test_max_r2_searches_on_tight_clouds(nb, monkeypatch, case):
             from oracle import oracle as O
             _, dbg = O.accelerations(pos, np.ones(N, np.float32), mode, G=G, softening=soft, debug=True)
             assert np.float32(l_s) == np.float32(dbg["lmax"]), (l_s, dbg["lmax"])
+
+
+@pytest.mark.parametrize("d", [2, 3])
+def test_tracked_search_hands_its_maximum_to_multi_block_tables(nb, monkeypatch, d):
+    """A grid of 1000 levels is more than one workgroup of tables: the tracked scan's last workgroup stores the maximum
+    and the tables kernel follows with its arrival count, instead of the scan building the tables itself.  First
+    evaluation and three steps of the gauss cloud at radius 4: r2max equals the host's fp32 all-pairs maximum at every
+    read, and r2max, lmax and the trajectory are those of the all-pairs handle bit for bit."""
+    soft = 0.1
+    pos = _positions("gauss", d, 4.0, 0.0)
+    eps2 = _eps2(soft)
+    sim = _make(nb, monkeypatch, pos, nb.PrecisionMode.CUSTOM, soft, no_prune=False, levels=1000)
+    ref = _make(nb, monkeypatch, pos, nb.PrecisionMode.CUSTOM, soft, no_prune=True, levels=1000)
+    for read in range(4):
+        if read:
+            sim.run(1)
+            ref.run(1)
+        r_s, l_s, x_s = _read(sim)
+        r_r, l_r, x_r = _read(ref)
+        want = _exact_r2max_f32(x_r, eps2)
+        print(f"read {read}: searched {r_s!r} all-pairs {r_r!r} host {want!r} lmax {l_s!r} / {l_r!r}")
+        assert _same(r_s, want), (read, r_s, want)
+        assert _same(r_s, r_r), (read, r_s, r_r)
+        assert _same(l_s, l_r), (read, l_s, l_r)
+        assert np.array_equal(x_s.view(np.uint32), x_r.view(np.uint32)), f"read {read}: the search changed the trajectory"
 
 
 # ----------------------------------------------------------------------------------------------- non-finite bounds

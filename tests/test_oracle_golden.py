@@ -898,7 +898,7 @@ def test_hook_cases_launch_arithmetic_mirrors_the_sources():
     has("nb_misc.hip", f"(int64_t)blockIdx.x * {HC.MM_THREADS} + threadIdx.x, count, (int64_t)gridDim.x * {HC.MM_THREADS}, min_val, mn, mx);")
     has("nb_misc.hip", f"for (int i = threadIdx.x; i < nblocks; i += {HC.MM_THREADS}) {{", 2)
     has("nb_hooks.cpp", "count >= (int64_t)1 << 21")
-    has("nb_force.hip", "grid = grid < 1 ? 1 : (grid > 4096 ? 4096 : grid);")
+    has("nb_grid.hip", "grid = grid < 1 ? 1 : (grid > 4096 ? 4096 : grid);")
     assert (HC.EW_BLOCKS, HC.TABLE_FROM, HC.TAB_PASS) == (2048 * 8, 1 << 21, 4096 * 256)
 
 
