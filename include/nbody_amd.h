@@ -174,6 +174,14 @@ int nb_ens_create(nb_ens **out, const nb_ens_config *cfg, const double *G, const
  * entry works on it, and a member is bit-identical to the nb_sim of the same mode and levels. */
 int nb_ens_create_grid(nb_ens **out, const nb_ens_config *cfg, const int32_t *levels, const double *G,
                        const double *softening_sq, const double *dt);
+/* Members of different cast modes in one handle: cfg->mode must be NB_FLOAT32 (the storage mode of every cast mode)
+ * and modes holds `members` entries, each NB_FLOAT32, NB_BFLOAT16 or NB_FLOAT16 (anything else: NB_ERR_UNSUPPORTED
+ * with the member's index -- NB_FLOAT64 is stored differently, the grid modes need per-member tables).  One force
+ * launch per tick serves all members ("ens_step_mixed_kernel"), and member b is bit-identical to the nb_sim of mode
+ * modes[b].  The handle is an ordinary nb_ens: every nb_ens_* entry works on it; the energies do not pass through the
+ * hook, so nb_ens_energy gives each member the value of its solo run in its own mode. */
+int nb_ens_create_mixed(nb_ens **out, const nb_ens_config *cfg, const int32_t *modes, const double *G,
+                        const double *softening_sq, const double *dt);
 int nb_ens_destroy(nb_ens *e);
 /* any array may be NULL to keep its values; the device copy is updated on the handle's stream */
 int nb_ens_set_params(nb_ens *e, const double *G, const double *softening_sq, const double *dt);
@@ -266,6 +274,28 @@ int nb_ens_crash_measures(nb_ens *e, const void *prev_pos, int on_device, int32_
 int nb_ens_run_crash_watched(nb_ens *e, const int32_t *nsteps, double *kinetic, double *potential,
                              int64_t capacity, int on_device, int32_t *samples, int32_t *stop_tick,
                              int32_t *kind, int32_t *flags, double *measures);
+/* How far members have drifted apart (the reference's comparison loops: reality_glitch_tests.py:148-256,
+ * omega_point_test.py:665-766), measured on the device in ONE launch, one workgroup per member: member b against
+ * member baseline[b] (`members` entries, each in [0, members), else NB_ERR_INVALID naming the member; b itself is
+ * allowed).  Over the n * dim elements, differences formed in the state dtype with one subtraction each:
+ * max_pos[b] = max |pos_b - pos_base| and max_vel[b] = max |vel_b - vel_base| with torch's max() semantics (NaN if
+ * any element is NaN, inf - inf included; +inf is an ordinary value), widened to double; mean_pos[b] = the fp64 sum
+ * of |pos_b - pos_base| in a fixed order (deterministic; NaN if any term is) divided by n * dim.  Outputs: `members`
+ * doubles each, host or device as `on_device` says; any may be NULL.  One launch, one copy-out, one wait.  Needs
+ * positions and velocities.  Changes neither the state nor force_launches. */
+int nb_ens_divergence(nb_ens *e, const int32_t *baseline, double *max_pos, double *mean_pos, double *max_vel,
+                      int on_device);
+/* nb_ens_step(nsteps) that records the divergence of nb_ens_divergence on the device, and with with_energies != 0
+ * the energies of nb_ens_run_recorded beside it (with_energies == 0: no energy launch is issued, kinetic and
+ * potential are not used).  Sampling rule, layout (index s * members + b), capacity and *samples as
+ * nb_ens_run_recorded: sample 0 is the state at entry, sample s the state after tick s * every.  A sampled tick is
+ * issued closed -- force launch, the energy launches if asked, the divergence launch, a separate kick + drift -- so
+ * the trajectory is bit-identical to nb_ens_step(nsteps); force_launches grows by nsteps; every member takes nsteps
+ * ticks.  Nothing waits on the stream before the one copy-out.  NB_ERR_INVALID for every < 1, nsteps < 0, a
+ * baseline that is no member or too small a capacity, before anything is launched. */
+int nb_ens_run_diverged(nb_ens *e, int32_t nsteps, int32_t every, const int32_t *baseline, int32_t with_energies,
+                        double *max_pos, double *mean_pos, double *max_vel, double *kinetic, double *potential,
+                        int64_t capacity, int on_device, int32_t *samples);
 /* The diagnostics of nb_metrics (rotation curve, r_percentile, bound fraction, dispersion) for every member, from
  * the resident state, in ONE kernel launch (one workgroup per member; no host round trip before the copy-out).
  * num_bins in [0, 255].  max_radius: `members` doubles, each >= 0 or NaN, the end of that member's bin edges; or
@@ -283,8 +313,8 @@ int nb_ens_metrics(nb_ens *e, int32_t num_bins, const double *max_radius, double
                    int64_t *curve_count, float *edges, double *scalars);
 /* members; batched force launches issued since creation (nb_ens_compute_accelerations and one per tick;
  * the opening kick + drift launch of an nb_ens_step is not counted); name of the last force kernel
- * ("ens_step_kernel", or "ens_grid_step_kernel" on a grid-mode handle, whose table and finish launches are
- * not counted either; "none" before the first).  Any output may be NULL. */
+ * ("ens_step_kernel", "ens_step_mixed_kernel" on a handle of nb_ens_create_mixed, or "ens_grid_step_kernel" on a
+ * grid-mode handle, whose table and finish launches are not counted either; "none" before the first).  Any output may be NULL. */
 int nb_ens_info(nb_ens *e, int32_t *members, int64_t *force_launches, const char **kernel_name);
 /* Grid-mode handles: out[8 b .. 8 b + 7] = member b's {lmin, lmax, fmin, fmax, r2max, fast_ok, fast_maxdev,
  * fast_maxrel} of the LAST evaluation, the layout of nb_quant_debug's info (fmin / fmax NaN under NB_CUSTOM,

@@ -22,6 +22,11 @@
 // ticks in a device array that every kernel of the tick path reads (nb_device.h) and a watch kernel lowers on the device
 // (nb_ens_watch.hip, nb_ens_crash.hip), and one wait.  The step and run_recorded pass no array: no member ever stops, and
 // the kernels launched are the instantiations without stops.  nb_ens_crash_measures is the detector's kernel alone.
+//
+// nb_ens_create_mixed: fp32 state, every member with its own cast mode (FLOAT32 / BFLOAT16 / FLOAT16) -- the handle keeps
+// the members' hooks on the device and launch_force launches ens_step_mixed_kernel, which reads them; everything else is
+// the FLOAT32 handle's.  nb_ens_divergence / nb_ens_run_diverged compare every member with another member of the handle on
+// the device (nb_ens_diverge.hip): the kernel alone, or as part of run_train's samples.
 #include <algorithm>
 #include <cstddef>
 #include <cstring>
@@ -67,12 +72,24 @@ struct nb_ens {
     void *prev_pos = nullptr;
     double *dt_dev = nullptr, *crash_out = nullptr;
     std::vector<double> crash_host;
+    // members of different cast modes (nb_ens_create_mixed): the hook of every member, as given and on the device
+    bool mixed = false;
+    std::vector<int> hooks_host;
+    int *hooks = nullptr;
+    // divergence between members (created on first use): the members' baselines, as uploaded and on the device; dhist_cap
+    // samples of max |d position|, then as many of mean |d position|, then of max |d velocity|
+    std::vector<int32_t> base_host;
+    int *base_dev = nullptr;
+    double *dhist = nullptr;
+    int64_t dhist_cap = 0;
 };
 
 namespace {
 
 // what run_train launches behind the energy launches of a sampled tick
 enum WatchMode { WATCH_NONE, WATCH_EXPLOSION, WATCH_CRASH };
+// what a sample of run_train holds (a bit set; 0: the run takes no samples)
+enum SampleBits { SAMPLE_ENERGIES = 1, SAMPLE_DIVERGENCE = 2 };
 
 inline size_t el(const nb_ens *e) { return e->is_f64 ? 8 : 4; }
 inline size_t cnt_nd(const nb_ens *e) { return (size_t)e->cfg.members * e->cfg.n * e->cfg.dim; }
@@ -126,6 +143,14 @@ int launch_force(nb_ens *e, int do_kick, const int *stop = nullptr, int t = 0)
 {
     const nb_ens_config &c = e->cfg;
     if (e->grid) return launch_force_grid(e, do_kick, stop, t);
+    if (e->mixed) {
+        HIPCHK(nb_launch_ens_step_mixed((const float *)e->pos, (float *)e->pos_alt, (float *)e->vel, (float *)e->acc,
+                                        (const float *)e->mass, c.members, c.n, c.dim, e->prm, do_kick, e->lanes, e->hooks, stop,
+                                        t, e->stream));
+        e->force_launches++;
+        e->last_kernel = "ens_step_mixed_kernel";
+        return NB_OK;
+    }
     HIPCHK(nb_launch_ens_step(e->pos, e->pos_alt, e->vel, e->acc, e->mass, c.members, c.n, c.dim, e->is_f64, e->hook, e->prm,
                               do_kick, e->lanes, stop, t, e->stream));
     e->force_launches++;
@@ -150,7 +175,8 @@ void release(nb_ens *e)
     if (e->probe) (void)nb_destroy(e->probe);
     for (void *p : {e->prm, e->pos, e->pos_alt, e->vel, e->acc, e->mass, (void *)e->epart, (void *)e->ehist, (void *)e->tabs,
                     (void *)e->levels_dev, (void *)e->fpart, (void *)e->fbounds, e->mscratch, (void *)e->mout, (void *)e->mradius,
-                    (void *)e->medges, (void *)e->stops, e->prev_pos, (void *)e->dt_dev, (void *)e->crash_out})
+                    (void *)e->medges, (void *)e->stops, e->prev_pos, (void *)e->dt_dev, (void *)e->crash_out, (void *)e->hooks,
+                    (void *)e->base_dev, (void *)e->dhist})
         if (p) (void)hipFree(p);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
@@ -170,6 +196,59 @@ int energy_buffers(nb_ens *e, int64_t samples)
                         (long long)samples, hipGetErrorString(he));
         e->ehist_cap = samples;
     }
+    return NB_OK;
+}
+
+// room for `samples` samples of the divergence (buffers grow, never shrink) and for the baselines
+int divergence_buffers(nb_ens *e, int64_t samples)
+{
+    const size_t B = (size_t)e->cfg.members;
+    if (!e->base_dev) HIPCHK(hipMalloc((void **)&e->base_dev, B * sizeof(int)));
+    if (samples > e->dhist_cap) {
+        // no launch reads the old history: every call that fills it copies it out and waits before it returns
+        if (e->dhist) { (void)hipFree(e->dhist); e->dhist = nullptr; e->dhist_cap = 0; }
+        hipError_t he = hipMalloc((void **)&e->dhist, (size_t)samples * B * 3 * sizeof(double));
+        if (he != hipSuccess)
+            return fail(he == hipErrorOutOfMemory ? NB_ERR_OOM : NB_ERR_HIP, "divergence history of %lld samples: %s",
+                        (long long)samples, hipGetErrorString(he));
+        e->dhist_cap = samples;
+    }
+    return NB_OK;
+}
+
+// baseline[0 .. members) name members; then on their way to the device (base_host is free to rewrite: every call that
+// uploads it waits before it returns)
+int upload_baselines(nb_ens *e, const int32_t *baseline)
+{
+    const int B = e->cfg.members;
+    if (!baseline) return fail(NB_ERR_INVALID, "null baseline");
+    for (int b = 0; b < B; ++b)
+        if (baseline[b] < 0 || baseline[b] >= B)
+            return fail(NB_ERR_INVALID, "baseline[%d] = %d is no member: must be in [0, %d)", b, baseline[b], B);
+    e->base_host.assign(baseline, baseline + B);
+    static_assert(sizeof(int32_t) == sizeof(int), "the kernel reads ints");
+    HIPCHK(hipMemcpyAsync(e->base_dev, e->base_host.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    return NB_OK;
+}
+
+// sample `s` of the divergence history: the resident state, one launch behind whatever the stream holds
+int launch_divergence(nb_ens *e, int64_t s)
+{
+    const nb_ens_config &c = e->cfg;
+    const size_t plane = (size_t)e->dhist_cap * c.members;
+    HIPCHK(nb_launch_ens_divergence(e->pos, e->vel, c.members, c.n, c.dim, e->is_f64, e->base_dev, s, e->dhist,
+                                    e->dhist + plane, e->dhist + 2 * plane, e->stream));
+    return NB_OK;
+}
+
+// the first `samples` samples of the divergence history to the caller's arrays (any may be null); does not wait
+int divergence_out(nb_ens *e, int64_t samples, double *max_pos, double *mean_pos, double *max_vel, int on_device)
+{
+    const size_t bytes = (size_t)samples * e->cfg.members * sizeof(double), plane = (size_t)e->dhist_cap * e->cfg.members;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (max_pos && bytes) HIPCHK(hipMemcpyAsync(max_pos, e->dhist, bytes, kind, e->stream));
+    if (mean_pos && bytes) HIPCHK(hipMemcpyAsync(mean_pos, e->dhist + plane, bytes, kind, e->stream));
+    if (max_vel && bytes) HIPCHK(hipMemcpyAsync(max_vel, e->dhist + 2 * plane, bytes, kind, e->stream));
     return NB_OK;
 }
 
@@ -228,22 +307,26 @@ int history_out(nb_ens *e, int64_t samples, double *kinetic, double *potential, 
 // taken at entry, and a sampled tick is issued as a one-tick nb_ens_step issues it -- the force launch only closes the tick
 // (velocities and positions are then what a reader sees), the two energy launches follow, then the watch of `watch`
 // (none, the explosion watch, or the crash-point detector, which needs every = 1 and crash_buffers), and a separate
-// kick + drift launch opens the next tick.  stop: null, or the members' stop ticks on the device;
+// kick + drift launch opens the next tick.  what: the SampleBits of a sample (0 with every = 0) -- the energy launches
+// are issued with SAMPLE_ENERGIES, and SAMPLE_DIVERGENCE adds the divergence launch (divergence_buffers, upload_baselines)
+// behind the watch, in front of the kick + drift.  stop: null, or the members' stop ticks on the device;
 // every launch of the tick path gets it with the number of ticks closed so far.  Nothing waits on the stream.
-int run_train(nb_ens *e, int32_t nmax, int32_t every, int *stop, WatchMode watch)
+int run_train(nb_ens *e, int32_t nmax, int32_t every, int *stop, WatchMode watch, unsigned what)
 {
     const nb_ens_config &c = e->cfg;
     auto open_tick = [&](int t) {
         return nb_launch_ens_kick_drift(e->pos, e->vel, e->acc, c.members, c.n, c.dim, e->is_f64, e->prm, stop, t, e->stream);
     };
-    if (every)
+    if (what & SAMPLE_ENERGIES)
         if (int rc = launch_energy(e, 0, true)) return rc;
+    if (what & SAMPLE_DIVERGENCE)
+        if (int rc = launch_divergence(e, 0)) return rc;
     if (nmax >= 1) HIPCHK(open_tick(0));
     for (int t = 1; t <= nmax; ++t) {
-        const bool last = (t == nmax), sampled = (every && t % every == 0);
+        const bool last = (t == nmax), sampled = (what && t % every == 0);
         if (sampled || last) {
             if (int rc = launch_force(e, NB_KICK_CLOSE, stop, t - 1)) return rc;
-            if (sampled) {
+            if (sampled && (what & SAMPLE_ENERGIES)) {
                 if (int rc = launch_energy(e, t / every, true)) return rc;
                 if (watch == WATCH_EXPLOSION)
                     HIPCHK(nb_launch_ens_watch(e->pos, e->vel, c.members, c.n, c.dim, e->is_f64, e->ehist,
@@ -254,6 +337,8 @@ int run_train(nb_ens *e, int32_t nmax, int32_t every, int *stop, WatchMode watch
                                                e->ehist + e->ehist_cap * c.members, t / every, t, stop, stop + c.members,
                                                crash_flags(e), e->crash_out, e->stream));
             }
+            if (sampled && (what & SAMPLE_DIVERGENCE))
+                if (int rc = launch_divergence(e, t / every)) return rc;
             if (!last) HIPCHK(open_tick(t));
         } else {
             if (int rc = launch_force(e, NB_KICK_CLOSE_OPEN, stop, t - 1)) return rc;
@@ -320,7 +405,7 @@ int run_sampled(nb_ens *e, const int32_t *budgets, int32_t nmax, int32_t every, 
         HIPCHK(hipMemsetAsync(e->crash_out, 0, B * (4 * sizeof(double) + sizeof(int32_t)), e->stream));
         HIPCHK(hipMemcpyAsync(e->prev_pos, e->pos, cnt_nd(e) * el(e), hipMemcpyDeviceToDevice, e->stream));
     }
-    if (int rc = run_train(e, nmax, every, budgets ? e->stops : nullptr, watch)) return rc;
+    if (int rc = run_train(e, nmax, every, budgets ? e->stops : nullptr, watch, every ? SAMPLE_ENERGIES : 0u)) return rc;
     if (budgets) HIPCHK(hipMemcpyAsync(e->stops_host.data(), e->stops, stop_bytes, hipMemcpyDeviceToHost, e->stream));
     if (watch == WATCH_CRASH)
         if (int rc = crash_out_async(e)) return rc;
@@ -458,6 +543,38 @@ int nb_ens_create_grid(nb_ens **out, const nb_ens_config *cfg, const int32_t *le
     return create(out, cfg, lv.data(), G, softening_sq, dt);
 }
 
+int nb_ens_create_mixed(nb_ens **out, const nb_ens_config *cfg, const int32_t *modes, const double *G,
+                        const double *softening_sq, const double *dt)
+{
+    if (!out || !cfg || !modes || !G || !softening_sq || !dt) return fail(NB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (int rc = check_shape(cfg)) return rc;
+    if (cfg->mode != NB_FLOAT32)
+        return fail(NB_ERR_UNSUPPORTED, "nb_ens_create_mixed: cfg->mode must be NB_FLOAT32, the storage mode of every cast mode "
+                                        "(got mode %d)", cfg->mode);
+    for (int b = 0; b < cfg->members; ++b)
+        if (modes[b] != NB_FLOAT32 && modes[b] != NB_BFLOAT16 && modes[b] != NB_FLOAT16)
+            return fail(NB_ERR_UNSUPPORTED, "modes[%d] = %d: members of one ensemble mix the FLOAT32, BFLOAT16 and FLOAT16 modes "
+                                            "only (FLOAT64 is stored differently, the grid modes need per-member tables)", b,
+                        modes[b]);
+    nb_ens *e = nullptr;
+    if (int rc = create(&e, cfg, nullptr, G, softening_sq, dt)) return rc;
+    DeviceGuard guard(cfg->device);
+    e->mixed = true;
+    e->hooks_host.resize(cfg->members);
+    for (int b = 0; b < cfg->members; ++b) e->hooks_host[b] = mode_hook(modes[b]);
+    const size_t bytes = (size_t)cfg->members * sizeof(int);
+    hipError_t he = hipMalloc((void **)&e->hooks, bytes);
+    if (he == hipSuccess) he = hipMemcpyAsync(e->hooks, e->hooks_host.data(), bytes, hipMemcpyHostToDevice, e->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+    if (he != hipSuccess) {
+        release(e);
+        return fail(he == hipErrorOutOfMemory ? NB_ERR_OOM : NB_ERR_HIP, "ensemble allocation failed: %s", hipGetErrorString(he));
+    }
+    *out = e;
+    return NB_OK;
+}
+
 int nb_ens_destroy(nb_ens *e)
 {
     if (!e) return NB_OK;
@@ -531,7 +648,7 @@ int nb_ens_step(nb_ens *e, int32_t nsteps)
     if (int rc = check_steppable(e)) return rc;
     if (nsteps < 1) return NB_OK;
     DeviceGuard guard(e->cfg.device);
-    return run_train(e, nsteps, 0, nullptr, WATCH_NONE);
+    return run_train(e, nsteps, 0, nullptr, WATCH_NONE, 0u);
 }
 
 int nb_ens_energy(nb_ens *e, double *kinetic, double *potential)
@@ -629,6 +746,50 @@ int nb_ens_run_crash_watched(nb_ens *e, const int32_t *nsteps, double *kinetic, 
     if (int rc = check_budgets(e, nsteps, &nmax)) return rc;
     return run_sampled(e, nsteps, nmax, 1, WATCH_CRASH, kinetic, potential, capacity, on_device, samples, stop_tick, kind, flags,
                        measures);
+}
+
+// the divergence kernel alone on the resident state: one launch, one copy-out, one wait
+int nb_ens_divergence(nb_ens *e, const int32_t *baseline, double *max_pos, double *mean_pos, double *max_vel, int on_device)
+{
+    if (!e) return fail(NB_ERR_INVALID, "null handle");
+    if (!e->have_pos || !e->have_vel) return fail(NB_ERR_INVALID, "state incomplete");
+    DeviceGuard guard(e->cfg.device);
+    if (int rc = divergence_buffers(e, 1)) return rc;
+    if (int rc = upload_baselines(e, baseline)) return rc;
+    if (int rc = launch_divergence(e, 0)) return rc;
+    if (int rc = divergence_out(e, 1, max_pos, mean_pos, max_vel, on_device)) return rc;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return NB_OK;
+}
+
+// run_train with the divergence (and, asked for, the energies) in every sample and no stop array
+int nb_ens_run_diverged(nb_ens *e, int32_t nsteps, int32_t every, const int32_t *baseline, int32_t with_energies,
+                        double *max_pos, double *mean_pos, double *max_vel, double *kinetic, double *potential, int64_t capacity,
+                        int on_device, int32_t *samples)
+{
+    if (samples) *samples = 0;
+    if (int rc = check_steppable(e)) return rc;
+    if (nsteps < 0) return fail(NB_ERR_INVALID, "nsteps must be >= 0 (got %d)", nsteps);
+    if (every < 1) return fail(NB_ERR_INVALID, "every must be >= 1 (got %d)", every);
+    const int64_t S = 1 + (int64_t)(nsteps / every);
+    if (capacity < S)
+        return fail(NB_ERR_INVALID, "capacity of %lld samples is below the %lld of %d ticks sampled every %d",
+                    (long long)capacity, (long long)S, nsteps, every);
+    DeviceGuard guard(e->cfg.device);
+    if (int rc = divergence_buffers(e, S)) return rc;
+    if (int rc = upload_baselines(e, baseline)) return rc;      // (checks them: nothing is launched for a bad one)
+    if (with_energies)
+        if (int rc = energy_buffers(e, S)) return rc;
+    if (int rc = run_train(e, nsteps, every, nullptr, WATCH_NONE, SAMPLE_DIVERGENCE | (with_energies ? SAMPLE_ENERGIES : 0u)))
+        return rc;
+    if (int rc = divergence_out(e, S, max_pos, mean_pos, max_vel, on_device)) return rc;
+    if (with_energies) {
+        if (int rc = history_out(e, S, kinetic, potential, on_device)) return rc;      // (waits)
+    } else {
+        HIPCHK(hipStreamSynchronize(e->stream));
+    }
+    if (samples) *samples = (int32_t)S;
+    return NB_OK;
 }
 
 // the diagnostics of every member from the resident state: one launch, two copies, one wait

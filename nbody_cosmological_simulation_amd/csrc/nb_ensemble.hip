@@ -48,6 +48,29 @@ ens_step_kernel(const T *__restrict__ pos_in, T *__restrict__ pos_out, T *__rest
                                        p.G, p.eps2, p.half_dt, p.dt, do_kick, nullptr);
 }
 
+// Members of different cast modes in one launch (nb_ens_create_mixed; fp32 state): ens_step_kernel<float, ...> with the
+// hook read per member from hooks[b] (HOOK_NONE / HOOK_BF16 / HOOK_F16) instead of compiled in.  The body is the same
+// small_step_body with the hook as a workgroup-uniform argument: member b performs the operations of the uniform kernel of
+// its hook, in the same order, on one copy of the LDS tile.
+template <int D, int S, int BS, bool STOPS>
+__global__ void __launch_bounds__(BS)
+ens_step_mixed_kernel(const float *__restrict__ pos_in, float *__restrict__ pos_out, float *__restrict__ vel,
+                      float *__restrict__ acc, const float *__restrict__ mass, int n, const EnsScalars<float> *__restrict__ prm,
+                      int do_kick, const int *__restrict__ hooks, const int *__restrict__ stop, int t)
+{
+    const int b = blockIdx.y;                        // member: uniform per workgroup
+    const EnsScalars<float> p = prm[b];
+    const size_t o = (size_t)b * n;
+    const int left = ens_ticks_left<STOPS>(stop, b, t);
+    if (STOPS && left <= 1) {
+        ens_carry_positions<float, D, S, BS>(pos_in + o * D, pos_out + o * D, n);
+        if (left <= 0) return;
+        do_kick = ens_kick_mode(left, do_kick);
+    }
+    small_step_body<float, D, HOOK_AT_RUN_TIME, S, BS>(blockIdx.x, pos_in + o * D, pos_out + o * D, vel + o * D, acc + o * D,
+                                                       mass + o, n, p.G, p.eps2, p.half_dt, p.dt, do_kick, nullptr, hooks[b]);
+}
+
 // grid hook: member b reads the tables its own max-r2 launch built (tabs[b]); under INT8 / INT4 (part != null) it leaves
 // one {min, max} pair of its forces per workgroup at part[(b * gridDim.x + blockIdx.x) * 2]
 template <int D, int S, int BS, bool STOPS>
@@ -120,6 +143,26 @@ hipError_t nb_launch_ens_step(const void *pos_in, void *pos_out, void *vel, void
             });
         return nb::pick<HOOK_NONE, HOOK_BF16, HOOK_F16>(hook, [&](auto H) {
             return launch_e<float, D.value, H.value>(pos_in, pos_out, vel, acc, mass, members, n, prm, do_kick, lanes, stop, t, st);
+        });
+    });
+}
+
+hipError_t nb_launch_ens_step_mixed(const float *pos_in, float *pos_out, float *vel, float *acc, const float *mass, int members,
+                                    int n, int dim, const void *prm, int do_kick, int lanes, const int *hooks, const int *stop,
+                                    int t, hipStream_t st)
+{
+    if (members < 1 || members > NB_ENS_MAX_MEMBERS || n < 1 || !hooks || t < 0) return hipErrorInvalidValue;
+    if ((do_kick & NB_KICK_MODE_MASK) == NB_KICK_CLOSE_SPEC || (do_kick & NB_KICK_OPEN_ON_READ)) return hipErrorInvalidValue;
+    return nb::pick<2, 3>(dim, [&](auto D) {
+        return nb::pick<64, 32, 16>(lanes, [&](auto S) {
+            return nb::pick<512, 256>(nb_small_block(n), [&](auto BS) {
+                return nb::pick_bool(stop != nullptr, [&](auto ST) {
+                    hipLaunchKernelGGL((ens_step_mixed_kernel<D.value, S.value, BS.value, ST.value>),
+                                       dim3(nb_small_blocks(n, lanes), members), dim3(BS.value), 0, st, pos_in, pos_out, vel, acc,
+                                       mass, n, (const EnsScalars<float> *)prm, do_kick, hooks, stop, t);
+                    return hipGetLastError();
+                });
+            });
         });
     });
 }

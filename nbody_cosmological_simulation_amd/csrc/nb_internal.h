@@ -17,7 +17,8 @@ constexpr int NB_LUT_MIN = 256;   // smallest table allocation (INT8); tables ar
 
 // hooks compiled into the pair loop (quantization.py:21-71)
 enum { HOOK_NONE = 0, HOOK_BF16 = 1, HOOK_F16 = 2, HOOK_GRID = 3,
-       HOOK_F32PAIR = 4 /* fp64 state, diff/r2 in fp32: FLOAT64-mode first evaluation */ };
+       HOOK_F32PAIR = 4 /* fp64 state, diff/r2 in fp32: FLOAT64-mode first evaluation */,
+       HOOK_AT_RUN_TIME = 5 /* small_step_body only: NONE / BF16 / F16 as a workgroup-uniform argument (mixed ensembles) */ };
 
 // Device-resident grid tables written by grid_tables_kernel, read by the force kernel.
 struct GridTables {
@@ -345,6 +346,10 @@ constexpr int NB_ENS_MAX_MEMBERS = 1024;
 hipError_t nb_launch_ens_step(const void *pos_in, void *pos_out, void *vel, void *acc, const void *mass, int members, int n,
                               int dim, int is_f64, int hook, const void *prm, int do_kick, int lanes, const int *stop, int t,
                               hipStream_t st);
+// members of different cast modes (fp32 state): hooks is device, one of HOOK_NONE / HOOK_BF16 / HOOK_F16 per member
+hipError_t nb_launch_ens_step_mixed(const float *pos_in, float *pos_out, float *vel, float *acc, const float *mass, int members,
+                                    int n, int dim, const void *prm, int do_kick, int lanes, const int *hooks, const int *stop,
+                                    int t, hipStream_t st);
 // opening kick + drift of every member with its own dt (two roundings per line, like nb_launch_kick_drift)
 hipError_t nb_launch_ens_kick_drift(void *pos, void *vel, const void *acc, int members, int n, int dim, int is_f64,
                                     const void *prm, const int *stop, int t, hipStream_t st);
@@ -384,6 +389,13 @@ hipError_t nb_launch_ens_watch(const void *pos, const void *vel, int members, in
 hipError_t nb_launch_ens_crash(const void *pos, void *prev, const void *vel, int members, int n, int dim, int is_f64,
                                const double *dt, const double *kinetic, const double *potential, int64_t sample, int t, int *stop,
                                int *kind, int *flags, double *measures, hipStream_t st);
+// ---- divergence between the members of an ensemble (nb_ens_diverge.hip) ---------------------------------------------------
+// ONE launch on `st`, one workgroup per member: member b against member baseline[b] (device, `members` ints in
+// [0, members)) -- max |pos_b - pos_base|, mean |pos_b - pos_base| and max |vel_b - vel_base| over the n * dim elements,
+// differences in the state dtype, to max_pos / mean_pos / max_vel[sample * members + b].  The maxima are torch's max() (NaN
+// if any element is NaN, +inf an ordinary value); the mean is a fixed-order fp64 sum divided by n * dim.
+hipError_t nb_launch_ens_divergence(const void *pos, const void *vel, int members, int n, int dim, int is_f64, const int *baseline,
+                                    int64_t sample, double *max_pos, double *mean_pos, double *max_vel, hipStream_t st);
 // ---- batched energies of an ensemble (nb_ens_energy.hip) -----------------------------------------------------------------
 // Two launches on `st`: per-tile-pair partial sums into part (members * nb_ens_energy_pairs(n) * 2 doubles, every slot
 // rewritten), then one wave per member that writes kinetic[sample * members + b] and potential[sample * members + b].

@@ -1,6 +1,7 @@
 // nb_small_body.h -- device bodies of the one-launch small-system step (D = 2 or 3): the pair loop over LDS-staged
 // source tiles, the butterfly that finishes a target's sum, and the fused closing / opening kicks (see nb_small.hip for
-// the scheme).  small_step_body: the cast hooks (HOOK_NONE / HOOK_BF16 / HOOK_F16; T = double or float);
+// the scheme).  small_step_body: the cast hooks (HOOK_NONE / HOOK_BF16 / HOOK_F16; T = double or float), or
+// HOOK_AT_RUN_TIME (fp32): one of the three cast hooks as a workgroup-uniform argument (ens_step_mixed_kernel);
 // small_grid_body: the grid hook (fp32, tables, bin read-out).  Included by nb_small.hip (small_step_kernel: one system
 // per launch, target block = blockIdx.x) and nb_ensemble.hip (ens_step_kernel / ens_grid_step_kernel: many systems per
 // launch): the SAME code, so a member of an ensemble rounds every sum exactly as the solo step does.
@@ -35,12 +36,19 @@ __device__ __forceinline__ float inv_r3_f(float q)
 // sources.  The pointers are that system's own arrays ((n, D) row-major; mass (n)); the scalars are already cast to T.
 // do_kick: an NbKick mode, | NB_KICK_OPEN_ON_READ (nb_internal.h); the drifted positions go to pos_out.
 // part (kernel-uniform, may be null): per-workgroup {min, max} of the forces written, at part[2 blk].
+// hook_rt: read under HOOK_AT_RUN_TIME only -- HOOK_NONE, HOOK_BF16 or HOOK_F16, uniform over the workgroup; the two
+// rounding lines of the pair loop then test it, and every other operation is the one the compile-time hook performs.
 template <typename T, int D, int HOOK, int S, int BS>
 __device__ __forceinline__ void small_step_body(int blk, const T *pos_in, T *pos_out,
                                                 T *vel, T *acc, const T *mass, int n,
-                                                T G, T eps2, T half_dt, T dt, int do_kick, double *part)
+                                                T G, T eps2, T half_dt, T dt, int do_kick, double *part,
+                                                int hook_rt = HOOK_NONE)
 {
-    static_assert(HOOK == HOOK_NONE || HOOK == HOOK_BF16 || HOOK == HOOK_F16, "the grid hook has its own body: small_grid_body");
+    static_assert(HOOK == HOOK_NONE || HOOK == HOOK_BF16 || HOOK == HOOK_F16 || HOOK == HOOK_AT_RUN_TIME,
+                  "the grid hook has its own body: small_grid_body");
+    static_assert(HOOK != HOOK_AT_RUN_TIME || sizeof(T) == 4, "the cast hooks round an fp32 r2");
+    const bool hook_bf16 = HOOK == HOOK_BF16 || (HOOK == HOOK_AT_RUN_TIME && hook_rt == HOOK_BF16);
+    const bool hook_f16 = HOOK == HOOK_F16 || (HOOK == HOOK_AT_RUN_TIME && hook_rt == HOOK_F16);
     constexpr bool F64 = sizeof(T) == 8;
     constexpr int TG = BS / S;                       // targets per workgroup
     __shared__ T sx[D][SM_TILE];
@@ -101,10 +109,10 @@ __device__ __forceinline__ void small_step_body(int blk, const T *pos_in, T *pos
 #pragma unroll
                 for (int k = 0; k < D; ++k) d[k] = __fsub_rn(sx[k][jj], xc[k]);
                 float q = r2_f32_exact<D>(d, eps2);
-                if (HOOK == HOOK_BF16) q = round_bf16(q);
-                if (HOOK == HOOK_F16) q = round_f16(q);
+                if (hook_bf16) q = round_bf16(q);
+                if (hook_f16) q = round_f16(q);
                 float w = __fmul_rn(inv_r3_f(q), G);
-                if (HOOK == HOOK_F16) w = (q == __builtin_inff()) ? 0.0f : w;      // pow(inf) = inf -> G / inf = 0 upstream
+                if (hook_f16) w = (q == __builtin_inff()) ? 0.0f : w;      // pow(inf) = inf -> G / inf = 0 upstream
                 w = __fmul_rn(w, sg[jj]);
 #pragma unroll
                 for (int k = 0; k < D; ++k) a[k] += (double)__fmul_rn(w, d[k]);

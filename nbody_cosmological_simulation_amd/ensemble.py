@@ -79,7 +79,30 @@ gives it.  A halted member's state is that of its solo run of `ticks_taken[b]` s
 reference's 0-based index of the tick whose check fired, and later calls go on from there; `tick`, `member_ticks` and
 `launches()` move as under `run_members`, and a halted QuantizedEnsemble member keeps the tables of its last evaluation.
 
-Not covered: more than 256 levels, mixed modes within one ensemble, a crash check interval other than 1, crash thresholds
+Members of different cast modes -- the reference's comparison runs put FLOAT32 beside FLOAT16 (reality_glitch_tests.py:
+148-256, whose universe C rounds r^2 through half() exactly as PrecisionMode.FLOAT16 does; simulation.py:199-250
+run_comparison) -- share one ensemble: `precision_mode` may be a list of B modes drawn from FLOAT32, BFLOAT16 and FLOAT16
+(`check_mode_list`), `precision_modes` always holds the B modes in force, and a tick is still ONE force launch
+("ens_step_mixed_kernel": the member's hook is read per workgroup, the step body is the uniform kernel's).  Contract: member
+b is bit-identical to the `GalaxySimulation` of mode `precision_modes[b]`, no tolerance; every other method works unchanged.
+A list whose entries are all equal is the scalar mode (FLOAT64 included).  FLOAT64 cannot be mixed in (different storage
+type), nor the grid modes (per-member tables: `QuantizedEnsemble`).
+
+Divergence between members -- what those comparison loops and omega_point_test.py:665-766 (_test_point) read back after
+every tick as (a.positions - b.positions).abs().max().item() -- is measured on the device: `divergence(baseline)` compares
+every member b with member `baseline[b]` (an int: one member for all) in one launch (csrc/nb_ens_diverge.hip, one workgroup
+per member) and returns a `Divergence`; `run_diverged(num_ticks, every, baseline, energies)` runs the ticks and samples the
+divergence (and, asked for, the energies of run_recorded) between them with no host round trip, returning a
+`DivergenceHistory`.  Sampling rule: sample 0 is the state at entry, sample s the state after tick s * every of the call; a
+sampled tick is issued closed, so the trajectory is bit-identical to run(num_ticks).  Contract of the values: differences
+are formed in the state dtype, one subtraction each; `max_position` / `max_velocity` equal torch's
+(a - b).abs().max() widened to double -- NaN rule: NaN if any element is NaN (inf - inf included), +inf an ordinary value;
+`mean_position` is a fixed-order fp64 sum over n * D divided in double (deterministic; NaN if any term is; within
+n * D * 2^-53 relative of any other fp64 order).  `entropy_bits` and `divergence_rate` are the reference's derived
+quantities in numpy float64.
+
+Not covered: more than 256 levels, FLOAT64 or grid-mode members beside cast-mode members, stopping members on a divergence
+threshold, a crash check interval other than 1, crash thresholds
 other than the reference's constants,
 compacting the launch grid as members finish (a finished member costs its workgroups one load each), mixed dtypes and the
 fp32 -> fp64 promotion timeline, subclass overrides, checkpoints, multi-GPU.
@@ -99,6 +122,7 @@ MAX_MEMBERS = 1024
 MAX_STARS = {torch.float64: 4096, torch.float32: 3072}     # the solo one-launch step's limits (csrc/nb_step.cpp)
 MAX_BINS = 255                        # rotation-curve bins of metrics() (csrc/nb_ens_metrics.hip: the edges live in LDS)
 MAX_HISTORY_BYTES = 256 << 20         # an EnergyHistory's kinetic + potential samples (16 bytes per member and sample)
+DIVERGENCE_SAMPLE_BYTES = 24          # a DivergenceHistory's three values per member and sample, under the same limit
 _MODES = (PrecisionMode.FLOAT64, PrecisionMode.FLOAT32, PrecisionMode.BFLOAT16, PrecisionMode.FLOAT16)
 _GRID_MODES = (PrecisionMode.INT8_SIM, PrecisionMode.INT4_SIM, PrecisionMode.CUSTOM)
 MIN_LEVELS, MAX_LEVELS = 2, 256       # MAX_LEVELS: above it the solo engine leaves the one-launch step (csrc/nb_step.cpp)
@@ -155,6 +179,33 @@ def check_arguments(positions, velocities, masses, precision_mode=PrecisionMode.
         raise ValueError(f"GalaxyEnsemble runs the FLOAT64, FLOAT32, BFLOAT16 and FLOAT16 modes; {precision_mode.name} needs "
                          "per-member quantisation tables (use GalaxySimulation)")
     return _check_state(positions, velocities, masses, precision_mode, G, softening, dt)
+
+
+def check_mode_list(modes, members=None) -> list:
+    """Validate a per-member list of precision modes without touching a device: `members` entries (None: any length),
+    all equal (any cast mode or FLOAT64: the uniform ensemble of that mode) or drawn from FLOAT32, BFLOAT16 and FLOAT16.
+    Returns the list; raises TypeError / ValueError naming the reason."""
+    if isinstance(modes, (str, bytes)) or not isinstance(modes, Sequence):
+        raise TypeError(f"precision modes must be a sequence of PrecisionMode, got {type(modes).__name__}")
+    modes = list(modes)
+    for m in modes:
+        if not isinstance(m, PrecisionMode):
+            raise TypeError(f"precision modes must be PrecisionMode values, got {type(m).__name__}")
+    if not modes:
+        raise ValueError("precision modes: an empty list")
+    if members is not None and len(modes) != int(members):
+        raise ValueError(f"precision_mode has {len(modes)} entries for {int(members)} members")
+    for b, m in enumerate(modes):
+        if m in _GRID_MODES:
+            raise ValueError(f"precision_mode[{b}] = {m.name}: a grid mode needs per-member quantisation tables, which the "
+                             "cast-mode members of a GalaxyEnsemble do not have (use QuantizedEnsemble)")
+    if len(set(modes)) > 1:
+        for b, m in enumerate(modes):
+            if m == PrecisionMode.FLOAT64:
+                raise ValueError(f"precision_mode[{b}] = FLOAT64 beside other modes: FLOAT64 members have a different storage "
+                                 "type (fp64 state) from FLOAT32 / BFLOAT16 / FLOAT16 members (fp32) and cannot share an "
+                                 "ensemble with them")
+    return modes
 
 
 def _check_state(positions, velocities, masses, precision_mode, G, softening, dt, more_lists=()):
@@ -279,6 +330,60 @@ def check_member_ticks_arguments(num_ticks, every, members):
     if every is None:
         return budgets, None
     return budgets, check_record_arguments(max(budgets), int(every), members)
+
+
+def check_divergence_arguments(num_ticks, every, baseline, members):
+    """Validate run_diverged's arguments without touching a device (divergence(): num_ticks = 0, every = 1).  `baseline`:
+    an int (one member for all) or a sequence, tensor or numpy array of `members` ints, each in [0, members).  Returns
+    (baselines, offsets): the length-`members` list and the tick offsets of the samples relative to the tick at entry;
+    raises TypeError / ValueError."""
+    offsets = check_record_arguments(num_ticks, every, members)
+    members = int(members)
+    baseline = _scalar_or_list(baseline, "baseline", numbers.Integral, "an int or a sequence of ints")
+    if isinstance(baseline, list) and len(baseline) != members:
+        raise ValueError(f"baseline has {len(baseline)} entries for {members} members")
+    baselines = [int(v) for v in baseline] if isinstance(baseline, list) else [int(baseline)] * members
+    for v in baselines:
+        if not 0 <= v < members:
+            raise ValueError(f"baseline must name a member, 0 .. {members - 1}, got {v}")
+    if len(offsets) * members * DIVERGENCE_SAMPLE_BYTES > MAX_HISTORY_BYTES:
+        raise ValueError(f"{len(offsets)} samples of {members} members are {len(offsets) * members * DIVERGENCE_SAMPLE_BYTES} "
+                         f"bytes of divergence history, above the limit of {MAX_HISTORY_BYTES}: raise `every` (or record the "
+                         "run in shorter stretches)")
+    return baselines, offsets
+
+
+def entropy_bits(max_position_diff):
+    """The reference's "bits of uncertainty" of a largest position difference (reality_glitch_tests.py:245-247), elementwise
+    in numpy float64: log2(x / 1e-10 + 1) where x > 1e-10, else 0.0 (a NaN compares false: 0.0)."""
+    import numpy as np
+    x = np.asarray(max_position_diff, np.float64)
+    out = np.zeros(x.shape, np.float64)
+    hit = x > 1e-10
+    out[hit] = np.log2(x[hit] / 1e-10 + 1)
+    return out if out.ndim else float(out)
+
+
+def divergence_rate(series):
+    """The reference's Lyapunov-style rate (reality_glitch_tests.py:250-253) of a series of largest position differences as
+    the reference accumulates it, one value per step(), along axis 0: entry i is
+    log(max(series[i-1], 1e-15) / series[i-10]) / 10 if i > 10 and series[i-10] > 1e-15, else 0.0 -- the window is the ten
+    entries before the current one.  numpy float64, with Python's max() as the reference calls it."""
+    import numpy as np
+    x = np.asarray(series, np.float64)
+    if x.ndim < 1:
+        raise ValueError("divergence_rate needs a series (one value per step)")
+    out = np.zeros(x.shape, np.float64)
+    if x.shape[0] <= 11:
+        return out
+    cols_in, cols_out = x.reshape(x.shape[0], -1), out.reshape(x.shape[0], -1)       # (views: out is filled through cols_out)
+    for i in range(11, x.shape[0]):
+        for c in range(cols_in.shape[1]):
+            first, last = cols_in[i - 10, c], cols_in[i - 1, c]
+            if first > 1e-15:
+                with np.errstate(all="ignore"):
+                    cols_out[i, c] = np.log(max(last, 1e-15) / first) / 10
+    return out
 
 
 def explosion_reason(initial_energy, energy, finite) -> int:
@@ -413,6 +518,55 @@ class EnergyHistory(NamedTuple):
         return self.kinetic + self.potential
 
 
+class Divergence(NamedTuple):
+    """What divergence() returns, (B,) float64 tensors: member b against its baseline member -- the largest and the mean
+    |position difference| and the largest |velocity difference| over the N * D elements (module docstring: contract)."""
+    max_position: torch.Tensor
+    mean_position: torch.Tensor
+    max_velocity: torch.Tensor
+
+
+class DivergenceHistory(NamedTuple):
+    """What run_diverged returns: `ticks[s]` is the absolute tick of sample s; `baseline` the B baseline members;
+    `max_position`, `mean_position` and `max_velocity` are float64 tensors of shape (samples, members); `energy` is the
+    EnergyHistory of the same samples, or None."""
+    ticks: list
+    baseline: list
+    max_position: torch.Tensor
+    mean_position: torch.Tensor
+    max_velocity: torch.Tensor
+    energy: "EnergyHistory"
+
+    def entropy_bits(self):
+        """`entropy_bits` of every sample's max_position: a (samples, members) numpy array."""
+        return entropy_bits(self.max_position.cpu().numpy())
+
+    def divergence_rate(self):
+        """`divergence_rate` per member: the reference's series holds one value per step(), so the rule is applied to
+        samples 1.. and the entry sample reports 0.  A (samples, members) numpy array."""
+        import numpy as np
+        x = self.max_position.cpu().numpy()
+        out = np.zeros(x.shape, np.float64)
+        out[1:] = divergence_rate(x[1:])
+        return out
+
+    def peak(self):
+        """The running maximum of max_position over the samples (omega_point_test.py _test_point's max_divergence, which
+        Python's max() keeps: a NaN sample never replaces the maximum so far): a (samples, members) numpy array."""
+        import numpy as np
+        x = self.max_position.cpu().numpy()
+        out = np.empty(x.shape, np.float64)
+        best = np.zeros(x.shape[1:], np.float64)
+        for s in range(x.shape[0]):
+            best = np.where(x[s] > best, x[s], best)          # max(best, x): x wins only where it compares greater
+            out[s] = best
+        return out
+
+    def butterfly(self, threshold: float = 0.1):
+        """Per member: the peak went above `threshold` (_test_point's "butterfly"): a (members,) bool numpy array."""
+        return self.peak()[-1] > threshold
+
+
 class StabilityReport(NamedTuple):
     """What run_watched returns, (B,) numpy arrays: `stable_ticks` int64, the ticks the member took in the call before it
     stopped (its budget, or the check that halted it); `exploded` bool; `reason` int64, REASON_NONE / REASON_NONFINITE /
@@ -472,15 +626,28 @@ class GalaxyEnsemble:
     def __init__(self, positions, velocities, masses, precision_mode=PrecisionMode.FLOAT64,
                  G=0.001, softening=0.1, dt=0.01, device=None):
         self._handle = C.c_void_p()
-        positions, velocities, masses, self.G, self.softening, self.dt = check_arguments(
-            positions, velocities, masses, precision_mode, G, softening, dt)
-        self._construct(positions, velocities, masses, precision_mode, device)
+        modes = None
+        if isinstance(precision_mode, (list, tuple)):
+            # one mode per member: the state is checked under the storage mode, a lone galaxy is broadcast over the list
+            modes = check_mode_list(precision_mode)
+            storage = modes[0] if len(set(modes)) == 1 else PrecisionMode.FLOAT32
+            positions, velocities, masses, self.G, self.softening, self.dt = _check_state(
+                positions, velocities, masses, storage, G, softening, dt, [len(modes)])
+            check_mode_list(modes, int(positions.shape[0]))
+        else:
+            positions, velocities, masses, self.G, self.softening, self.dt = check_arguments(
+                positions, velocities, masses, precision_mode, G, softening, dt)
+        self._construct(positions, velocities, masses, precision_mode, device, modes)
 
-    def _construct(self, positions, velocities, masses, precision_mode, device):
-        """Everything behind the argument checks: the native handle, the upload and the initial accelerations."""
+    def _construct(self, positions, velocities, masses, precision_mode, device, modes=None):
+        """Everything behind the argument checks: the native handle, the upload and the initial accelerations.  modes: the
+        checked per-member list, if the caller gave one."""
         self.device = torch.device(device) if device is not None else positions.device
         self.precision_mode = precision_mode
         self.num_members, self.num_stars, self._dim = (int(v) for v in positions.shape)
+        self.precision_modes = list(modes) if modes is not None else [precision_mode] * self.num_members
+        self._mixed = len(set(self.precision_modes)) > 1
+        precision_mode = PrecisionMode.FLOAT32 if self._mixed else self.precision_modes[0]     # what the handle is created with
         self._dtype = state_dtype(precision_mode)
         self.tick = 0
         if self.device.type == "cuda":
@@ -495,8 +662,12 @@ class GalaxyEnsemble:
 
     # ------------------------------------------------------------------ native plumbing
     def _create(self, cfg):
-        N.check(N.lib().nb_ens_create(C.byref(self._handle), C.byref(cfg), _doubles(self.G),
-                                      _doubles([s ** 2 for s in self.softening]), _doubles(self.dt)))
+        params = (_doubles(self.G), _doubles([s ** 2 for s in self.softening]), _doubles(self.dt))
+        if self._mixed:
+            codes = (C.c_int32 * self.num_members)(*[mode_code(m) for m in self.precision_modes])
+            N.check(N.lib().nb_ens_create_mixed(C.byref(self._handle), C.byref(cfg), codes, *params))
+        else:       # (an all-equal list too: exactly the scalar mode's handle)
+            N.check(N.lib().nb_ens_create(C.byref(self._handle), C.byref(cfg), *params))
 
     def close(self):
         """Release the native handle (device buffers, stream) now instead of at garbage collection."""
@@ -716,6 +887,36 @@ class GalaxyEnsemble:
         del held
         return _crash_measures(flags, meas)
 
+    def divergence(self, baseline=0) -> Divergence:
+        """How far every member is from its baseline member (`baseline`: an int, one member for all, or one per member)
+        on the resident state: one launch, one copy-out (module docstring: contract)."""
+        baselines, _ = check_divergence_arguments(0, 1, baseline, self.num_members)
+        B = self.num_members
+        out = [torch.empty(B, dtype=torch.float64, device=self.device) for _ in range(3)]
+        N.check(N.lib().nb_ens_divergence(self._handle, (C.c_int32 * B)(*baselines), *[C.c_void_p(t.data_ptr()) for t in out],
+                                          int(self.device.type == "cuda")))
+        return Divergence(*out)
+
+    def run_diverged(self, num_ticks: int, every: int = 1, baseline=0, energies: bool = True) -> DivergenceHistory:
+        """`num_ticks` ticks like run(), recording every member's divergence from its baseline member on the device: at
+        entry and after every `every`-th tick of this call; `energies`: also the EnergyHistory of run_recorded at the same
+        samples (False: no energy launch is issued, `energy` is None).  One native call; nothing is copied to the host in
+        between.  The trajectory is bit-identical to run(num_ticks)."""
+        baselines, offsets = check_divergence_arguments(num_ticks, every, baseline, self.num_members)
+        S, B = len(offsets), self.num_members
+        dv = [torch.empty((S, B), dtype=torch.float64, device=self.device) for _ in range(3)]
+        en = [torch.empty((S, B), dtype=torch.float64, device=self.device) for _ in range(2)] if energies else []
+        got = C.c_int32()
+        N.check(N.lib().nb_ens_run_diverged(
+            self._handle, int(num_ticks), int(every), (C.c_int32 * B)(*baselines), int(bool(energies)),
+            *[C.c_void_p(t.data_ptr()) for t in dv], *([C.c_void_p(t.data_ptr()) for t in en] or [None, None]), S,
+            int(self.device.type == "cuda"), C.byref(got)))
+        if got.value != S:
+            raise RuntimeError(f"nb_ens_run_diverged wrote {got.value} samples, expected {S}")
+        ticks = [self.tick + o for o in offsets]
+        self._advance(int(num_ticks))
+        return DivergenceHistory(ticks, baselines, dv[0], dv[1], dv[2], EnergyHistory(ticks, en[0], en[1]) if energies else None)
+
     def energies(self):
         """(kinetic, potential): float64 tensors of shape (B,) on `self.device`, all members evaluated in one batched
         pass.  Equal to get_kinetic_energy() / get_potential_energy() to the project's bars, not bit for bit."""
@@ -773,7 +974,7 @@ class GalaxyEnsemble:
             "velocities": self.velocities[b].clone(),
             "masses": self.masses[b].clone(),
             "tick": self.member_ticks[b],
-            "precision_mode": self.precision_mode.value,
+            "precision_mode": self.precision_modes[b].value,
         }
 
     def _info(self):
