@@ -147,13 +147,16 @@ int nb_energy(nb_sim *s, double *kinetic, double *potential);
  * of them one tick per kernel launch.  No arithmetic crosses members; a member's state is bit-identical to
  * the nb_sim that takes the same steps on the one-launch small-system path.
  * Limits: nb_ens_create takes the modes NB_FLOAT64 .. NB_FLOAT16 (the grid modes need per-member tables:
- * NB_ERR_UNSUPPORTED there) and nb_ens_create_grid takes NB_INT8_SIM, NB_INT4_SIM and NB_CUSTOM with up to 256
- * levels per member; state of the settled dtype only (NB_F64 under NB_FLOAT64, NB_F32 otherwise); n at most
+ * NB_ERR_UNSUPPORTED there), nb_ens_create_grid takes NB_INT8_SIM, NB_INT4_SIM and NB_CUSTOM with up to 256
+ * levels per member, and nb_ens_create_grid_wide takes NB_CUSTOM with up to 4096 levels per member (above
+ * 256 levels a member is no longer bit-identical to its nb_sim, see there); state of the settled dtype only (NB_F64 under NB_FLOAT64, NB_F32 otherwise); n at most
  * the one-launch step's limit (4096 fp64, 3072 fp32); 1 <= members <= 1024; one device, no communicator.
  * Arrays are whole (members, n, dim) / (members, n) row-major blocks, host or device as flagged.
  * Grid modes: an evaluation is two launches over all members (max r^2 + tables, the pair sweep) and under
  * INT8 / INT4 a third (force snap + kicks); every member has its own tables (49 KB of device memory each),
- * built from its own exact max r^2, softening, G and level count, so they are the tables of its solo run. */
+ * built from its own exact max r^2, softening, G and level count, so they are the tables of its solo run.
+ * A handle of nb_ens_create_grid_wide with a member above 256 levels adds one tables launch per evaluation
+ * for those members and keeps its pair sweep's tables (up to 2 * 4097 floats) in LDS sized per launch. */
 typedef struct nb_ens nb_ens;
 typedef struct nb_ens_config {
     int32_t members;       /* B                                                              */
@@ -174,6 +177,18 @@ int nb_ens_create(nb_ens **out, const nb_ens_config *cfg, const double *G, const
  * entry works on it, and a member is bit-identical to the nb_sim of the same mode and levels. */
 int nb_ens_create_grid(nb_ens **out, const nb_ens_config *cfg, const int32_t *levels, const double *G,
                        const double *softening_sq, const double *dt);
+/* NB_CUSTOM with up to 4096 levels per member (the threshold tables' capacity): cfg->mode must be NB_CUSTOM (any
+ * other: NB_ERR_UNSUPPORTED, as is n above the fp32 limit); levels: `members` level counts, each in [2, 4096]
+ * (else NB_ERR_INVALID with the member's index and the range), or NULL for 64 everywhere.  Arguments are refused
+ * before a device is looked for.  While no member exceeds 256 levels the handle is nb_ens_create_grid's, launch
+ * for launch ("ens_grid_step_kernel").  Otherwise a tick is still ONE force launch, "ens_grid_step_wide_kernel":
+ * a member of up to 256 levels stays bit-identical to its nb_sim whatever its neighbours' level counts; a
+ * member of 257 .. 4096 levels has the tables of its nb_sim (lmin, lmax, r2max equal, fast_ok = 0), gives every
+ * pair the bin and the table entry the nb_sim gives it, and sums the products in the one-launch step's order --
+ * deterministic and independent of the other members, but not the order of the nb_sim's tiled path, so
+ * accelerations agree with the nb_sim's to rounding, not bit for bit. */
+int nb_ens_create_grid_wide(nb_ens **out, const nb_ens_config *cfg, const int32_t *levels, const double *G,
+                            const double *softening_sq, const double *dt);
 /* Members of different cast modes in one handle: cfg->mode must be NB_FLOAT32 (the storage mode of every cast mode)
  * and modes holds `members` entries, each NB_FLOAT32, NB_BFLOAT16 or NB_FLOAT16 (anything else: NB_ERR_UNSUPPORTED
  * with the member's index -- NB_FLOAT64 is stored differently, the grid modes need per-member tables).  One force
@@ -314,12 +329,22 @@ int nb_ens_metrics(nb_ens *e, int32_t num_bins, const double *max_radius, double
 /* members; batched force launches issued since creation (nb_ens_compute_accelerations and one per tick;
  * the opening kick + drift launch of an nb_ens_step is not counted); name of the last force kernel
  * ("ens_step_kernel", "ens_step_mixed_kernel" on a handle of nb_ens_create_mixed, or "ens_grid_step_kernel" on a
- * grid-mode handle, whose table and finish launches are not counted either; "none" before the first).  Any output may be NULL. */
+ * grid-mode handle -- "ens_grid_step_wide_kernel" when a member exceeds 256 levels -- whose table and finish launches
+ * are not counted either; "none" before the first).  Any output may be NULL. */
 int nb_ens_info(nb_ens *e, int32_t *members, int64_t *force_launches, const char **kernel_name);
 /* Grid-mode handles: out[8 b .. 8 b + 7] = member b's {lmin, lmax, fmin, fmax, r2max, fast_ok, fast_maxdev,
  * fast_maxrel} of the LAST evaluation, the layout of nb_quant_debug's info (fmin / fmax NaN under NB_CUSTOM,
  * which does not quantise forces).  NB_ERR_UNSUPPORTED on a handle of nb_ens_create. */
 int nb_ens_quant_info(nb_ens *e, double *out /* members * 8 */);
+/* Grid-mode handles: nb_quant_bin_sums for every member, read out of the production pair sweep (its BINS
+ * instantiation) on the members' CURRENT positions: sum_k / sum_kw are (members, n) -- per star p the check-sums
+ * s1 = sum_q k(p, q) and s2 = sum_q k(p, q) ((q mod 65521) + 1) of the bin every pair was given -- and
+ * pairs[2 b], pairs[2 b + 1] member b's pair evaluations binned table-free / through a threshold table.  Any
+ * output may be NULL.  An observer: the forces of the read-out go to a scratch buffer, the tables are rebuilt
+ * from the same positions (the same values); state, accelerations and force_launches are untouched.  A member on
+ * a degenerate grid (values pass through, no bins) reports zeros.  NB_ERR_UNSUPPORTED on a handle of nb_ens_create
+ * or nb_ens_create_mixed. */
+int nb_ens_quant_bin_sums(nb_ens *e, int64_t *sum_k, int64_t *sum_kw, int64_t *pairs /* members * 2 */);
 int nb_ens_synchronize(nb_ens *e);
 
 /* ---- precision-hook introspection ---------------------------------------------------- */

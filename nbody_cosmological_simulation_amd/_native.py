@@ -37,6 +37,7 @@ EXPORTS = [
     "nb_ens_energies", "nb_ens_run_recorded", "nb_ens_create_grid", "nb_ens_quant_info", "nb_ens_metrics",
     "nb_ens_run_members", "nb_ens_crash_measures", "nb_ens_run_crash_watched",
     "nb_ens_create_mixed", "nb_ens_divergence", "nb_ens_run_diverged",
+    "nb_ens_create_grid_wide", "nb_ens_quant_bin_sums",
 ]
 
 
@@ -131,7 +132,9 @@ def lib():
         "nb_ens_create_mixed": ([C.POINTER(vp), C.POINTER(NbEnsConfig), pi32, pdbl, pdbl, pdbl], C.c_int),
         "nb_ens_divergence": ([vp, pi32, vp, vp, vp, C.c_int], C.c_int),
         "nb_ens_run_diverged": ([vp, i32, i32, pi32, i32, vp, vp, vp, vp, vp, i64, C.c_int, pi32], C.c_int),
+        "nb_ens_create_grid_wide": ([C.POINTER(vp), C.POINTER(NbEnsConfig), pi32, pdbl, pdbl, pdbl], C.c_int),
         "nb_ens_quant_info": ([vp, pdbl], C.c_int),
+        "nb_ens_quant_bin_sums": ([vp, vp, vp, vp], C.c_int),
         "nb_ens_destroy": ([vp], C.c_int),
         "nb_ens_set_params": ([vp, pdbl, pdbl, pdbl], C.c_int),
         "nb_ens_set_state": ([vp, vp, vp, vp, C.c_int, C.c_int], C.c_int),

@@ -10,6 +10,10 @@
 // count per member, and under INT8 / INT4 the force launch's per-workgroup {min, max} partials and a (B, 2) array of force
 // bounds.  An evaluation is then step_small's sequence (nb_step.cpp) batched: max r2 + tables, the grid step, and under
 // INT8 / INT4 the finish launch that snaps the forces and carries the kicks IN PLACE (no ping-pong of the positions).
+// nb_ens_create_grid_wide (CUSTOM, up to NB_MAX_LUT levels per member) is the same handle; once a member exceeds NB_LUT_MIN
+// levels, a second tables launch builds those members' multi-chunk tables and the pair sweep is the wide kernel (tables in
+// dynamic LDS) -- still one force launch per tick.  nb_ens_quant_bin_sums runs the evaluation once more with the BINS
+// instantiation of the pair sweep in use, forces into a scratch buffer: an observer.
 //
 // Energies are off the hot path and must equal a solo handle's bit for bit, whichever kernel variant the solo engine
 // picks for this shape and these masses: each member's slice is handed (device to device) to one solo handle of the same
@@ -64,6 +68,10 @@ struct nb_ens {
     GridTables *tabs = nullptr;               // device: one per member (max r2, arrival counter, the evaluation's tables)
     int *levels_dev = nullptr;
     double *fpart = nullptr, *fbounds = nullptr;   // INT8 / INT4: members * grid_blocks * 2 partials; members * {fmin, fmax}
+    int max_levels = 0;                       // the largest of `levels`: above NB_LUT_MIN the tick runs the wide kernels
+    // nb_ens_quant_bin_sums (created on first use): the read-out's forces; members * (2 n + 2) checksum / counter words
+    float *bin_acc = nullptr;
+    unsigned long long *bin_out = nullptr;
     // nb_ens_run_members (created on first use): members stop ticks, then members halt reasons; what is uploaded / read back
     int32_t *stops = nullptr;
     std::vector<int32_t> stops_host;
@@ -115,12 +123,32 @@ int upload_params(nb_ens *e)
     return NB_OK;
 }
 
-// one evaluation of a grid-mode ensemble, as step_small issues a solo one (stop / t: nb_internal.h)
-int launch_force_grid(nb_ens *e, int do_kick, const int *stop, int t)
+// the tables of one evaluation of a grid-mode ensemble: max r2 of every member and its single-block tables in one launch;
+// members above NB_LUT_MIN levels get theirs from a second one (neither is counted by force_launches)
+int launch_tables(nb_ens *e, const int *stop, int t)
 {
     const nb_ens_config &c = e->cfg;
     HIPCHK(nb_launch_ens_r2max_tables((const float *)e->pos, c.members, c.n, c.dim, e->prm, e->tabs, e->levels_dev, 0.01f,
                                       e->allow_fast, stop, t, e->stream));
+    if (e->max_levels > NB_LUT_MIN)
+        HIPCHK(nb_launch_ens_tables_wide(c.members, e->max_levels, e->prm, e->tabs, e->levels_dev, 0.01f, e->allow_fast, stop, t,
+                                         e->stream));
+    return NB_OK;
+}
+
+// one evaluation of a grid-mode ensemble, as step_small issues a solo one (stop / t: nb_internal.h)
+int launch_force_grid(nb_ens *e, int do_kick, const int *stop, int t)
+{
+    const nb_ens_config &c = e->cfg;
+    if (int rc = launch_tables(e, stop, t)) return rc;
+    if (e->max_levels > NB_LUT_MIN) {        // (CUSTOM only: no force bounds, no finish launch)
+        HIPCHK(nb_launch_ens_grid_step_wide((const float *)e->pos, (float *)e->pos_alt, (float *)e->vel, (float *)e->acc,
+                                            (const float *)e->mass, c.members, c.n, c.dim, e->prm, do_kick, e->lanes, e->tabs,
+                                            e->max_levels, stop, t, e->stream));
+        e->force_launches++;
+        e->last_kernel = "ens_grid_step_wide_kernel";
+        return NB_OK;
+    }
     HIPCHK(nb_launch_ens_grid_step((const float *)e->pos, (float *)e->pos_alt, (float *)e->vel, (float *)e->acc,
                                    (const float *)e->mass, c.members, c.n, c.dim, e->prm, e->fq ? NB_KICK_NONE : do_kick, e->lanes,
                                    e->tabs, e->fq ? e->fpart : nullptr, stop, t, e->stream));
@@ -176,7 +204,7 @@ void release(nb_ens *e)
     for (void *p : {e->prm, e->pos, e->pos_alt, e->vel, e->acc, e->mass, (void *)e->epart, (void *)e->ehist, (void *)e->tabs,
                     (void *)e->levels_dev, (void *)e->fpart, (void *)e->fbounds, e->mscratch, (void *)e->mout, (void *)e->mradius,
                     (void *)e->medges, (void *)e->stops, e->prev_pos, (void *)e->dt_dev, (void *)e->crash_out, (void *)e->hooks,
-                    (void *)e->base_dev, (void *)e->dhist})
+                    (void *)e->base_dev, (void *)e->dhist, (void *)e->bin_acc, (void *)e->bin_out})
         if (p) (void)hipFree(p);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
@@ -486,6 +514,7 @@ int create(nb_ens **out, const nb_ens_config *cfg, const int32_t *levels, const 
         e->allow_fast = knobs.no_grid_fast ? 0 : 1;
         e->grid_blocks = nb_small_blocks(cfg->n, e->lanes);
         e->levels.assign(levels, levels + B);
+        e->max_levels = *std::max_element(levels, levels + B);
         const size_t part_bytes = (size_t)B * e->grid_blocks * 2 * sizeof(double);
         // zeroed once: every evaluation puts a member's maximum and arrival counter back (grid_tables_body)
         if (he == hipSuccess) he = hipMalloc((void **)&e->tabs, (size_t)B * sizeof(GridTables));
@@ -540,6 +569,24 @@ int nb_ens_create_grid(nb_ens **out, const nb_ens_config *cfg, const int32_t *le
         if (lv[b] < 2 || lv[b] > NB_LUT_MIN)
             return fail(NB_ERR_INVALID, "levels[%d] = %d is outside [2, %d]: above it a solo run leaves the one-launch step", b,
                         lv[b], NB_LUT_MIN);
+    return create(out, cfg, lv.data(), G, softening_sq, dt);
+}
+
+int nb_ens_create_grid_wide(nb_ens **out, const nb_ens_config *cfg, const int32_t *levels, const double *G,
+                            const double *softening_sq, const double *dt)
+{
+    if (!out || !cfg || !G || !softening_sq || !dt) return fail(NB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (int rc = check_shape(cfg)) return rc;
+    if (cfg->mode != NB_CUSTOM)
+        return fail(NB_ERR_UNSUPPORTED, "nb_ens_create_grid_wide runs the CUSTOM mode (got mode %d): INT8_SIM / INT4_SIM are "
+                                        "nb_ens_create_grid's, the other modes nb_ens_create's", cfg->mode);
+    std::vector<int32_t> lv(cfg->members, 64);
+    if (levels) lv.assign(levels, levels + cfg->members);
+    for (int b = 0; b < cfg->members; ++b)
+        if (lv[b] < 2 || lv[b] > NB_MAX_LUT)
+            return fail(NB_ERR_INVALID, "levels[%d] = %d is outside [2, %d]: finer grids are the solo engine's generic kernel's", b,
+                        lv[b], NB_MAX_LUT);
     return create(out, cfg, lv.data(), G, softening_sq, dt);
 }
 
@@ -874,6 +921,37 @@ int nb_ens_quant_info(nb_ens *e, double *out)
         double *o = out + b * 8;
         o[0] = h.lmin; o[1] = h.lmax; o[2] = fb[2 * b]; o[3] = fb[2 * b + 1]; o[4] = h.r2max;
         o[5] = h.fast_ok; o[6] = h.fast_maxdev; o[7] = h.fast_maxrel;
+    }
+    return NB_OK;
+}
+
+// the evaluation once more on the current positions with the BINS instantiation of the pair sweep this handle runs:
+// tables (the same values: a function of the positions), then the sweep with the forces into bin_acc and no kick
+int nb_ens_quant_bin_sums(nb_ens *e, int64_t *sum_k, int64_t *sum_kw, int64_t *pairs)
+{
+    if (!e) return fail(NB_ERR_INVALID, "null handle");
+    if (!e->grid) return fail(NB_ERR_UNSUPPORTED, "the quant-bin read-out is only defined for the grid modes (nb_ens_create_grid, "
+                                                  "nb_ens_create_grid_wide)");
+    if (!e->have_pos || !e->have_mass) return fail(NB_ERR_INVALID, "positions/masses not set");
+    DeviceGuard guard(e->cfg.device);
+    const nb_ens_config &c = e->cfg;
+    const size_t B = (size_t)c.members, n = (size_t)c.n, per = 2 * n + 2, bytes = B * per * sizeof(unsigned long long);
+    if (!e->bin_acc) HIPCHK(hipMalloc((void **)&e->bin_acc, cnt_nd(e) * sizeof(float)));
+    if (!e->bin_out) HIPCHK(hipMalloc((void **)&e->bin_out, bytes));
+    HIPCHK(hipMemsetAsync(e->bin_out, 0, bytes, e->stream));
+    if (int rc = launch_tables(e, nullptr, 0)) return rc;
+    HIPCHK(nb_launch_ens_grid_bins((const float *)e->pos, e->bin_acc, (const float *)e->mass, c.members, c.n, c.dim, e->prm,
+                                   e->lanes, e->tabs, e->max_levels, e->bin_out, e->stream));
+    std::vector<unsigned long long> host(B * per);
+    HIPCHK(hipMemcpyAsync(host.data(), e->bin_out, bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (size_t b = 0; b < B; ++b) {
+        const unsigned long long *h = host.data() + b * per;
+        for (size_t i = 0; i < n; ++i) {
+            if (sum_k) sum_k[b * n + i] = (int64_t)h[i];
+            if (sum_kw) sum_kw[b * n + i] = (int64_t)h[n + i];
+        }
+        if (pairs) { pairs[2 * b] = (int64_t)h[2 * n]; pairs[2 * b + 1] = (int64_t)h[2 * n + 1]; }
     }
     return NB_OK;
 }

@@ -516,12 +516,13 @@ __device__ __forceinline__ void tables_publish(GridTables *__restrict__ tab, int
 // One thread per level, NB_LUT_MIN threads per block; the block that arrives last (all others have read
 // tab->r2max_bits and written their entries) writes the scalars and resets the scratch for the next evaluation.
 // FUSED: called by the last workgroup of r2max_tables_kernel (single-block tables, levels <= NB_LUT_MIN; the
-// caller passes the finished maximum).  Otherwise the body of grid_tables_kernel (one workgroup per NB_LUT_MIN levels).
+// caller passes the finished maximum).  Otherwise the body of grid_tables_kernel (one workgroup per NB_LUT_MIN levels):
+// `chunks` workgroups share the levels -- 0: the launch's gridDim.x; the batched ens_tables_wide_kernel passes the member's own.
 // Phases: tables_entries -> last_block_arrives -> fast_path_fit -> fast_path_check -> prune_rearm -> tables_publish.
 template <bool FUSED>
 __device__ __forceinline__ void grid_tables_body(GridTables *__restrict__ tab, int levels, float G, float eps2, float min_val,
                                                  PruneState *__restrict__ ps, int allow_fast, unsigned int r2max_bits,
-                                                 const double *__restrict__ bounds = nullptr)
+                                                 const double *__restrict__ bounds = nullptr, int chunks = 0)
 {
     if (bounds) {                  // tensor-level hook: minimum / maximum of the tensor, found on the device
         eps2 = (float)bounds[0];
@@ -531,7 +532,8 @@ __device__ __forceinline__ void grid_tables_body(GridTables *__restrict__ tab, i
     __shared__ float s_thr[NB_LUT_MIN], s_lut[NB_LUT_MIN], s_red[NB_LUT_MIN], s_par[4];
     __shared__ double s_lg2[2];          // log2 of the first / last factor, taken by their own threads (off the serial tail)
     const int k = (FUSED ? 0 : blockIdx.x) * NB_LUT_MIN + threadIdx.x;
-    const int tables_blocks = FUSED ? 1 : gridDim.x;
+    const unsigned int nblocks = chunks ? (unsigned int)chunks : gridDim.x;      // (non-FUSED) workgroups that share the levels
+    const int tables_blocks = FUSED ? 1 : nblocks;
     TableBounds b;
     b.min_val = min_val;
     b.r2max = __uint_as_float(r2max_bits);
@@ -551,7 +553,7 @@ __device__ __forceinline__ void grid_tables_body(GridTables *__restrict__ tab, i
     tables_entries(tab, levels, G, b, k, tables_blocks, s_lut, s_thr, s_lg2);
     __syncthreads();               // every thread of this block has read tab->r2max_bits and written its entry
     if constexpr (!FUSED) {        // (single-block tables -- every grid up to 256 levels -- need no arrival count)
-        if (gridDim.x > 1 && !last_block_arrives(&tab->blocks_done, gridDim.x)) return;
+        if (nblocks > 1 && !last_block_arrives(&tab->blocks_done, nblocks)) return;
     }
     const bool fin = threadIdx.x == 0;
     // ---- table-free pair path: parameters + validation (single-block tables only: levels <= NB_LUT_MIN) ------
@@ -649,13 +651,20 @@ grid_quantize_safe_tab_kernel(const float *__restrict__ in, float *__restrict__ 
 constexpr int NB_R2MAX_SPLIT = 8;
 
 // behind r2max_block, shared by the solo and the batched kernel: count this workgroup's arrival at *tab; the last of
-// `gridDim.x * gridDim.y` builds the tables from the finished maximum, the others return (*levels is read by the last only)
+// `gridDim.x * gridDim.y` builds the tables from the finished maximum, the others return (*levels is read by the last only).
+// WIDE_OK (batched kernel): a grid above NB_LUT_MIN levels has multi-chunk tables, which ens_tables_wide_kernel builds from
+// the maximum left in tab->r2max_bits -- the last workgroup only puts the arrival counter back for that launch.
+template <bool WIDE_OK = false>
 __device__ __forceinline__ void r2max_last_builds_tables(GridTables *tab, const int *levels, float G, float eps2,
                                                          float min_val, int allow_fast)
 {
     static_assert(NB_BLOCK == NB_LUT_MIN, "the last workgroup runs the single-block tables code");
     __shared__ unsigned int s_bits;
     if (!last_block_arrives(&tab->blocks_done, gridDim.x * gridDim.y)) return;
+    if (WIDE_OK && *levels > NB_LUT_MIN) {
+        if (threadIdx.x == 0) tab->blocks_done = 0u;
+        return;
+    }
     // the maximum itself through the same atomic unit that every workgroup's atomicMax went to
     if (threadIdx.x == 0) s_bits = atomicMax(&tab->r2max_bits, 0u);
     __syncthreads();
@@ -689,7 +698,26 @@ ens_r2max_tables_kernel(const float *__restrict__ pos, ForceGeom g, const EnsSca
     GridTables *tab = tabs + b;
     const float G = prm[b].G, eps2 = prm[b].eps2;
     r2max_block<D, 1, NB_R2MAX_SPLIT>(pos + (size_t)b * g.n * D, g, eps2, tab);
-    r2max_last_builds_tables(tab, levels + b, G, eps2, min_val, allow_fast);
+    r2max_last_builds_tables<true>(tab, levels + b, G, eps2, min_val, allow_fast);
+}
+
+// The tables of the members above NB_LUT_MIN levels, behind ens_r2max_tables_kernel: blockIdx.y is the member, blockIdx.x
+// one chunk of NB_LUT_MIN of its levels -- grid_tables_kernel's body with the member's own chunk count, so the entries, the
+// NaN sentinel and the published scalars (fast_ok = 0: more than one chunk) are those of the member's solo run.  Workgroups
+// of a member with single-block tables (built by the launch before), beyond a member's own chunks, or of a stopped member
+// (whose maximum was not taken either) return at once.
+template <bool STOPS>
+__global__ void __launch_bounds__(NB_LUT_MIN)
+ens_tables_wide_kernel(const EnsScalars<float> *__restrict__ prm, GridTables *__restrict__ tabs, const int *__restrict__ levels,
+                       float min_val, int allow_fast, const int *__restrict__ stop, int t)
+{
+    const int b = blockIdx.y;
+    const int L = levels[b];
+    const int chunks = (L + NB_LUT_MIN - 1) / NB_LUT_MIN;
+    if (L <= NB_LUT_MIN || L > NB_MAX_LUT || (int)blockIdx.x >= chunks) return;
+    if (ens_ticks_left<STOPS>(stop, b, t) <= 0) return;
+    GridTables *tab = tabs + b;
+    grid_tables_body<false>(tab, L, prm[b].G, prm[b].eps2, min_val, nullptr, allow_fast, tab->r2max_bits, nullptr, chunks);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -946,6 +974,19 @@ hipError_t nb_launch_ens_r2max_tables(const float *pos, int members, int n, int 
                                (const EnsScalars<float> *)prm, tabs, levels, min_val, allow_fast, stop, t);
             return hipGetLastError();
         });
+    });
+}
+
+hipError_t nb_launch_ens_tables_wide(int members, int max_levels, const void *prm, GridTables *tabs, const int *levels,
+                                     float min_val, int allow_fast, const int *stop, int t, hipStream_t st)
+{
+    if (members < 1 || members > NB_ENS_MAX_MEMBERS || !tabs || !levels || !prm || t < 0) return hipErrorInvalidValue;
+    if (max_levels <= NB_LUT_MIN || max_levels > NB_MAX_LUT) return hipErrorInvalidValue;
+    const dim3 grid((max_levels + NB_LUT_MIN - 1) / NB_LUT_MIN, members);
+    return nb::pick_bool(stop != nullptr, [&](auto ST) {
+        hipLaunchKernelGGL((ens_tables_wide_kernel<ST.value>), grid, dim3(NB_LUT_MIN), 0, st, (const EnsScalars<float> *)prm, tabs,
+                           levels, min_val, allow_fast, stop, t);
+        return hipGetLastError();
     });
 }
 

@@ -355,7 +355,8 @@ hipError_t nb_launch_ens_kick_drift(void *pos, void *vel, const void *acc, int m
                                     const void *prm, const int *stop, int t, hipStream_t st);
 // The grid modes (INT8 / INT4 / CUSTOM, fp32 state), three launches per evaluation, each over all members:
 //   nb_launch_ens_r2max_tables        max r2 of every member and, by the member's last workgroup, its tables (tabs: `members`
-//                                     GridTables, zeroed once; levels: device, `members` ints in [2, NB_LUT_MIN])
+//                                     GridTables, zeroed once; levels: device, `members` ints in [2, NB_LUT_MIN];
+//                                     [2, NB_MAX_LUT] on a wide handle, see below)
 //   nb_launch_ens_grid_step           the solo grid step's body (nb_small_body.h small_grid_body) on every member with
 //                                     tabs[b]; part (INT8 / INT4, else null): members * nb_small_blocks * 2 doubles, one
 //                                     {min, max} of the forces per workgroup -- the kicks are then the finish launch's
@@ -367,6 +368,22 @@ hipError_t nb_launch_ens_r2max_tables(const float *pos, int members, int n, int 
 hipError_t nb_launch_ens_grid_step(const float *pos_in, float *pos_out, float *vel, float *acc, const float *mass, int members,
                                    int n, int dim, const void *prm, int do_kick, int lanes, const GridTables *tabs, double *part,
                                    const int *stop, int t, hipStream_t st);
+// CUSTOM members of up to NB_MAX_LUT levels (nb_ens_create_grid_wide), when a member exceeds NB_LUT_MIN:
+//   nb_launch_ens_r2max_tables        as above (levels in [2, NB_MAX_LUT]): a member above NB_LUT_MIN levels only gets its maximum
+//   nb_launch_ens_tables_wide         ... and its tables here, built as grid_tables_kernel builds a solo run's: one workgroup per
+//                                     NB_LUT_MIN levels of the member; the other members' workgroups return at once
+//   nb_launch_ens_grid_step_wide      nb_launch_ens_grid_step with the tables in dynamic LDS sized for max_levels, the largest
+//                                     level count of the members
+//   nb_launch_ens_grid_bins           the bin read-out of either grid step (BINS = true; wide when max_levels > NB_LUT_MIN):
+//                                     forces to the scratch `acc`, no kicks; bin_out: members * (2 n + 2) words, zeroed by the
+//                                     caller, per member {s1[n], s2[n], {table-free pairs, table pairs}}
+hipError_t nb_launch_ens_tables_wide(int members, int max_levels, const void *prm, GridTables *tabs, const int *levels,
+                                     float min_val, int allow_fast, const int *stop, int t, hipStream_t st);
+hipError_t nb_launch_ens_grid_step_wide(const float *pos_in, float *pos_out, float *vel, float *acc, const float *mass,
+                                        int members, int n, int dim, const void *prm, int do_kick, int lanes,
+                                        const GridTables *tabs, int max_levels, const int *stop, int t, hipStream_t st);
+hipError_t nb_launch_ens_grid_bins(const float *pos, float *acc, const float *mass, int members, int n, int dim, const void *prm,
+                                   int lanes, const GridTables *tabs, int max_levels, unsigned long long *bin_out, hipStream_t st);
 hipError_t nb_launch_ens_force_quant_finish(float *acc, int members, int count, int levels, const double *partials, int nblocks,
                                             double *bounds, float *vel, float *pos, const void *prm, int kick, const int *stop,
                                             int t, hipStream_t st);

@@ -3,8 +3,8 @@
 // the scheme).  small_step_body: the cast hooks (HOOK_NONE / HOOK_BF16 / HOOK_F16; T = double or float), or
 // HOOK_AT_RUN_TIME (fp32): one of the three cast hooks as a workgroup-uniform argument (ens_step_mixed_kernel);
 // small_grid_body: the grid hook (fp32, tables, bin read-out).  Included by nb_small.hip (small_step_kernel: one system
-// per launch, target block = blockIdx.x) and nb_ensemble.hip (ens_step_kernel / ens_grid_step_kernel: many systems per
-// launch): the SAME code, so a member of an ensemble rounds every sum exactly as the solo step does.
+// per launch, target block = blockIdx.x), nb_ensemble.hip (ens_step_kernel / ens_grid_step_kernel: many systems per
+// launch) and nb_ens_grid_wide.hip (ens_grid_step_wide_kernel, ens_grid_bins_kernel): the SAME code, so a member of an ensemble rounds every sum exactly as the solo step does.
 #pragma once
 #include "nb_device.h"
 
@@ -181,11 +181,17 @@ __device__ __forceinline__ void small_step_body(int blk, const T *pos_in, T *pos
 // s2 = sum_j k ((j mod 65521) + 1) of the bin every pair was given, by whichever route the production code took
 // (table-free estimate / wave ballot / threshold fallback); bin_out = {s1[n], s2[n], {table-free pairs, table pairs}}.
 // part (kernel-uniform; INT8 / INT4): per-workgroup {min, max} of the forces written, at part[2 blk].
-template <int D, int S, bool BINS, int BS>
+// WIDE (ens_grid_step_wide_kernel: CUSTOM members of up to NB_MAX_LUT levels): the tables live in the launch's dynamic LDS
+// instead -- wide_tabs = 2 (wide_cap + 1) floats, wide_cap the padded size (nb_lut_pad) of the launch's widest member --
+// and the binary search walks the member's OWN padded size.  A grid above NB_LUT_MIN levels has fast_ok = 0 (multi-chunk
+// tables, nb_grid.hip) and takes the estimate or the search, as on the solo tiled path; one of up to NB_LUT_MIN levels
+// performs the operations of the fixed-size body in the same order.  Lane layout and source order are the same either way.
+template <int D, int S, bool BINS, int BS, bool WIDE = false>
 __device__ __forceinline__ void small_grid_body(int blk, const float *pos_in, float *pos_out, float *vel, float *acc,
                                                 const float *mass, int n, float G, float eps2, float half_dt, float dt,
                                                 int do_kick, const GridTables *tab, double *part,
-                                                unsigned long long *bin_out)
+                                                unsigned long long *bin_out, float *wide_tabs = nullptr,
+                                                int wide_cap = NB_LUT_MIN)
 {
     using T = float;
     constexpr bool F64 = sizeof(T) == 8;
@@ -193,13 +199,20 @@ __device__ __forceinline__ void small_grid_body(int blk, const float *pos_in, fl
     __shared__ T sx[D][SM_TILE];
     __shared__ T sg[SM_TILE];                        // G * m_j (fp32: the reference's (1/p * G) * m_j order is kept below)
     // grid hook (INT8 / INT4 / CUSTOM up to 256 levels): the evaluation's tables (nb_grid.hip grid_tables_kernel)
-    __shared__ float s_thr[NB_LUT_MIN + 1], s_lut[NB_LUT_MIN + 1];
+    __shared__ float s_thr_fix[WIDE ? 1 : NB_LUT_MIN + 1], s_lut_fix[WIDE ? 1 : NB_LUT_MIN + 1];
+    float *const s_thr = WIDE ? wide_tabs : s_thr_fix;
+    float *const s_lut = WIDE ? wide_tabs + wide_cap + 1 : s_lut_fix;
     const int tid = threadIdx.x;
     bool g_fast = false, g_est = false, g_deg = false;
     float est_a = 0.0f, est_b = 0.0f, est_bc = 0.0f, sure_lim = 0.0f, c1 = 0.0f, c0c = 0.0f, kcf = 0.0f;
     int g_levels = 0, g_tm = 0;
     g_levels = tab->levels;
-    for (int k = tid; k <= NB_LUT_MIN; k += BS) {
+    int lp = NB_LUT_MIN;                             // the member's padded table size (nb_lut_pad), never above the launch's
+    if constexpr (WIDE) {
+        g_levels = min(g_levels, wide_cap);
+        while (lp < g_levels) lp <<= 1;
+    }
+    for (int k = tid; k <= lp; k += BS) {
         s_thr[k] = (k <= g_levels) ? tab->thr[k] : __builtin_inff();     // thr[levels] = NaN sentinel, +inf padding
         s_lut[k] = (k < g_levels) ? tab->lut[k] : 0.0f;
     }
@@ -293,7 +306,7 @@ __device__ __forceinline__ void small_grid_body(int blk, const float *pos_in, fl
             } else {
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    kb[u] = grid_bin_lookup(s_thr, q[u], NB_LUT_MIN);
+                    kb[u] = grid_bin_lookup(s_thr, q[u], lp);
                     w[u] = s_lut[kb[u]];
                 }
             }

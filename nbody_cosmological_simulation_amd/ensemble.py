@@ -30,7 +30,29 @@ INT8_SIM, INT4_SIM and CUSTOM with `custom_levels` per member (2 .. 256), fp32 s
 its own quantisation tables, built on the device from its own exact max r^2, softening, G and level count, so they are
 the tables of its solo run and the member stays bit-identical to `GalaxySimulation(custom_levels=levels[b])`.  A tick
 is two launches over all members (max r^2 + tables, pair sweep) and under INT8 / INT4 a third (force snap + kicks);
-`quant_debug()` reads every member's grid bounds back.  It inherits everything else from `GalaxyEnsemble`.
+`quant_debug()` reads every member's grid bounds back, and `quant_bin_sums()` the bin every pair was given: the solo
+`quant_bin_sums` check-sums per member and star, read out of the production pair loop (its BINS instantiation) on the
+members' current positions.  It is an observer -- the read-out's forces go to a scratch buffer, the tables are rebuilt from
+the same positions -- so positions, velocities, accelerations, `tick`, `launches()` and every later tick stay bit-identical.
+It inherits everything else from `GalaxyEnsemble`.
+
+Finer grids -- the convergence sweep of falsification_tests.py:44-104 steps one galaxy under CUSTOM grids of 4, 8, ...
+levels -- are `FineGridEnsemble`'s: a `QuantizedEnsemble` in CUSTOM mode whose `custom_levels` go up to
+MAX_FINE_LEVELS = 4096, the capacity of the threshold tables (C-ABI nb_ens_create_grid_wide).  While no member exceeds
+256 levels it launches exactly what `QuantizedEnsemble` launches ("ens_grid_step_kernel").  Otherwise a tick is still one
+force launch, "ens_grid_step_wide_kernel" -- the same pair loop with the tables in LDS sized for the widest member -- behind
+the max r^2 launch and one more tables launch that builds the multi-chunk tables of the members above 256 levels.  Contract:
+  * a member with <= 256 levels is bit-identical to `GalaxySimulation(custom_levels=L)` on the one-launch path, whatever its
+    neighbours' level counts (QuantizedEnsemble's contract);
+  * a member with 257 .. 4096 levels has the tables of its solo run (`lmin`, `lmax`, `r2max` of `quant_debug()` equal the
+    solo's exactly, `fast_path` is False); every pair gets the bin the reference gives it (`quant_bin_sums()` equals the
+    check-sums of the reference formula's bin matrix and the solo `quant_bin_sums("tiled")` at the same positions, exactly) and the
+    table entry the solo run uses, so its accelerations are the same fp32 products summed in the one-launch body's order:
+    deterministic, independent of the other members, their order and number; `run(T)`, T calls of `step()`,
+    `run_recorded(T, every)` and `run_members` with equal budgets give the same bits, and a stopped or halted member
+    equals the same member run alone for as many ticks, bit for bit;
+  * against the solo run -- which above 256 levels takes the tiled path and sums in another order -- accelerations and
+    trajectories of such a member agree at the suite's bars (2e-6 relative), not bit for bit.
 
 Galaxy diagnostics -- the rotation curve the sweeps record beside the energies, and `collect_metrics`' radius, bound
 fraction and dispersion -- are batched too: `metrics(num_bins, max_radius, percentile)` evaluates all four diagnostics of
@@ -101,7 +123,8 @@ are formed in the state dtype, one subtraction each; `max_position` / `max_veloc
 n * D * 2^-53 relative of any other fp64 order).  `entropy_bits` and `divergence_rate` are the reference's derived
 quantities in numpy float64.
 
-Not covered: more than 256 levels, FLOAT64 or grid-mode members beside cast-mode members, stopping members on a divergence
+Not covered: more than 4096 levels (a solo `GalaxySimulation` serves them through its generic kernel), INT8 / INT4 beside
+CUSTOM members, FLOAT64 or grid-mode members beside cast-mode members, stopping members on a divergence
 threshold, a crash check interval other than 1, crash thresholds
 other than the reference's constants,
 compacting the launch grid as members finish (a finished member costs its workgroups one load each), mixed dtypes and the
@@ -126,6 +149,7 @@ DIVERGENCE_SAMPLE_BYTES = 24          # a DivergenceHistory's three values per m
 _MODES = (PrecisionMode.FLOAT64, PrecisionMode.FLOAT32, PrecisionMode.BFLOAT16, PrecisionMode.FLOAT16)
 _GRID_MODES = (PrecisionMode.INT8_SIM, PrecisionMode.INT4_SIM, PrecisionMode.CUSTOM)
 MIN_LEVELS, MAX_LEVELS = 2, 256       # MAX_LEVELS: above it the solo engine leaves the one-launch step (csrc/nb_step.cpp)
+MAX_FINE_LEVELS = 4096                # FineGridEnsemble: the threshold tables' capacity (csrc/nb_internal.h NB_MAX_LUT)
 DEFAULT_CUSTOM_LEVELS = 64            # the reference's default (quantization.py:67)
 # why run_watched halted a member (include/nbody_amd.h NB_ENS_REASON_*; `explosion_reason`)
 REASON_NONE, REASON_NONFINITE, REASON_ENERGY, REASON_UNBOUND = 0, 1, 2, 3
@@ -278,6 +302,28 @@ def check_grid_arguments(positions, velocities, masses, precision_mode=Precision
     elif precision_mode == PrecisionMode.INT4_SIM:
         levels = [16] * B
     elif levels is None:
+        levels = [DEFAULT_CUSTOM_LEVELS] * B
+    elif not isinstance(levels, list):
+        levels = [levels] * B
+    elif len(levels) != B:
+        raise ValueError(f"custom_levels has {len(levels)} entries for {B} members")
+    return positions, velocities, masses, levels, G, softening, dt
+
+
+def check_fine_grid_arguments(positions, velocities, masses, custom_levels=None, G=0.001, softening=0.1, dt=0.01):
+    """Validate FineGridEnsemble's constructor arguments without touching a device: check_grid_arguments under CUSTOM with
+    the level range [2, MAX_FINE_LEVELS].  Returns (positions, velocities, masses, levels, G, softening, dt) as there; raises
+    ValueError / TypeError."""
+    levels = _level_list(custom_levels)
+    for v in (levels if isinstance(levels, list) else [levels] if levels is not None else []):
+        if not MIN_LEVELS <= v <= MAX_FINE_LEVELS:
+            more = (": a solo GalaxySimulation(custom_levels=...) serves such grids through its generic kernel"
+                    if v > MAX_FINE_LEVELS else "")
+            raise ValueError(f"custom_levels must be in [{MIN_LEVELS}, {MAX_FINE_LEVELS}], got {v}{more}")
+    positions, velocities, masses, G, softening, dt = _check_state(
+        positions, velocities, masses, PrecisionMode.CUSTOM, G, softening, dt, [len(levels)] if isinstance(levels, list) else [])
+    B = int(positions.shape[0])
+    if levels is None:
         levels = [DEFAULT_CUSTOM_LEVELS] * B
     elif not isinstance(levels, list):
         levels = [levels] * B
@@ -1022,3 +1068,34 @@ class QuantizedEnsemble(GalaxyEnsemble):
         a = np.asarray(info, np.float64).reshape(B, 8)
         return dict(lmin=a[:, 0].copy(), lmax=a[:, 1].copy(), fmin=a[:, 2].copy(), fmax=a[:, 3].copy(), r2max=a[:, 4].copy(),
                     fast_path=a[:, 5] != 0, levels=np.asarray(self.levels, np.int64))
+
+    def quant_bin_sums(self) -> dict:
+        """The bin every pair was given, read out of the production pair loop on the members' current positions, as
+        GalaxySimulation.quant_bin_sums() gives it for a solo run: `sum_k` and `sum_kw`, (B, N) int64 numpy arrays -- per
+        star p the check-sums sum_q k(p, q) and sum_q k(p, q) ((q mod 65521) + 1) over all q -- `pairs_table_free` and
+        `pairs_table`, (B,) int64 (pair evaluations binned by the table-free estimate alone / through a threshold table),
+        and `levels`.  An observer: state, accelerations, `tick` and `launches()` stay as they are (module docstring)."""
+        import numpy as np
+        B, n = self.num_members, self.num_stars
+        s1, s2, pairs = np.zeros((B, n), np.int64), np.zeros((B, n), np.int64), np.zeros((B, 2), np.int64)
+        N.check(N.lib().nb_ens_quant_bin_sums(self._handle, C.c_void_p(s1.ctypes.data), C.c_void_p(s2.ctypes.data),
+                                              C.c_void_p(pairs.ctypes.data)))
+        return dict(sum_k=s1, sum_kw=s2, pairs_table_free=pairs[:, 0].copy(), pairs_table=pairs[:, 1].copy(),
+                    levels=np.asarray(self.levels, np.int64))
+
+
+class FineGridEnsemble(QuantizedEnsemble):
+    """A QuantizedEnsemble in CUSTOM mode whose members take up to MAX_FINE_LEVELS = 4096 grid levels (`custom_levels`: None
+    = 64, an int, or one per member).  A member of up to 256 levels keeps QuantizedEnsemble's bit identity with its solo run;
+    a finer one has its solo run's tables and bins and a deterministic sum of its own (see the module docstring)."""
+
+    def __init__(self, positions, velocities, masses, custom_levels=None, G=0.001, softening=0.1, dt=0.01, device=None):
+        self._handle = C.c_void_p()
+        positions, velocities, masses, self.levels, self.G, self.softening, self.dt = check_fine_grid_arguments(
+            positions, velocities, masses, custom_levels, G, softening, dt)
+        self._construct(positions, velocities, masses, PrecisionMode.CUSTOM, device)
+
+    def _create(self, cfg):
+        levels = (C.c_int32 * len(self.levels))(*self.levels)
+        N.check(N.lib().nb_ens_create_grid_wide(C.byref(self._handle), C.byref(cfg), levels, _doubles(self.G),
+                                                _doubles([s ** 2 for s in self.softening]), _doubles(self.dt)))
