@@ -197,6 +197,31 @@ int nb_ens_create_grid_wide(nb_ens **out, const nb_ens_config *cfg, const int32_
  * hook, so nb_ens_energy gives each member the value of its solo run in its own mode. */
 int nb_ens_create_mixed(nb_ens **out, const nb_ens_config *cfg, const int32_t *modes, const double *G,
                         const double *softening_sq, const double *dt);
+/* Members of different SIZES in one handle (the reference's density sweeps: omega_point_test.py:595-766 scans 100 ..
+ * 2000 stars, density_limit_test.py:206-246 100 .. 4000).  cfg->n is the CAPACITY, the largest member; sizes holds
+ * `members` star counts, each in [1, cfg->n] (else NB_ERR_INVALID naming the member).  cfg->mode is NB_FLOAT64 ..
+ * NB_FLOAT16 (a grid mode: NB_ERR_UNSUPPORTED); modes is NULL for that mode everywhere, else as in nb_ens_create_mixed
+ * (cfg->mode NB_FLOAT32).  Limits as nb_ens_create's, with the capacity for n.  Arguments are refused before a device
+ * is looked for.
+ * Layout: padded, not packed -- the arrays are whole (members, cfg->n, dim) / (members, cfg->n) blocks as on every
+ * handle; member b owns the first sizes[b] rows of its block and NO kernel reads or writes the rows behind them.
+ * nb_ens_set_state / nb_ens_get_state / nb_ens_set_accelerations move whole blocks, padding included.
+ * A tick is ONE force launch ("ens_step_ragged_kernel") over a work list of sum_b ceil(sizes[b] / (512 / lanes))
+ * workgroups, largest members first (nb_ens_ragged_plan), and member b is bit-identical to the nb_sim of its own size
+ * and mode.  The handle is an ordinary nb_ens: step, run_recorded, run_members (with the explosion watch), energies,
+ * divergence and run_diverged work on it with every member's own size; nb_ens_energy returns nb_ens_energies' values
+ * (those of a handle of the member's size alone, bit for bit).  nb_ens_divergence / nb_ens_run_diverged refuse a
+ * baseline of another size than the member's (NB_ERR_INVALID naming both).  NB_ERR_UNSUPPORTED, as follow-ups:
+ * nb_ens_metrics (ragged metrics), nb_ens_crash_measures and nb_ens_run_crash_watched (ragged crash watch),
+ * nb_ens_quant_info and nb_ens_quant_bin_sums (ragged grid modes). */
+int nb_ens_create_ragged(nb_ens **out, const nb_ens_config *cfg, const int32_t *sizes, const int32_t *modes,
+                         const double *G, const double *softening_sq, const double *dt);
+/* The work list of a ragged handle's force launch, without a device: `members` sizes (each >= 1), lanes 16 / 32 /
+ * 64 lanes per target (a workgroup of 512 threads holds 512 / lanes targets).  *items = the number of work items;
+ * work: NULL to ask for the count alone, else room for `capacity` items of {member, blk} (2 int32 each; capacity
+ * below *items: NB_ERR_INVALID).  Members by size descending, ties by index; blk ascending within a member. */
+int nb_ens_ragged_plan(const int32_t *sizes, int32_t members, int32_t lanes, int32_t *work, int64_t capacity,
+                       int64_t *items);
 int nb_ens_destroy(nb_ens *e);
 /* any array may be NULL to keep its values; the device copy is updated on the handle's stream */
 int nb_ens_set_params(nb_ens *e, const double *G, const double *softening_sq, const double *dt);
@@ -328,7 +353,8 @@ int nb_ens_metrics(nb_ens *e, int32_t num_bins, const double *max_radius, double
                    int64_t *curve_count, float *edges, double *scalars);
 /* members; batched force launches issued since creation (nb_ens_compute_accelerations and one per tick;
  * the opening kick + drift launch of an nb_ens_step is not counted); name of the last force kernel
- * ("ens_step_kernel", "ens_step_mixed_kernel" on a handle of nb_ens_create_mixed, or "ens_grid_step_kernel" on a
+ * ("ens_step_kernel", "ens_step_mixed_kernel" on a handle of nb_ens_create_mixed, "ens_step_ragged_kernel" on a
+ * handle of nb_ens_create_ragged, or "ens_grid_step_kernel" on a
  * grid-mode handle -- "ens_grid_step_wide_kernel" when a member exceeds 256 levels -- whose table and finish launches
  * are not counted either; "none" before the first).  Any output may be NULL. */
 int nb_ens_info(nb_ens *e, int32_t *members, int64_t *force_launches, const char **kernel_name);

@@ -130,6 +130,29 @@ __device__ __forceinline__ int ens_kick_mode(int left, int kick)
 {
     return (left == 1 && kick != NB_KICK_NONE) ? NB_KICK_CLOSE : kick;
 }
+// a stopped member's positions into the second buffer: the targets of target block `blk` (the workgroup's own: nobody else
+// writes or reads them there) of a member of n stars
+template <typename T, int D, int S, int BS>
+__device__ __forceinline__ void ens_carry_positions(int blk, const T *__restrict__ pos_in, T *__restrict__ pos_out, int n)
+{
+    constexpr int PER = BS / S * D;                  // elements of this workgroup's targets
+    const int k = blk * PER + threadIdx.x;
+    if (threadIdx.x < PER && k < n * D) pos_out[k] = pos_in[k];
+}
+
+// ---- members of different sizes (nb_ens_create_ragged) ----------------------------------------------------------------------
+// A ragged handle's buffers are strided by the capacity; member b owns the first sizes[b] rows of its slice and no kernel
+// touches the rest.  Every kernel of the tick path that needs the member's own count takes `sizes` (device, one int per
+// member, or null) and comes in two instantiations, as with `stop`: RAGGED = false for a launch without the array, whose
+// code is what it was before there were sizes.  per: elements per row (D, or 1 for stars); count: what a member of a
+// uniform handle has, rows of the stride * per.
+template <bool RAGGED>
+__device__ __forceinline__ int ens_member_count(const int *__restrict__ sizes, int b, int per, int count)
+{
+    if constexpr (RAGGED) return sizes[b] * per;
+    else return count;
+}
+
 // the watch kernels behind a sampled tick t (nb_ens_watch.hip, nb_ens_crash.hip): the member has not stopped before this
 // tick and no earlier check halted it (halted: its reason / kind, 0 = none)
 __device__ __forceinline__ bool ens_still_running(const int *stop, const int *halted, int b, int t)

@@ -31,6 +31,12 @@
 // the members' hooks on the device and launch_force launches ens_step_mixed_kernel, which reads them; everything else is
 // the FLOAT32 handle's.  nb_ens_divergence / nb_ens_run_diverged compare every member with another member of the handle on
 // the device (nb_ens_diverge.hip): the kernel alone, or as part of run_train's samples.
+//
+// nb_ens_create_ragged: members of different sizes.  cfg.n is the capacity, member b owns the first sizes[b] rows of its
+// slice and no kernel touches the rest; launch_force launches ens_step_ragged_kernel over the work list built at creation
+// (nb_plan_ragged), and every other launch of the tick path gets `sizes` (null on every other handle: the instantiations
+// without sizes).  The solo probe has the capacity's shape, so nb_ens_energy returns the batched values there; the entries
+// whose kernels are one workgroup per member of one shape, and the grid modes', refuse such a handle (refuse_ragged).
 #include <algorithm>
 #include <cstddef>
 #include <cstring>
@@ -90,6 +96,12 @@ struct nb_ens {
     int *base_dev = nullptr;
     double *dhist = nullptr;
     int64_t dhist_cap = 0;
+    // members of different sizes (nb_ens_create_ragged): cfg.n is the capacity; every member's size, as given and on the
+    // device (null on every other handle: the kernels without sizes run); the work list of the step, built once
+    std::vector<int32_t> sizes_host;
+    int *sizes = nullptr;
+    EnsWork *work = nullptr;
+    int work_items = 0;
 };
 
 namespace {
@@ -171,6 +183,14 @@ int launch_force(nb_ens *e, int do_kick, const int *stop = nullptr, int t = 0)
 {
     const nb_ens_config &c = e->cfg;
     if (e->grid) return launch_force_grid(e, do_kick, stop, t);
+    if (e->sizes) {
+        HIPCHK(nb_launch_ens_step_ragged(e->pos, e->pos_alt, e->vel, e->acc, e->mass, c.members, c.n, c.dim, e->is_f64,
+                                         e->mixed ? HOOK_AT_RUN_TIME : e->hook, e->prm, do_kick, e->lanes, e->sizes, e->work,
+                                         e->work_items, e->hooks, stop, t, e->stream));
+        e->force_launches++;
+        e->last_kernel = "ens_step_ragged_kernel";
+        return NB_OK;
+    }
     if (e->mixed) {
         HIPCHK(nb_launch_ens_step_mixed((const float *)e->pos, (float *)e->pos_alt, (float *)e->vel, (float *)e->acc,
                                         (const float *)e->mass, c.members, c.n, c.dim, e->prm, do_kick, e->lanes, e->hooks, stop,
@@ -204,7 +224,7 @@ void release(nb_ens *e)
     for (void *p : {e->prm, e->pos, e->pos_alt, e->vel, e->acc, e->mass, (void *)e->epart, (void *)e->ehist, (void *)e->tabs,
                     (void *)e->levels_dev, (void *)e->fpart, (void *)e->fbounds, e->mscratch, (void *)e->mout, (void *)e->mradius,
                     (void *)e->medges, (void *)e->stops, e->prev_pos, (void *)e->dt_dev, (void *)e->crash_out, (void *)e->hooks,
-                    (void *)e->base_dev, (void *)e->dhist, (void *)e->bin_acc, (void *)e->bin_out})
+                    (void *)e->base_dev, (void *)e->dhist, (void *)e->bin_acc, (void *)e->bin_out, (void *)e->sizes, (void *)e->work})
         if (p) (void)hipFree(p);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
@@ -253,6 +273,11 @@ int upload_baselines(nb_ens *e, const int32_t *baseline)
     for (int b = 0; b < B; ++b)
         if (baseline[b] < 0 || baseline[b] >= B)
             return fail(NB_ERR_INVALID, "baseline[%d] = %d is no member: must be in [0, %d)", b, baseline[b], B);
+    for (int b = 0; e->sizes && b < B; ++b)
+        if (e->sizes_host[baseline[b]] != e->sizes_host[b])
+            return fail(NB_ERR_INVALID, "baseline[%d] = %d: member %d has %d stars and member %d has %d; a member is compared "
+                                        "with a member of its own size", b, baseline[b], b, e->sizes_host[b], baseline[b],
+                        e->sizes_host[baseline[b]]);
     e->base_host.assign(baseline, baseline + B);
     static_assert(sizeof(int32_t) == sizeof(int), "the kernel reads ints");
     HIPCHK(hipMemcpyAsync(e->base_dev, e->base_host.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, e->stream));
@@ -265,7 +290,7 @@ int launch_divergence(nb_ens *e, int64_t s)
     const nb_ens_config &c = e->cfg;
     const size_t plane = (size_t)e->dhist_cap * c.members;
     HIPCHK(nb_launch_ens_divergence(e->pos, e->vel, c.members, c.n, c.dim, e->is_f64, e->base_dev, s, e->dhist,
-                                    e->dhist + plane, e->dhist + 2 * plane, e->stream));
+                                    e->dhist + plane, e->dhist + 2 * plane, e->stream, e->sizes));
     return NB_OK;
 }
 
@@ -314,7 +339,7 @@ int launch_energy(nb_ens *e, int64_t s, bool with_kinetic)
 {
     const nb_ens_config &c = e->cfg;
     HIPCHK(nb_launch_ens_energy(e->pos, with_kinetic ? e->vel : nullptr, e->mass, c.members, c.n, c.dim, e->is_f64, e->prm,
-                                e->epart, e->ehist, e->ehist + e->ehist_cap * c.members, s, e->stream));
+                                e->epart, e->ehist, e->ehist + e->ehist_cap * c.members, s, e->stream, e->sizes));
     return NB_OK;
 }
 
@@ -343,7 +368,8 @@ int run_train(nb_ens *e, int32_t nmax, int32_t every, int *stop, WatchMode watch
 {
     const nb_ens_config &c = e->cfg;
     auto open_tick = [&](int t) {
-        return nb_launch_ens_kick_drift(e->pos, e->vel, e->acc, c.members, c.n, c.dim, e->is_f64, e->prm, stop, t, e->stream);
+        return nb_launch_ens_kick_drift(e->pos, e->vel, e->acc, c.members, c.n, c.dim, e->is_f64, e->prm, stop, t, e->stream,
+                                        e->sizes);
     };
     if (what & SAMPLE_ENERGIES)
         if (int rc = launch_energy(e, 0, true)) return rc;
@@ -359,7 +385,7 @@ int run_train(nb_ens *e, int32_t nmax, int32_t every, int *stop, WatchMode watch
                 if (watch == WATCH_EXPLOSION)
                     HIPCHK(nb_launch_ens_watch(e->pos, e->vel, c.members, c.n, c.dim, e->is_f64, e->ehist,
                                                e->ehist + e->ehist_cap * c.members, t / every, t, stop, stop + c.members,
-                                               e->stream));
+                                               e->stream, e->sizes));
                 else if (watch == WATCH_CRASH)
                     HIPCHK(nb_launch_ens_crash(e->pos, e->prev_pos, e->vel, c.members, c.n, c.dim, e->is_f64, e->dt_dev, e->ehist,
                                                e->ehist + e->ehist_cap * c.members, t / every, t, stop, stop + c.members,
@@ -463,6 +489,16 @@ int metrics_buffers(nb_ens *e, int num_bins)
     return NB_OK;
 }
 
+// the entries a handle of nb_ens_create_ragged refuses: their kernels are one workgroup per member of the handle's n, or
+// the grid modes'
+int refuse_ragged(const nb_ens *e, const char *entry, const char *follow_up)
+{
+    if (e->sizes)
+        return fail(NB_ERR_UNSUPPORTED, "%s is not implemented for members of different sizes (nb_ens_create_ragged): %s is a "
+                                        "follow-up", entry, follow_up);
+    return NB_OK;
+}
+
 // what both constructors ask of the shape
 int check_shape(const nb_ens_config *cfg)
 {
@@ -537,6 +573,36 @@ int create(nb_ens **out, const nb_ens_config *cfg, const int32_t *levels, const 
     return NB_OK;
 }
 
+// modes[0 .. members) of a handle whose members have their own cast modes (cfg->mode: NB_FLOAT32)
+int check_mode_list(const nb_ens_config *cfg, const int32_t *modes)
+{
+    for (int b = 0; b < cfg->members; ++b)
+        if (modes[b] != NB_FLOAT32 && modes[b] != NB_BFLOAT16 && modes[b] != NB_FLOAT16)
+            return fail(NB_ERR_UNSUPPORTED, "modes[%d] = %d: members of one ensemble mix the FLOAT32, BFLOAT16 and FLOAT16 modes "
+                                            "only (FLOAT64 is stored differently, the grid modes need per-member tables)", b,
+                        modes[b]);
+    return NB_OK;
+}
+
+// the members' hooks onto the device of a freshly created handle (released on failure)
+int attach_hooks(nb_ens *e, const int32_t *modes)
+{
+    DeviceGuard guard(e->cfg.device);
+    const int B = e->cfg.members;
+    e->mixed = true;
+    e->hooks_host.resize(B);
+    for (int b = 0; b < B; ++b) e->hooks_host[b] = mode_hook(modes[b]);
+    const size_t bytes = (size_t)B * sizeof(int);
+    hipError_t he = hipMalloc((void **)&e->hooks, bytes);
+    if (he == hipSuccess) he = hipMemcpyAsync(e->hooks, e->hooks_host.data(), bytes, hipMemcpyHostToDevice, e->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+    if (he != hipSuccess) {
+        release(e);
+        return fail(he == hipErrorOutOfMemory ? NB_ERR_OOM : NB_ERR_HIP, "ensemble allocation failed: %s", hipGetErrorString(he));
+    }
+    return NB_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -599,26 +665,74 @@ int nb_ens_create_mixed(nb_ens **out, const nb_ens_config *cfg, const int32_t *m
     if (cfg->mode != NB_FLOAT32)
         return fail(NB_ERR_UNSUPPORTED, "nb_ens_create_mixed: cfg->mode must be NB_FLOAT32, the storage mode of every cast mode "
                                         "(got mode %d)", cfg->mode);
-    for (int b = 0; b < cfg->members; ++b)
-        if (modes[b] != NB_FLOAT32 && modes[b] != NB_BFLOAT16 && modes[b] != NB_FLOAT16)
-            return fail(NB_ERR_UNSUPPORTED, "modes[%d] = %d: members of one ensemble mix the FLOAT32, BFLOAT16 and FLOAT16 modes "
-                                            "only (FLOAT64 is stored differently, the grid modes need per-member tables)", b,
-                        modes[b]);
+    if (int rc = check_mode_list(cfg, modes)) return rc;
     nb_ens *e = nullptr;
     if (int rc = create(&e, cfg, nullptr, G, softening_sq, dt)) return rc;
+    if (int rc = attach_hooks(e, modes)) return rc;
+    *out = e;
+    return NB_OK;
+}
+
+int nb_ens_create_ragged(nb_ens **out, const nb_ens_config *cfg, const int32_t *sizes, const int32_t *modes, const double *G,
+                         const double *softening_sq, const double *dt)
+{
+    if (!out || !cfg || !sizes || !G || !softening_sq || !dt) return fail(NB_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (int rc = check_shape(cfg)) return rc;
+    if (cfg->mode < NB_FLOAT64 || cfg->mode > NB_FLOAT16)
+        return fail(NB_ERR_UNSUPPORTED, "nb_ens_create_ragged runs the FLOAT64, FLOAT32, BFLOAT16 and FLOAT16 modes (got mode %d): "
+                                        "the ragged grid modes are a follow-up", cfg->mode);
+    if (modes && cfg->mode != NB_FLOAT32)
+        return fail(NB_ERR_UNSUPPORTED, "nb_ens_create_ragged: with a mode list cfg->mode must be NB_FLOAT32, the storage mode of "
+                                        "every cast mode (got mode %d)", cfg->mode);
+    if (modes)
+        if (int rc = check_mode_list(cfg, modes)) return rc;
+    for (int b = 0; b < cfg->members; ++b)
+        if (sizes[b] < 1 || sizes[b] > cfg->n)
+            return fail(NB_ERR_INVALID, "sizes[%d] = %d is outside [1, %d]: member %d must fit the capacity cfg->n", b, sizes[b],
+                        cfg->n, b);
+    nb_ens *e = nullptr;
+    if (int rc = create(&e, cfg, nullptr, G, softening_sq, dt)) return rc;
+    if (modes)
+        if (int rc = attach_hooks(e, modes)) return rc;
     DeviceGuard guard(cfg->device);
-    e->mixed = true;
-    e->hooks_host.resize(cfg->members);
-    for (int b = 0; b < cfg->members; ++b) e->hooks_host[b] = mode_hook(modes[b]);
-    const size_t bytes = (size_t)cfg->members * sizeof(int);
-    hipError_t he = hipMalloc((void **)&e->hooks, bytes);
-    if (he == hipSuccess) he = hipMemcpyAsync(e->hooks, e->hooks_host.data(), bytes, hipMemcpyHostToDevice, e->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+    const int B = cfg->members;
+    e->sizes_host.assign(sizes, sizes + B);
+    std::vector<EnsWork> work;
+    e->work_items = (int)nb_plan_ragged(sizes, B, e->lanes, &work);
+    static_assert(sizeof(int32_t) == sizeof(int), "the kernels read ints");
+    hipError_t he = hipMalloc((void **)&e->work, work.size() * sizeof(EnsWork));
+    if (he == hipSuccess) he = hipMemcpyAsync(e->work, work.data(), work.size() * sizeof(EnsWork), hipMemcpyHostToDevice, e->stream);
+    // sizes last: a handle that holds them is complete
+    int *dev_sizes = nullptr;
+    if (he == hipSuccess) he = hipMalloc((void **)&dev_sizes, (size_t)B * sizeof(int));
+    if (he == hipSuccess) he = hipMemcpyAsync(dev_sizes, e->sizes_host.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, e->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);       // (the uploads have consumed `work`)
+    e->sizes = dev_sizes;
     if (he != hipSuccess) {
         release(e);
         return fail(he == hipErrorOutOfMemory ? NB_ERR_OOM : NB_ERR_HIP, "ensemble allocation failed: %s", hipGetErrorString(he));
     }
     *out = e;
+    return NB_OK;
+}
+
+int nb_ens_ragged_plan(const int32_t *sizes, int32_t members, int32_t lanes, int32_t *work, int64_t capacity, int64_t *items)
+{
+    if (!sizes || !items) return fail(NB_ERR_INVALID, "null argument");
+    *items = 0;
+    if (members < 1 || members > NB_ENS_MAX_MEMBERS)
+        return fail(NB_ERR_INVALID, "members must be in [1, %d] (got %d)", NB_ENS_MAX_MEMBERS, members);
+    if (lanes != 16 && lanes != 32 && lanes != 64) return fail(NB_ERR_INVALID, "lanes must be 16, 32 or 64 (got %d)", lanes);
+    for (int b = 0; b < members; ++b)
+        if (sizes[b] < 1) return fail(NB_ERR_INVALID, "sizes[%d] = %d: member %d must have at least one star", b, sizes[b], b);
+    std::vector<EnsWork> list;
+    *items = nb_plan_ragged(sizes, members, lanes, work ? &list : nullptr);
+    if (!work) return NB_OK;
+    if (capacity < *items)
+        return fail(NB_ERR_INVALID, "capacity of %lld work items is below the %lld of this list", (long long)capacity,
+                    (long long)*items);
+    for (size_t w = 0; w < list.size(); ++w) { work[2 * w] = list[w].member; work[2 * w + 1] = list[w].blk; }
     return NB_OK;
 }
 
@@ -650,6 +764,9 @@ int nb_ens_set_state(nb_ens *e, const void *pos, const void *vel, const void *ma
                                         "timeline are nb_sim's", e->is_f64 ? "fp64" : "fp32", dtype);
     DeviceGuard guard(e->cfg.device);
     if (pos) { if (int rc = copy_in(e, e->pos, pos, cnt_nd(e), on_device)) return rc; e->have_pos = true; }
+    // a ragged handle: the second buffer too -- no kernel writes the rows behind a member's own, so after a swap they would
+    // hold whatever the allocation held instead of the caller's padding
+    if (pos && e->sizes) if (int rc = copy_in(e, e->pos_alt, pos, cnt_nd(e), on_device)) return rc;
     if (vel) { if (int rc = copy_in(e, e->vel, vel, cnt_nd(e), on_device)) return rc; e->have_vel = true; }
     if (mass) { if (int rc = copy_in(e, e->mass, mass, cnt_n(e), on_device)) return rc; e->have_mass = true; }
     HIPCHK(hipStreamSynchronize(e->stream));      // the copies have consumed the caller's buffers
@@ -705,6 +822,14 @@ int nb_ens_energy(nb_ens *e, double *kinetic, double *potential)
     if (!e->have_mass || (kinetic && !e->have_vel) || (potential && !e->have_pos)) return fail(NB_ERR_INVALID, "state incomplete");
     DeviceGuard guard(e->cfg.device);
     const nb_ens_config &c = e->cfg;
+    if (e->sizes) {
+        // the probe has the capacity's shape, not the member's: a ragged member's energies are the batched kernels', which
+        // give it the values of a handle of its own size (nb_ens_energy.hip)
+        if (!e->have_pos || (kinetic && !e->have_vel)) return fail(NB_ERR_INVALID, "state incomplete");
+        if (int rc = energy_buffers(e, 1)) return rc;
+        if (int rc = launch_energy(e, 0, kinetic != nullptr)) return rc;
+        return history_out(e, 1, kinetic, potential, 0);
+    }
     if (!e->probe) {
         nb_config pc{};
         pc.n = c.n; pc.dim = c.dim; pc.mode = c.mode; pc.G = e->G[0]; pc.softening_sq = e->eps2[0]; pc.dt = e->dt[0];
@@ -766,6 +891,7 @@ int nb_ens_run_members(nb_ens *e, const int32_t *nsteps, int32_t every, int32_t 
 int nb_ens_crash_measures(nb_ens *e, const void *prev_pos, int on_device, int32_t *flags, double *measures)
 {
     if (!e) return fail(NB_ERR_INVALID, "null handle");
+    if (int rc = refuse_ragged(e, "nb_ens_crash_measures", "the ragged crash watch")) return rc;
     if (!e->have_pos || !e->have_vel) return fail(NB_ERR_INVALID, "state incomplete");
     DeviceGuard guard(e->cfg.device);
     const nb_ens_config &c = e->cfg;
@@ -789,6 +915,7 @@ int nb_ens_run_crash_watched(nb_ens *e, const int32_t *nsteps, double *kinetic, 
 {
     if (samples) *samples = 0;
     if (int rc = check_steppable(e)) return rc;
+    if (int rc = refuse_ragged(e, "nb_ens_run_crash_watched", "the ragged crash watch")) return rc;
     int32_t nmax = 0;
     if (int rc = check_budgets(e, nsteps, &nmax)) return rc;
     return run_sampled(e, nsteps, nmax, 1, WATCH_CRASH, kinetic, potential, capacity, on_device, samples, stop_tick, kind, flags,
@@ -844,6 +971,7 @@ int nb_ens_metrics(nb_ens *e, int32_t num_bins, const double *max_radius, double
                    int64_t *curve_count, float *edges, double *scalars)
 {
     if (!e) return fail(NB_ERR_INVALID, "null handle");
+    if (int rc = refuse_ragged(e, "nb_ens_metrics", "ragged metrics")) return rc;
     if (!e->have_pos || !e->have_vel || !e->have_mass) return fail(NB_ERR_INVALID, "state incomplete");
     if (num_bins < 0 || num_bins > 255) return fail(NB_ERR_INVALID, "num_bins must be in [0, 255] (got %d)", num_bins);
     if (percentile != percentile) return fail(NB_ERR_INVALID, "percentile is NaN");
@@ -904,6 +1032,7 @@ int nb_ens_info(nb_ens *e, int32_t *members, int64_t *force_launches, const char
 int nb_ens_quant_info(nb_ens *e, double *out)
 {
     if (!e || !out) return fail(NB_ERR_INVALID, "null argument");
+    if (int rc = refuse_ragged(e, "nb_ens_quant_info", "the ragged grid modes")) return rc;
     if (!e->grid) return fail(NB_ERR_UNSUPPORTED, "quant info is only defined for the grid modes (nb_ens_create_grid)");
     DeviceGuard guard(e->cfg.device);
     const size_t B = (size_t)e->cfg.members;
@@ -930,6 +1059,7 @@ int nb_ens_quant_info(nb_ens *e, double *out)
 int nb_ens_quant_bin_sums(nb_ens *e, int64_t *sum_k, int64_t *sum_kw, int64_t *pairs)
 {
     if (!e) return fail(NB_ERR_INVALID, "null handle");
+    if (int rc = refuse_ragged(e, "nb_ens_quant_bin_sums", "the ragged grid modes")) return rc;
     if (!e->grid) return fail(NB_ERR_UNSUPPORTED, "the quant-bin read-out is only defined for the grid modes (nb_ens_create_grid, "
                                                   "nb_ens_create_grid_wide)");
     if (!e->have_pos || !e->have_mass) return fail(NB_ERR_INVALID, "positions/masses not set");

@@ -51,11 +51,13 @@ __device__ __forceinline__ T wave_max_plain(T m)
     return m;
 }
 
-template <typename T, int D>
+// RAGGED (sizes: nb_device.h): n is the stride of a member's slice; the member compares its own sizes[b] * D elements with
+// its baseline's (of the same size: the host has checked) and divides the mean by that count
+template <typename T, int D, bool RAGGED>
 __global__ void __launch_bounds__(ED_THREADS)
 ens_divergence_kernel(const T *__restrict__ pos, const T *__restrict__ vel, int n, int members,
                       const int *__restrict__ baseline, int64_t sample, double *__restrict__ max_pos,
-                      double *__restrict__ mean_pos, double *__restrict__ max_vel)
+                      double *__restrict__ mean_pos, double *__restrict__ max_vel, const int *__restrict__ sizes)
 {
     __shared__ T s_max[ED_WAVES][2];
     __shared__ double s_sum[ED_WAVES];
@@ -63,8 +65,8 @@ ens_divergence_kernel(const T *__restrict__ pos, const T *__restrict__ vel, int 
     const int b = blockIdx.x;                        // member: uniform per workgroup
     int base = baseline[b];
     if ((unsigned)base >= (unsigned)members) base = b;     // (the host has checked the range: never read outside the state)
-    const int count = n * D;
-    const size_t o = (size_t)b * count, ob = (size_t)base * count;
+    const size_t o = (size_t)b * (n * D), ob = (size_t)base * (n * D);
+    const int count = ens_member_count<RAGGED>(sizes, b, D, n * D);
     NanMax<T> mp{(T)0, false}, mv{(T)0, false};
     double sum = 0.0;
     for (int k = threadIdx.x; k < count; k += ED_THREADS) {
@@ -106,16 +108,19 @@ ens_divergence_kernel(const T *__restrict__ pos, const T *__restrict__ vel, int 
 }  // namespace
 
 hipError_t nb_launch_ens_divergence(const void *pos, const void *vel, int members, int n, int dim, int is_f64, const int *baseline,
-                                    int64_t sample, double *max_pos, double *mean_pos, double *max_vel, hipStream_t st)
+                                    int64_t sample, double *max_pos, double *mean_pos, double *max_vel, hipStream_t st,
+                                    const int *sizes)
 {
     if (members < 1 || members > NB_ENS_MAX_MEMBERS || n < 1 || sample < 0) return hipErrorInvalidValue;
     if (!pos || !vel || !baseline || !max_pos || !mean_pos || !max_vel) return hipErrorInvalidValue;
     return nb::pick_real(is_f64, [&](auto real) {
         using T = typename decltype(real)::type;
         return nb::pick<2, 3>(dim, [&](auto D) {
-            hipLaunchKernelGGL((ens_divergence_kernel<T, D.value>), dim3(members), dim3(ED_THREADS), 0, st, (const T *)pos,
-                               (const T *)vel, n, members, baseline, sample, max_pos, mean_pos, max_vel);
-            return hipGetLastError();
+            return nb::pick_bool(sizes != nullptr, [&](auto RG) {
+                hipLaunchKernelGGL((ens_divergence_kernel<T, D.value, RG.value>), dim3(members), dim3(ED_THREADS), 0, st,
+                                   (const T *)pos, (const T *)vel, n, members, baseline, sample, max_pos, mean_pos, max_vel, sizes);
+                return hipGetLastError();
+            });
         });
     });
 }

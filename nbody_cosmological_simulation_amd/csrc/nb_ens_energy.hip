@@ -39,25 +39,34 @@ __device__ __forceinline__ double pair_term(const double (&d)[D], double eps2, d
     return (mi * mj) * (y0 * c);
 }
 
-template <typename T, int D>
+// RAGGED (sizes: nb_device.h): n is the stride of a member's slice and ntiles the grid's; the member cuts its OWN stars into
+// tiles, the workgroups past its own tile pairs return, and its slots are the first of its gridDim.x: the {pe, ke} a
+// handle of that size alone would write, in the same slots
+template <typename T, int D, bool RAGGED>
 __global__ void __launch_bounds__(EE_TILE)
 ens_energy_partials_kernel(const T *__restrict__ pos, const T *__restrict__ vel /* null: no kinetic terms */,
                            const T *__restrict__ mass, int n, int ntiles, const EnsScalars<T> *__restrict__ prm,
-                           double *__restrict__ part)
+                           double *__restrict__ part, const int *__restrict__ sizes)
 {
     __shared__ T sx[D][EE_TILE];
     __shared__ T sm[EE_TILE];
     __shared__ double s_red[2][EE_WAVES];
     const int b = blockIdx.y;                        // member: uniform per workgroup
     const int tid = threadIdx.x;
+    const size_t stride = (size_t)n;                 // stars of a member's slice
+    if constexpr (RAGGED) {
+        n = ens_member_count<true>(sizes, b, 1, n);
+        ntiles = (n + EE_TILE - 1) / EE_TILE;
+        if ((int)blockIdx.x >= ntiles * (ntiles + 1) / 2) return;
+    }
     // blockIdx.x -> (ti, tj), ti <= tj: row ti of the upper triangle holds ntiles - ti pairs
     int ti = 0, rem = blockIdx.x;
     while (rem >= ntiles - ti) { rem -= ntiles - ti; ++ti; }
     const int tj = ti + rem;
     const bool diag = ti == tj;
     const T eps2 = prm[b].eps2;
-    const T *p = pos + (size_t)b * n * D;
-    const T *m = mass + (size_t)b * n;
+    const T *p = pos + (size_t)b * stride * D;
+    const T *m = mass + (size_t)b * stride;
 
     const int j0 = tj * EE_TILE;
     const int cnt = min(EE_TILE, n - j0);            // >= 1: tj < ntiles
@@ -104,7 +113,7 @@ ens_energy_partials_kernel(const T *__restrict__ pos, const T *__restrict__ vel 
 
     double ke = 0.0;
     if (diag && live && vel) {
-        const T *v = vel + ((size_t)b * n + i) * D;
+        const T *v = vel + ((size_t)b * stride + i) * D;
         if constexpr (sizeof(T) == 8) {
             double v2 = __dmul_rn(v[0], v[0]);
 #pragma unroll
@@ -135,13 +144,19 @@ ens_energy_partials_kernel(const T *__restrict__ pos, const T *__restrict__ vel 
     }
 }
 
-template <typename T>
+// RAGGED: npairs is the stride of a member's slots, of which it adds its own first pairs(sizes[b])
+template <typename T, bool RAGGED>
 __global__ void __launch_bounds__(64)
 ens_energy_finish_kernel(const double *__restrict__ part, int npairs, int members, const EnsScalars<T> *__restrict__ prm,
-                         double *__restrict__ kinetic, double *__restrict__ potential, int64_t sample)
+                         double *__restrict__ kinetic, double *__restrict__ potential, int64_t sample,
+                         const int *__restrict__ sizes)
 {
     const int b = blockIdx.x;
     const double *slots = part + (size_t)b * npairs * 2;
+    if constexpr (RAGGED) {
+        const int ntiles = (ens_member_count<true>(sizes, b, 1, 0) + EE_TILE - 1) / EE_TILE;
+        npairs = ntiles * (ntiles + 1) / 2;
+    }
     double pe = 0.0, ke = 0.0;
     for (int s = threadIdx.x; s < npairs; s += 64) {
         pe += slots[2 * s];
@@ -173,7 +188,7 @@ int nb_ens_energy_pairs(int n)
 
 hipError_t nb_launch_ens_energy(const void *pos, const void *vel, const void *mass, int members, int n, int dim, int is_f64,
                                 const void *prm, double *part, double *kinetic, double *potential, int64_t sample,
-                                hipStream_t st)
+                                hipStream_t st, const int *sizes)
 {
     if (members < 1 || members > NB_ENS_MAX_MEMBERS || n < 1 || (dim != 2 && dim != 3)) return hipErrorInvalidValue;
     if (!pos || !mass || !prm || !part || !kinetic || !potential || sample < 0) return hipErrorInvalidValue;
@@ -182,14 +197,16 @@ hipError_t nb_launch_ens_energy(const void *pos, const void *vel, const void *ma
     return nb::pick_real(is_f64, [&](auto real) {
         using T = typename decltype(real)::type;
         const EnsScalars<T> *p = (const EnsScalars<T> *)prm;
-        const hipError_t err = nb::pick<2, 3>(dim, [&](auto D) {
-            hipLaunchKernelGGL((ens_energy_partials_kernel<T, D.value>), grid, dim3(EE_TILE), 0, st, (const T *)pos, (const T *)vel,
-                               (const T *)mass, n, ntiles, p, part);
+        return nb::pick_bool(sizes != nullptr, [&](auto RG) {
+            const hipError_t err = nb::pick<2, 3>(dim, [&](auto D) {
+                hipLaunchKernelGGL((ens_energy_partials_kernel<T, D.value, RG.value>), grid, dim3(EE_TILE), 0, st, (const T *)pos,
+                                   (const T *)vel, (const T *)mass, n, ntiles, p, part, sizes);
+                return hipGetLastError();
+            });
+            if (err != hipSuccess) return err;
+            hipLaunchKernelGGL((ens_energy_finish_kernel<T, RG.value>), dim3(members), dim3(64), 0, st, (const double *)part, npairs,
+                               members, p, kinetic, potential, sample, sizes);
             return hipGetLastError();
         });
-        if (err != hipSuccess) return err;
-        hipLaunchKernelGGL((ens_energy_finish_kernel<T>), dim3(members), dim3(64), 0, st, (const double *)part, npairs, members, p,
-                           kinetic, potential, sample);
-        return hipGetLastError();
     });
 }

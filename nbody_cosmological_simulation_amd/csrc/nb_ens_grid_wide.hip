@@ -12,15 +12,6 @@ namespace {
 
 using namespace nbdev;
 
-// as in nb_ensemble.hip: a stopped member's positions into the second buffer (this workgroup's own targets)
-template <typename T, int D, int S, int BS>
-__device__ __forceinline__ void ens_carry_positions(const T *__restrict__ pos_in, T *__restrict__ pos_out, int n)
-{
-    constexpr int PER = BS / S * D;                  // elements of this workgroup's targets
-    const int k = blockIdx.x * PER + threadIdx.x;
-    if (threadIdx.x < PER && k < n * D) pos_out[k] = pos_in[k];
-}
-
 // CUSTOM members of up to NB_MAX_LUT levels (nb_ens_create_grid_wide, launched when a member exceeds NB_LUT_MIN): the same
 // kernel with the tables in dynamic LDS, 2 (cap + 1) floats with cap = nb_lut_pad of the launch's widest member -- at most
 // 32 776 bytes beside the 16 KiB source tile (D = 3) -- so the workgroups per CU follow the grid actually used.  Every
@@ -38,7 +29,7 @@ ens_grid_step_wide_kernel(const float *__restrict__ pos_in, float *__restrict__ 
     const size_t o = (size_t)b * n;
     const int left = ens_ticks_left<STOPS>(stop, b, t);
     if (STOPS && left <= 1) {
-        ens_carry_positions<float, D, S, BS>(pos_in + o * D, pos_out + o * D, n);
+        ens_carry_positions<float, D, S, BS>(blockIdx.x, pos_in + o * D, pos_out + o * D, n);
         if (left <= 0) return;
         do_kick = ens_kick_mode(left, do_kick);
     }

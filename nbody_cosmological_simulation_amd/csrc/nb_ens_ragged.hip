@@ -1,0 +1,94 @@
+// nb_ens_ragged.hip -- members of different sizes in one launch per tick (nb_ens_create_ragged, include/nbody_amd.h).
+//
+// The handle is an ordinary nb_ens whose n is the CAPACITY, the largest member: member b lives at offset b * capacity of the
+// (B, capacity, D) / (B, capacity) buffers and owns the first sizes[b] rows; the rows behind them are padding that no kernel
+// reads or writes.  A (blocks, members) grid sized for the capacity would launch capacity / 8 workgroups for a member of 16
+// stars, so the launch runs over a 1-D list of work items instead (nb_plan_ragged, nb_plan.cpp): workgroup w reads
+// work[w] = {member, blk} and runs the solo step's body (nb_small_body.h) on targets [blk * TG, (blk + 1) * TG) of that
+// member with the member's own n and scalars.  The list holds the largest members first, blk ascending within a member:
+// workgroups are dispatched in index order and a large member's workgroup streams more sources, so the tick ends with the
+// short items.
+//
+// Why ONE workgroup size serves every member bit for bit: in small_step_body a target's sum depends on S (lane l takes
+// sources l, l + S, ... of every SM_TILE tile, then the fixed butterfly over the S lanes), on SM_TILE and on the member's n
+// -- not on BS, which only decides which targets share a workgroup and how the threads split the staging of a tile that
+// holds the same values either way.  A solo run takes 256 threads for n in 2049 .. 3072 and 512 elsewhere; the member's
+// bits are the same under NB_ENS_RAGGED_BLOCK (512) at every size.
+//
+// The hook is compiled in (a uniform handle) or HOOK_AT_RUN_TIME with hooks[member] (a mode list), as ens_step_kernel and
+// ens_step_mixed_kernel have it; the stop rule is theirs (nb_device.h), with blk from the work item.
+#include "nb_dispatch.h"
+#include "nb_small_body.h"
+#include "nb_internal.h"
+
+namespace {
+
+using namespace nbdev;
+
+constexpr int ER_BLOCK = NB_ENS_RAGGED_BLOCK;
+
+// waves per SIMD: 8, what ens_step_kernel / ens_step_mixed_kernel come out at by themselves (at most 55 VGPRs).  Left to
+// itself the compiler gives the fp64 instantiations here 84 - 96 VGPRs (the four unrolled pairs interleaved) and 5 waves
+// per SIMD: two 512-thread workgroups per CU instead of four.  With the attribute they have ens_step_kernel's registers
+// (profiles/ensemble_ragged_step_resources.txt); no instantiation spills.
+template <typename T, int D, int HOOK, int S, bool STOPS>
+__global__ void __launch_bounds__(ER_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8)))
+ens_step_ragged_kernel(const T *__restrict__ pos_in, T *__restrict__ pos_out, T *__restrict__ vel, T *__restrict__ acc,
+                       const T *__restrict__ mass, int cap, const int *__restrict__ sizes, const EnsWork *__restrict__ work,
+                       const EnsScalars<T> *__restrict__ prm, int do_kick, const int *__restrict__ hooks,
+                       const int *__restrict__ stop, int t)
+{
+    const EnsWork w = work[blockIdx.x];              // member and target block: uniform per workgroup
+    const int b = w.member;
+    const int n = ens_member_count<true>(sizes, b, 1, cap);
+    const EnsScalars<T> p = prm[b];
+    const size_t o = (size_t)b * cap;
+    const int left = ens_ticks_left<STOPS>(stop, b, t);
+    if (STOPS && left <= 1) {
+        ens_carry_positions<T, D, S, ER_BLOCK>(w.blk, pos_in + o * D, pos_out + o * D, n);
+        if (left <= 0) return;
+        do_kick = ens_kick_mode(left, do_kick);
+    }
+    int hook_rt = HOOK_NONE;
+    if constexpr (HOOK == HOOK_AT_RUN_TIME) hook_rt = hooks[b];
+    small_step_body<T, D, HOOK, S, ER_BLOCK>(w.blk, pos_in + o * D, pos_out + o * D, vel + o * D, acc + o * D, mass + o, n,
+                                             p.G, p.eps2, p.half_dt, p.dt, do_kick, nullptr, hook_rt);
+}
+
+template <typename T, int D, int HOOK>
+hipError_t launch_r(const void *pos_in, void *pos_out, void *vel, void *acc, const void *mass, int cap, const int *sizes,
+                    const EnsWork *work, int items, const void *prm, int do_kick, int lanes, const int *hooks, const int *stop,
+                    int t, hipStream_t st)
+{
+    return nb::pick<64, 32, 16>(lanes, [&](auto S) {
+        return nb::pick_bool(stop != nullptr, [&](auto ST) {
+            hipLaunchKernelGGL((ens_step_ragged_kernel<T, D, HOOK, S.value, ST.value>), dim3(items), dim3(ER_BLOCK), 0, st,
+                               (const T *)pos_in, (T *)pos_out, (T *)vel, (T *)acc, (const T *)mass, cap, sizes, work,
+                               (const EnsScalars<T> *)prm, do_kick, hooks, stop, t);
+            return hipGetLastError();
+        });
+    });
+}
+
+}  // namespace
+
+hipError_t nb_launch_ens_step_ragged(const void *pos_in, void *pos_out, void *vel, void *acc, const void *mass, int members,
+                                     int cap, int dim, int is_f64, int hook, const void *prm, int do_kick, int lanes,
+                                     const int *sizes, const EnsWork *work, int items, const int *hooks, const int *stop, int t,
+                                     hipStream_t st)
+{
+    if (members < 1 || members > NB_ENS_MAX_MEMBERS || cap < 1 || !sizes || !work || items < 1 || t < 0) return hipErrorInvalidValue;
+    if ((do_kick & NB_KICK_MODE_MASK) == NB_KICK_CLOSE_SPEC || (do_kick & NB_KICK_OPEN_ON_READ)) return hipErrorInvalidValue;
+    if (hook == HOOK_AT_RUN_TIME && (is_f64 || !hooks)) return hipErrorInvalidValue;
+    return nb::pick<2, 3>(dim, [&](auto D) {
+        if (is_f64)
+            return nb::pick<HOOK_NONE>(hook, [&](auto H) {
+                return launch_r<double, D.value, H.value>(pos_in, pos_out, vel, acc, mass, cap, sizes, work, items, prm, do_kick,
+                                                          lanes, hooks, stop, t, st);
+            });
+        return nb::pick<HOOK_NONE, HOOK_BF16, HOOK_F16, HOOK_AT_RUN_TIME>(hook, [&](auto H) {
+            return launch_r<float, D.value, H.value>(pos_in, pos_out, vel, acc, mass, cap, sizes, work, items, prm, do_kick, lanes,
+                                                     hooks, stop, t, st);
+        });
+    });
+}

@@ -22,18 +22,20 @@ using namespace nbdev;
 
 constexpr int EW_THREADS = 256;
 
-template <typename T>
+// RAGGED (sizes, dim: nb_device.h): count is the stride of a member's slice, of which it scans its own sizes[b] * dim
+template <typename T, bool RAGGED>
 __global__ void __launch_bounds__(EW_THREADS)
 ens_watch_kernel(const T *__restrict__ pos, const T *__restrict__ vel, int count /* n * D */, int members,
                  const double *__restrict__ kinetic, const double *__restrict__ potential, int64_t sample, int t,
-                 int *__restrict__ stop, int *__restrict__ reason)
+                 int *__restrict__ stop, int *__restrict__ reason, const int *__restrict__ sizes, int dim)
 {
     __shared__ int s_bad[EW_THREADS / 64];
     const int b = blockIdx.x;                        // member: uniform per workgroup
     if (!ens_still_running(stop, reason, b, t)) return;
     const size_t o = (size_t)b * count;
+    const int mine = ens_member_count<RAGGED>(sizes, b, dim, count);
     bool bad = false;
-    for (int k = threadIdx.x; k < count; k += EW_THREADS) {
+    for (int k = threadIdx.x; k < mine; k += EW_THREADS) {
         const T x = pos[o + k], v = vel[o + k];
         bad = bad || non_finite(x) || non_finite(v);
     }
@@ -59,14 +61,17 @@ ens_watch_kernel(const T *__restrict__ pos, const T *__restrict__ vel, int count
 }  // namespace
 
 hipError_t nb_launch_ens_watch(const void *pos, const void *vel, int members, int n, int dim, int is_f64, const double *kinetic,
-                               const double *potential, int64_t sample, int t, int *stop, int *reason, hipStream_t st)
+                               const double *potential, int64_t sample, int t, int *stop, int *reason, hipStream_t st,
+                               const int *sizes)
 {
     if (members < 1 || members > NB_ENS_MAX_MEMBERS || n < 1 || (dim != 2 && dim != 3)) return hipErrorInvalidValue;
     if (!pos || !vel || !kinetic || !potential || !stop || !reason || sample < 1 || t < 1) return hipErrorInvalidValue;
     return nb::pick_real(is_f64, [&](auto real) {
         using T = typename decltype(real)::type;
-        hipLaunchKernelGGL((ens_watch_kernel<T>), dim3(members), dim3(EW_THREADS), 0, st, (const T *)pos, (const T *)vel, n * dim,
-                           members, kinetic, potential, sample, t, stop, reason);
-        return hipGetLastError();
+        return nb::pick_bool(sizes != nullptr, [&](auto RG) {
+            hipLaunchKernelGGL((ens_watch_kernel<T, RG.value>), dim3(members), dim3(EW_THREADS), 0, st, (const T *)pos,
+                               (const T *)vel, n * dim, members, kinetic, potential, sample, t, stop, reason, sizes, dim);
+            return hipGetLastError();
+        });
     });
 }

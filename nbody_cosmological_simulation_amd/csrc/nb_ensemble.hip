@@ -10,6 +10,9 @@
 // (ens_grid_step_kernel); their max-r2 + tables launch is ens_r2max_tables_kernel (nb_grid.hip) and the INT8 / INT4 force
 // snap ens_force_quant_finish_kernel (nb_misc.hip).
 //
+// Members of different sizes (nb_ens_create_ragged) have their own step kernel over a work list, nb_ens_ragged.hip; of the
+// kernels here they launch the kick + drift with `sizes` (its RAGGED instantiation, nb_device.h).
+//
 // Per-member stops (nb_ens_run_members): every kernel of the tick path takes `stop` and the launch's tick index t and comes
 // in two instantiations, with and without the array; nb_device.h states the rule and implements it (ens_ticks_left).
 #include "nb_dispatch.h"
@@ -19,15 +22,6 @@
 namespace {
 
 using namespace nbdev;
-
-// a stopped member's positions into the second buffer: this workgroup's own targets, nobody else writes or reads them there
-template <typename T, int D, int S, int BS>
-__device__ __forceinline__ void ens_carry_positions(const T *__restrict__ pos_in, T *__restrict__ pos_out, int n)
-{
-    constexpr int PER = BS / S * D;                  // elements of this workgroup's targets
-    const int k = blockIdx.x * PER + threadIdx.x;
-    if (threadIdx.x < PER && k < n * D) pos_out[k] = pos_in[k];
-}
 
 template <typename T, int D, int HOOK, int S, int BS, bool STOPS>
 __global__ void __launch_bounds__(BS)
@@ -40,7 +34,7 @@ ens_step_kernel(const T *__restrict__ pos_in, T *__restrict__ pos_out, T *__rest
     const size_t o = (size_t)b * n;
     const int left = ens_ticks_left<STOPS>(stop, b, t);
     if (STOPS && left <= 1) {
-        ens_carry_positions<T, D, S, BS>(pos_in + o * D, pos_out + o * D, n);
+        ens_carry_positions<T, D, S, BS>(blockIdx.x, pos_in + o * D, pos_out + o * D, n);
         if (left <= 0) return;
         do_kick = ens_kick_mode(left, do_kick);
     }
@@ -63,7 +57,7 @@ ens_step_mixed_kernel(const float *__restrict__ pos_in, float *__restrict__ pos_
     const size_t o = (size_t)b * n;
     const int left = ens_ticks_left<STOPS>(stop, b, t);
     if (STOPS && left <= 1) {
-        ens_carry_positions<float, D, S, BS>(pos_in + o * D, pos_out + o * D, n);
+        ens_carry_positions<float, D, S, BS>(blockIdx.x, pos_in + o * D, pos_out + o * D, n);
         if (left <= 0) return;
         do_kick = ens_kick_mode(left, do_kick);
     }
@@ -85,7 +79,7 @@ ens_grid_step_kernel(const float *__restrict__ pos_in, float *__restrict__ pos_o
     const size_t o = (size_t)b * n;
     const int left = ens_ticks_left<STOPS>(stop, b, t);
     if (STOPS && left <= 1) {
-        if (!part) ens_carry_positions<float, D, S, BS>(pos_in + o * D, pos_out + o * D, n);   // (INT8 / INT4: no ping-pong)
+        if (!part) ens_carry_positions<float, D, S, BS>(blockIdx.x, pos_in + o * D, pos_out + o * D, n);   // (INT8 / INT4: no ping-pong)
         if (left <= 0) return;
         do_kick = ens_kick_mode(left, do_kick);
     }
@@ -96,16 +90,19 @@ ens_grid_step_kernel(const float *__restrict__ pos_in, float *__restrict__ pos_o
 
 // opening kick + drift of a run (simulation.py:132,135) for every member with its own dt: v += a dt/2; x += v dt
 constexpr int EK_BLOCK = 256;
-template <typename T, bool STOPS>
+// RAGGED (sizes, dim: nb_device.h): count is the stride of a member's slice, of which it owns the first sizes[b] * dim
+template <typename T, bool STOPS, bool RAGGED>
 __global__ void __launch_bounds__(EK_BLOCK)
 ens_kick_drift_kernel(T *__restrict__ pos, T *__restrict__ vel, const T *__restrict__ acc, int count /* n * D */,
-                      const EnsScalars<T> *__restrict__ prm, const int *__restrict__ stop, int t)
+                      const EnsScalars<T> *__restrict__ prm, const int *__restrict__ stop, int t,
+                      const int *__restrict__ sizes, int dim)
 {
     const int b = blockIdx.y;
     if (ens_ticks_left<STOPS>(stop, b, t) <= 0) return;      // the member opens no further tick
     const T half_dt = prm[b].half_dt, dt = prm[b].dt;
     const size_t o = (size_t)b * count;
-    for (int k = blockIdx.x * EK_BLOCK + threadIdx.x; k < count; k += gridDim.x * EK_BLOCK) {
+    const int mine = ens_member_count<RAGGED>(sizes, b, dim, count);
+    for (int k = blockIdx.x * EK_BLOCK + threadIdx.x; k < mine; k += gridDim.x * EK_BLOCK) {
         const T v = axpy_rn<T>(vel[o + k], acc[o + k], half_dt);
         vel[o + k] = v;
         pos[o + k] = axpy_rn<T>(pos[o + k], v, dt);
@@ -190,7 +187,7 @@ hipError_t nb_launch_ens_grid_step(const float *pos_in, float *pos_out, float *v
 }
 
 hipError_t nb_launch_ens_kick_drift(void *pos, void *vel, const void *acc, int members, int n, int dim, int is_f64,
-                                    const void *prm, const int *stop, int t, hipStream_t st)
+                                    const void *prm, const int *stop, int t, hipStream_t st, const int *sizes)
 {
     if (members < 1 || members > NB_ENS_MAX_MEMBERS || n < 1 || (dim != 2 && dim != 3) || t < 0) return hipErrorInvalidValue;
     const int count = n * dim;
@@ -198,9 +195,11 @@ hipError_t nb_launch_ens_kick_drift(void *pos, void *vel, const void *acc, int m
     return nb::pick_real(is_f64, [&](auto real) {
         using T = typename decltype(real)::type;
         return nb::pick_bool(stop != nullptr, [&](auto ST) {
-            hipLaunchKernelGGL((ens_kick_drift_kernel<T, ST.value>), grid, dim3(EK_BLOCK), 0, st, (T *)pos, (T *)vel,
-                               (const T *)acc, count, (const EnsScalars<T> *)prm, stop, t);
-            return hipGetLastError();
+            return nb::pick_bool(sizes != nullptr, [&](auto RG) {
+                hipLaunchKernelGGL((ens_kick_drift_kernel<T, ST.value, RG.value>), grid, dim3(EK_BLOCK), 0, st, (T *)pos, (T *)vel,
+                                   (const T *)acc, count, (const EnsScalars<T> *)prm, stop, t, sizes, dim);
+                return hipGetLastError();
+            });
         });
     });
 }

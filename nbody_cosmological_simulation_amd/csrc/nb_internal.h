@@ -350,9 +350,24 @@ hipError_t nb_launch_ens_step(const void *pos_in, void *pos_out, void *vel, void
 hipError_t nb_launch_ens_step_mixed(const float *pos_in, float *pos_out, float *vel, float *acc, const float *mass, int members,
                                     int n, int dim, const void *prm, int do_kick, int lanes, const int *hooks, const int *stop,
                                     int t, hipStream_t st);
+// Members of different sizes (nb_ens_create_ragged; nb_ens_ragged.hip): n above is then the CAPACITY -- member b lives at
+// offset b * n and owns the first sizes[b] rows (sizes: device, `members` ints in [1, n]); no kernel touches the padding
+// rows behind them.  The step runs over a 1-D list of `items` work items (device; nb_plan_ragged, nb_plan.h), one workgroup
+// of NB_ENS_RAGGED_BLOCK threads each -- the one workgroup size of the launch: a target's sum does not depend on it
+// (nb_ens_ragged.hip).  hook: HOOK_NONE (fp64), HOOK_NONE / BF16 / F16 compiled in, or HOOK_AT_RUN_TIME with `hooks` as
+// nb_launch_ens_step_mixed takes them.  The launchers below that take `sizes` (null: every member has n rows, and the
+// instantiation without sizes is launched -- the code of before there were sizes) give every member its own count.
+struct EnsWork {
+    int member, blk;                // the member and which NB_ENS_RAGGED_BLOCK / lanes of its targets
+};
+constexpr int NB_ENS_RAGGED_BLOCK = 512;
+hipError_t nb_launch_ens_step_ragged(const void *pos_in, void *pos_out, void *vel, void *acc, const void *mass, int members,
+                                     int cap, int dim, int is_f64, int hook, const void *prm, int do_kick, int lanes,
+                                     const int *sizes, const EnsWork *work, int items, const int *hooks, const int *stop, int t,
+                                     hipStream_t st);
 // opening kick + drift of every member with its own dt (two roundings per line, like nb_launch_kick_drift)
 hipError_t nb_launch_ens_kick_drift(void *pos, void *vel, const void *acc, int members, int n, int dim, int is_f64,
-                                    const void *prm, const int *stop, int t, hipStream_t st);
+                                    const void *prm, const int *stop, int t, hipStream_t st, const int *sizes = nullptr);
 // The grid modes (INT8 / INT4 / CUSTOM, fp32 state), three launches per evaluation, each over all members:
 //   nb_launch_ens_r2max_tables        max r2 of every member and, by the member's last workgroup, its tables (tabs: `members`
 //                                     GridTables, zeroed once; levels: device, `members` ints in [2, NB_LUT_MIN];
@@ -394,7 +409,8 @@ hipError_t nb_launch_ens_force_quant_finish(float *acc, int members, int count, 
 // velocities (reason 1), |E - E0| / |E0| > 10 where |E0| > 1e-10 (2), E0 < 0 and E > |E0| (3), E0 = sample 0.  A member
 // that trips one gets stop[b] = t and reason[b] set: the launches behind this one leave it alone.
 hipError_t nb_launch_ens_watch(const void *pos, const void *vel, int members, int n, int dim, int is_f64, const double *kinetic,
-                               const double *potential, int64_t sample, int t, int *stop, int *reason, hipStream_t st);
+                               const double *potential, int64_t sample, int t, int *stop, int *reason, hipStream_t st,
+                               const int *sizes = nullptr);
 // ---- crash-point detector of an ensemble (nb_ens_crash.hip) -------------------------------------------------------------
 // ONE launch on `st`, one workgroup per member: flags[b] (bit 0: a NaN, bit 1: an Inf in positions or velocities) and
 // measures[4 b ..] = {max |pos - prev|, max |v_k|, max |vel|, max |pos|} in the state dtype, widened to double (device
@@ -412,7 +428,8 @@ hipError_t nb_launch_ens_crash(const void *pos, void *prev, const void *vel, int
 // differences in the state dtype, to max_pos / mean_pos / max_vel[sample * members + b].  The maxima are torch's max() (NaN
 // if any element is NaN, +inf an ordinary value); the mean is a fixed-order fp64 sum divided by n * dim.
 hipError_t nb_launch_ens_divergence(const void *pos, const void *vel, int members, int n, int dim, int is_f64, const int *baseline,
-                                    int64_t sample, double *max_pos, double *mean_pos, double *max_vel, hipStream_t st);
+                                    int64_t sample, double *max_pos, double *mean_pos, double *max_vel, hipStream_t st,
+                                    const int *sizes = nullptr /* the baseline's size is the member's: the host checks */);
 // ---- batched energies of an ensemble (nb_ens_energy.hip) -----------------------------------------------------------------
 // Two launches on `st`: per-tile-pair partial sums into part (members * nb_ens_energy_pairs(n) * 2 doubles, every slot
 // rewritten), then one wave per member that writes kinetic[sample * members + b] and potential[sample * members + b].
@@ -421,7 +438,7 @@ constexpr int NB_ENS_ENERGY_TILE = 256;
 int nb_ens_energy_pairs(int n);     // tile pairs of the upper triangle: 136 at n = 4096
 hipError_t nb_launch_ens_energy(const void *pos, const void *vel, const void *mass, int members, int n, int dim, int is_f64,
                                 const void *prm, double *part, double *kinetic, double *potential, int64_t sample,
-                                hipStream_t st);
+                                hipStream_t st, const int *sizes = nullptr);
 // ---- batched diagnostics of an ensemble (nb_ens_metrics.hip) -------------------------------------------------------------
 // ONE launch on `st`, one workgroup per member: the four diagnostics of nb_launch_metrics for every member, from the
 // ensemble's (members, n, dim) / (members, n) state of type A = storage = fp32 or fp64.  G comes from the member's scalars.

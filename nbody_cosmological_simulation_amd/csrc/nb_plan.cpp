@@ -46,6 +46,25 @@ NbKnobs nb_read_knobs()
     return k;
 }
 
+// Work list of the ragged ensemble step (nb_ens_ragged.hip): one item per workgroup, {member, target block}.  Members by
+// size descending, ties by index; blk ascending within a member.  Workgroups are dispatched in index order and a large
+// member's workgroup streams more sources, so the longest items start first and the tick ends with the short ones.
+int64_t nb_plan_ragged(const int32_t *sizes, int members, int lanes, std::vector<EnsWork> *work)
+{
+    const int targets = NB_ENS_RAGGED_BLOCK / lanes;          // per workgroup
+    std::vector<int> order(members);
+    for (int b = 0; b < members; ++b) order[b] = b;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return sizes[a] > sizes[b]; });
+    int64_t items = 0;
+    if (work) work->clear();
+    for (int b : order) {
+        const int blocks = (sizes[b] + targets - 1) / targets;
+        items += blocks;
+        for (int blk = 0; work && blk < blocks; ++blk) work->push_back(EnsWork{b, blk});
+    }
+    return items;
+}
+
 // Rows (target tiles) are grouped into super-rows of four (one per wave of a workgroup); super-rows are
 // dealt to the ranks in a snake pattern so every rank owns the same number of tile pairs to within one
 // super-row; each owned super-row is cut into work items of `cl` source tiles = one workgroup each.

@@ -60,5 +60,9 @@ struct PlanInput {
     int cus = 256;           // compute units of the device
 };
 
+// Work list of the ragged ensemble step: `members` checked sizes (each >= 1), lanes 16 / 32 / 64.  Returns the number of
+// items, sum over b of ceil(sizes[b] / (NB_ENS_RAGGED_BLOCK / lanes)); work may be null (the count alone).
+int64_t nb_plan_ragged(const int32_t *sizes, int members, int lanes, std::vector<EnsWork> *work);
+
 // Fills `out`; out.enabled == false means "use the one-sided kernels" (the decision is rank-independent).
 void nb_plan_sym(const PlanInput &in, const NbKnobs &knobs, SymPlanHost &out);

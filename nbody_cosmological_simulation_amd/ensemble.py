@@ -123,6 +123,20 @@ are formed in the state dtype, one subtraction each; `max_position` / `max_veloc
 n * D * 2^-53 relative of any other fp64 order).  `entropy_bits` and `divergence_rate` are the reference's derived
 quantities in numpy float64.
 
+Members of different sizes -- the reference's density sweeps (omega_point_test.py:595-766 scans 100 .. 2000 stars, two
+simulations per point with the divergence read back every tick; density_limit_test.py:206-246 runs 100 .. 4000) -- are
+`RaggedEnsemble`'s, for the cast modes: `positions` / `velocities` / `masses` are sequences of per-member (N_b, D) / (N_b,)
+tensors (`check_ragged_arguments`), `precision_mode` one mode or a list as above, and a tick is still ONE force launch
+("ens_step_ragged_kernel", csrc/nb_ens_ragged.hip: a 1-D grid over a work list of {member, target block}, largest members
+first).  Storage is padded to the largest member -- the constructor pads with NaN, and no kernel reads or writes a padding
+row.  Contract: member b is bit-identical to the `GalaxySimulation` of its own size and mode, no tolerance (a target's sum
+does not depend on the workgroup size, so the one size of the launch serves every N); `energies()`, the samples of
+`run_recorded` and the get_*_energy() lists of member b equal those of a one-member `GalaxyEnsemble` of the same system bit
+for bit; step, run, run_recorded, run_members, run_watched, divergence and run_diverged are inherited, the last two with
+baselines of the member's own size (ValueError otherwise).  `num_stars` is the list of sizes; the array attributes return
+lists of per-member tensors and `set_state` / `set_accelerations` take them.  `metrics`, `run_crash_watched` and
+`crash_measures` raise NotImplementedError: ragged metrics, the ragged crash watch and the ragged grid modes are follow-ups.
+
 Not covered: more than 4096 levels (a solo `GalaxySimulation` serves them through its generic kernel), INT8 / INT4 beside
 CUSTOM members, FLOAT64 or grid-mode members beside cast-mode members, stopping members on a divergence
 threshold, a crash check interval other than 1, crash thresholds
@@ -265,6 +279,72 @@ def _check_state(positions, velocities, masses, precision_mode, G, softening, dt
         raise ValueError(f"N must be in [1, {MAX_STARS[want]}] for {want} state, got {n}: above it a single system fills the "
                          "chip (use GalaxySimulation)")
     return (positions, velocities, masses, _param_list("G", G, B), _param_list("softening", softening, B),
+            _param_list("dt", dt, B))
+
+
+def check_ragged_arguments(positions, velocities, masses, precision_mode=PrecisionMode.FLOAT64, G=0.001, softening=0.1,
+                           dt=0.01):
+    """Validate RaggedEnsemble's constructor arguments without touching a device.  `positions` / `velocities`: sequences of
+    B tensors (N_b, D); `masses`: a sequence of B tensors (N_b,); `precision_mode`: one cast mode or a list of B modes as
+    GalaxyEnsemble takes it.  Returns (positions, velocities, masses, sizes, modes, G, softening, dt): the three as lists,
+    the B star counts, the checked mode list (None for one mode) and the parameters as length-B lists; raises TypeError /
+    ValueError naming the member."""
+    modes = None
+    if isinstance(precision_mode, (list, tuple)):
+        modes = check_mode_list(precision_mode)
+        storage = modes[0] if len(set(modes)) == 1 else PrecisionMode.FLOAT32
+    elif not isinstance(precision_mode, PrecisionMode):
+        raise TypeError(f"precision_mode must be a PrecisionMode or a list of them, got {type(precision_mode).__name__}")
+    elif precision_mode not in _MODES:
+        raise ValueError(f"RaggedEnsemble runs the FLOAT64, FLOAT32, BFLOAT16 and FLOAT16 modes; {precision_mode.name} needs "
+                         "per-member quantisation tables (the ragged grid modes are a follow-up; members of one size: "
+                         "QuantizedEnsemble)")
+    else:
+        storage = precision_mode
+    lists = []
+    for name, seq in (("positions", positions), ("velocities", velocities), ("masses", masses)):
+        if isinstance(seq, torch.Tensor) or isinstance(seq, (str, bytes)) or not isinstance(seq, Sequence):
+            raise TypeError(f"{name} must be a sequence of per-member tensors, got {type(seq).__name__} (members of one size: "
+                            "GalaxyEnsemble)")
+        lists.append(list(seq))
+    positions, velocities, masses = lists
+    B = len(positions)
+    if len(velocities) != B or len(masses) != B:
+        raise ValueError(f"positions has {B} members, velocities {len(velocities)} and masses {len(masses)}: the three lists "
+                         "must have one entry per member")
+    if not 1 <= B <= MAX_MEMBERS:
+        raise ValueError(f"B must be in [1, {MAX_MEMBERS}], got {B}")
+    if modes is not None:
+        check_mode_list(modes, B)
+    want = state_dtype(storage)
+    sizes, dim = [], None
+    for b in range(B):
+        for name, t in (("positions", positions[b]), ("velocities", velocities[b]), ("masses", masses[b])):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{name}[{b}] must be a torch.Tensor, got {type(t).__name__}")
+        if positions[b].dim() != 2 or masses[b].dim() != 1:
+            raise ValueError(f"member {b}: positions must be (N, D) with (N,) masses, got {tuple(positions[b].shape)} and "
+                             f"{tuple(masses[b].shape)}")
+        n, d = (int(v) for v in positions[b].shape)
+        if d not in (2, 3):
+            raise ValueError(f"member {b}: D must be 2 or 3, got {d}")
+        if dim is not None and d != dim:
+            raise ValueError(f"member {b} has D = {d} and member 0 has D = {dim}: the members of an ensemble share D")
+        dim = d
+        if n < 1:
+            raise ValueError(f"member {b} is empty: every member needs at least one star")
+        if tuple(velocities[b].shape) != (n, d) or tuple(masses[b].shape) != (n,):
+            raise ValueError(f"member {b}: positions {tuple(positions[b].shape)}, velocities {tuple(velocities[b].shape)} and "
+                             f"masses {tuple(masses[b].shape)} disagree on (N, D)")
+        for name, t in (("positions", positions[b]), ("velocities", velocities[b]), ("masses", masses[b])):
+            if t.dtype != want:
+                raise TypeError(f"{name}[{b}] must be {want} under {storage.name} (got {t.dtype}): an ensemble holds settled "
+                                "state only; mixed dtypes and the promotion timeline are GalaxySimulation's")
+        if n > MAX_STARS[want]:
+            raise ValueError(f"member {b} has N = {n}, above the limit of {MAX_STARS[want]} for {want} state: a single system "
+                             "of that size fills the chip (use GalaxySimulation)")
+        sizes.append(n)
+    return (positions, velocities, masses, sizes, modes, _param_list("G", G, B), _param_list("softening", softening, B),
             _param_list("dt", dt, B))
 
 
@@ -1099,3 +1179,106 @@ class FineGridEnsemble(QuantizedEnsemble):
         levels = (C.c_int32 * len(self.levels))(*self.levels)
         N.check(N.lib().nb_ens_create_grid_wide(C.byref(self._handle), C.byref(cfg), levels, _doubles(self.G),
                                                 _doubles([s ** 2 for s in self.softening]), _doubles(self.dt)))
+
+
+class RaggedEnsemble(GalaxyEnsemble):
+    """A GalaxyEnsemble whose members have their own star counts (see the module docstring): `positions` / `velocities` are
+    sequences of (N_b, D) tensors, `masses` of (N_b,) tensors; `num_stars` is the list of sizes; the array attributes and
+    set_state / set_accelerations speak lists of per-member tensors.  Everything else is GalaxyEnsemble's."""
+
+    def __init__(self, positions, velocities, masses, precision_mode=PrecisionMode.FLOAT64, G=0.001, softening=0.1, dt=0.01,
+                 device=None):
+        self._handle = C.c_void_p()
+        positions, velocities, masses, sizes, modes, self.G, self.softening, self.dt = check_ragged_arguments(
+            positions, velocities, masses, precision_mode, G, softening, dt)
+        self._sizes, self._capacity = list(sizes), max(sizes)
+        self.num_members, self._dim = len(sizes), int(positions[0].shape[1])
+        self._dtype = positions[0].dtype
+        padded = [self._padded(name, t) for name, t in (("positions", positions), ("velocities", velocities), ("masses", masses))]
+        self._construct(*padded, precision_mode, device, modes)       # (num_stars: the capacity, for the handle's shape)
+        self.num_stars = list(sizes)
+
+    def _create(self, cfg):
+        B = self.num_members
+        codes = (C.c_int32 * B)(*[mode_code(m) for m in self.precision_modes]) if self._mixed else None
+        N.check(N.lib().nb_ens_create_ragged(C.byref(self._handle), C.byref(cfg), (C.c_int32 * B)(*self._sizes), codes,
+                                             _doubles(self.G), _doubles([s ** 2 for s in self.softening]), _doubles(self.dt)))
+
+    def _shape(self, name):
+        return (self.num_members, self._capacity) if name == "masses" else (self.num_members, self._capacity, self._dim)
+
+    def _padded(self, name, members):
+        """A list of per-member tensors -> the whole (B, Nmax, ...) block the handle holds, the rows behind a member's own
+        filled with NaN: no kernel touches them, and one that did would poison a result.  A tensor of the block's shape
+        is taken as it is."""
+        if members is None or isinstance(members, torch.Tensor) and tuple(members.shape) == self._shape(name):
+            return members
+        if isinstance(members, torch.Tensor) or not isinstance(members, Sequence):
+            raise TypeError(f"{name} must be a sequence of {self.num_members} per-member tensors, or the whole padded "
+                            f"{self._shape(name)} block")
+        members = list(members)
+        if len(members) != self.num_members:
+            raise ValueError(f"{name} has {len(members)} entries for {self.num_members} members")
+        for b, t in enumerate(members):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{name}[{b}] must be a torch.Tensor, got {type(t).__name__}")
+            want = (self._sizes[b],) + self._shape(name)[2:]
+            if tuple(t.shape) != want:
+                raise ValueError(f"{name}[{b}] must have shape {want}, got {tuple(t.shape)}")
+            if t.dtype != self._dtype:
+                raise TypeError(f"{name}[{b}] must be {self._dtype}, got {t.dtype}")
+        out = torch.full(self._shape(name), float("nan"), dtype=self._dtype, device=members[0].device)
+        for b, t in enumerate(members):
+            out[b, :self._sizes[b]] = t.detach().to(out.device)
+        return out
+
+    def _members_of(self, name):
+        full = self._download(name)
+        return [full[b, :n].clone() for b, n in enumerate(self._sizes)]
+
+    positions = property(lambda s: s._members_of("positions"))
+    velocities = property(lambda s: s._members_of("velocities"))
+    masses = property(lambda s: s._members_of("masses"))
+    accelerations = property(lambda s: s._members_of("accelerations"))
+
+    def set_state(self, positions=None, velocities=None, masses=None):
+        """Replace the state: each argument None or a list of per-member (N_b, D) / (N_b,) tensors (re-padded with NaN); the
+        accelerations are NOT recomputed."""
+        super().set_state(self._padded("positions", positions), self._padded("velocities", velocities),
+                          self._padded("masses", masses))
+
+    def set_accelerations(self, accelerations):
+        """Replace the stored accelerations: a list of per-member (N_b, D) tensors."""
+        super().set_accelerations(self._padded("accelerations", accelerations))
+
+    def _same_size_baselines(self, baseline):
+        baselines, _ = check_divergence_arguments(0, 1, baseline, self.num_members)
+        for b, base in enumerate(baselines):
+            if self._sizes[base] != self._sizes[b]:
+                raise ValueError(f"baseline of member {b} is member {base}: {self._sizes[b]} stars against {self._sizes[base]}; "
+                                 "a member is compared with a member of its own size")
+
+    def divergence(self, baseline=0) -> Divergence:
+        self._same_size_baselines(baseline)
+        return super().divergence(baseline)
+
+    def run_diverged(self, num_ticks: int, every: int = 1, baseline=0, energies: bool = True) -> DivergenceHistory:
+        self._same_size_baselines(baseline)
+        return super().run_diverged(num_ticks, every, baseline, energies)
+
+    divergence.__doc__ = GalaxyEnsemble.divergence.__doc__
+    run_diverged.__doc__ = GalaxyEnsemble.run_diverged.__doc__
+
+    def metrics(self, *args, **kwargs):
+        """Not implemented for members of different sizes: its kernel is one workgroup per member of one shape."""
+        raise NotImplementedError("RaggedEnsemble.metrics: ragged metrics are a follow-up (members of one size: GalaxyEnsemble)")
+
+    def run_crash_watched(self, *args, **kwargs):
+        """Not implemented for members of different sizes."""
+        raise NotImplementedError("RaggedEnsemble.run_crash_watched: the ragged crash watch is a follow-up (members of one "
+                                  "size: GalaxyEnsemble)")
+
+    def crash_measures(self, *args, **kwargs):
+        """Not implemented for members of different sizes."""
+        raise NotImplementedError("RaggedEnsemble.crash_measures: the ragged crash watch is a follow-up (members of one size: "
+                                  "GalaxyEnsemble)")
