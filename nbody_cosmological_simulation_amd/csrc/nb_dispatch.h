@@ -45,4 +45,18 @@ hipError_t pick_real(bool is_f64, F &&f)
     return is_f64 ? f(real_tag<double>{}) : f(real_tag<float>{});
 }
 
+// The ladder under `dim` of the launchers that run the one-launch step's bodies (the nb_ens step kernels): f(S, BS, STOPS)
+// for 64 / 32 / 16 lanes per target, a workgroup of one of BLOCKS threads, and a kernel with or without a stop array (or
+// whatever else the launcher's last bool chooses).  dim stays the launcher's own outermost pick<2, 3>: the typed launchers
+// choose the storage type and the hook between the two, and the kernels leave the compiler in the order of the nesting.
+template <auto... BLOCKS, typename F>
+hipError_t pick_small_step(int lanes, int block, bool stops, F &&f)
+{
+    return pick<64, 32, 16>(lanes, [&](auto S) {
+        return pick<BLOCKS...>(block, [&](auto BS) {
+            return pick_bool(stops, [&](auto ST) { return f(S, BS, ST); });
+        });
+    });
+}
+
 }  // namespace nb

@@ -57,26 +57,18 @@ ens_grid_bins_kernel(const float *__restrict__ pos_in, float *__restrict__ acc, 
 
 }  // namespace
 
-hipError_t nb_launch_ens_grid_step_wide(const float *pos_in, float *pos_out, float *vel, float *acc, const float *mass,
-                                        int members, int n, int dim, const void *prm, int do_kick, int lanes,
-                                        const GridTables *tabs, int max_levels, const int *stop, int t, hipStream_t st)
+hipError_t nb_launch_ens_grid_step_wide(const EnsStepArgs &a, int do_kick, const int *stop, int t, hipStream_t st)
 {
-    if (members < 1 || members > NB_ENS_MAX_MEMBERS || n < 1 || !tabs || t < 0) return hipErrorInvalidValue;
-    if (max_levels < 2 || max_levels > NB_MAX_LUT) return hipErrorInvalidValue;
-    const int km = do_kick & NB_KICK_MODE_MASK;
-    if (km == NB_KICK_CLOSE_SPEC || (do_kick & NB_KICK_OPEN_ON_READ)) return hipErrorInvalidValue;
-    const int cap = nb_lut_pad(max_levels);
-    return nb::pick<2, 3>(dim, [&](auto D) {
-        return nb::pick<64, 32, 16>(lanes, [&](auto S) {
-            return nb::pick<512, 256>(nb_small_block(n), [&](auto BS) {
-                return nb::pick_bool(stop != nullptr, [&](auto ST) {
-                    hipLaunchKernelGGL((ens_grid_step_wide_kernel<D.value, S.value, BS.value, ST.value>),
-                                       dim3(nb_small_blocks(n, lanes), members), dim3(BS.value), nb_lut_lds_bytes(max_levels), st,
-                                       pos_in, pos_out, vel, acc, mass, n, (const EnsScalars<float> *)prm, do_kick, tabs, cap,
-                                       stop, t);
-                    return hipGetLastError();
-                });
-            });
+    if (hipError_t err = nb_ens_step_check(a, do_kick, t)) return err;
+    if (a.is_f64 || !a.tabs || a.max_levels < 2 || a.max_levels > NB_MAX_LUT) return hipErrorInvalidValue;
+    const int cap = nb_lut_pad(a.max_levels);
+    return nb::pick<2, 3>(a.dim, [&](auto D) {
+        return nb::pick_small_step<512, 256>(a.lanes, nb_small_block(a.n), stop != nullptr, [&](auto S, auto BS, auto ST) {
+            hipLaunchKernelGGL((ens_grid_step_wide_kernel<D.value, S.value, BS.value, ST.value>),
+                               dim3(nb_small_blocks(a.n, a.lanes), a.members), dim3(BS.value), nb_lut_lds_bytes(a.max_levels), st,
+                               (const float *)a.pos_in, (float *)a.pos_out, (float *)a.vel, (float *)a.acc, (const float *)a.mass,
+                               a.n, (const EnsScalars<float> *)a.prm, do_kick, a.tabs, cap, stop, t);
+            return hipGetLastError();
         });
     });
 }
@@ -89,16 +81,11 @@ hipError_t nb_launch_ens_grid_bins(const float *pos, float *acc, const float *ma
     const bool wide = max_levels > NB_LUT_MIN;
     const int cap = nb_lut_pad(max_levels);
     return nb::pick<2, 3>(dim, [&](auto D) {
-        return nb::pick<64, 32, 16>(lanes, [&](auto S) {
-            return nb::pick<512, 256>(nb_small_block(n), [&](auto BS) {
-                return nb::pick_bool(wide, [&](auto W) {
-                    hipLaunchKernelGGL((ens_grid_bins_kernel<D.value, S.value, BS.value, W.value>),
-                                       dim3(nb_small_blocks(n, lanes), members), dim3(BS.value),
-                                       wide ? nb_lut_lds_bytes(max_levels) : 0, st, pos, acc, mass, n,
-                                       (const EnsScalars<float> *)prm, tabs, cap, bin_out);
-                    return hipGetLastError();
-                });
-            });
+        return nb::pick_small_step<512, 256>(lanes, nb_small_block(n), wide, [&](auto S, auto BS, auto W) {
+            hipLaunchKernelGGL((ens_grid_bins_kernel<D.value, S.value, BS.value, W.value>),
+                               dim3(nb_small_blocks(n, lanes), members), dim3(BS.value), wide ? nb_lut_lds_bytes(max_levels) : 0,
+                               st, pos, acc, mass, n, (const EnsScalars<float> *)prm, tabs, cap, bin_out);
+            return hipGetLastError();
         });
     });
 }

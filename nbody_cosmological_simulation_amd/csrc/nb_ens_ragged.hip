@@ -55,40 +55,27 @@ ens_step_ragged_kernel(const T *__restrict__ pos_in, T *__restrict__ pos_out, T 
                                              p.G, p.eps2, p.half_dt, p.dt, do_kick, nullptr, hook_rt);
 }
 
-template <typename T, int D, int HOOK>
-hipError_t launch_r(const void *pos_in, void *pos_out, void *vel, void *acc, const void *mass, int cap, const int *sizes,
-                    const EnsWork *work, int items, const void *prm, int do_kick, int lanes, const int *hooks, const int *stop,
-                    int t, hipStream_t st)
-{
-    return nb::pick<64, 32, 16>(lanes, [&](auto S) {
-        return nb::pick_bool(stop != nullptr, [&](auto ST) {
-            hipLaunchKernelGGL((ens_step_ragged_kernel<T, D, HOOK, S.value, ST.value>), dim3(items), dim3(ER_BLOCK), 0, st,
-                               (const T *)pos_in, (T *)pos_out, (T *)vel, (T *)acc, (const T *)mass, cap, sizes, work,
-                               (const EnsScalars<T> *)prm, do_kick, hooks, stop, t);
-            return hipGetLastError();
-        });
-    });
-}
-
 }  // namespace
 
-hipError_t nb_launch_ens_step_ragged(const void *pos_in, void *pos_out, void *vel, void *acc, const void *mass, int members,
-                                     int cap, int dim, int is_f64, int hook, const void *prm, int do_kick, int lanes,
-                                     const int *sizes, const EnsWork *work, int items, const int *hooks, const int *stop, int t,
-                                     hipStream_t st)
+hipError_t nb_launch_ens_step_ragged(const EnsStepArgs &a, int do_kick, const int *stop, int t, hipStream_t st)
 {
-    if (members < 1 || members > NB_ENS_MAX_MEMBERS || cap < 1 || !sizes || !work || items < 1 || t < 0) return hipErrorInvalidValue;
-    if ((do_kick & NB_KICK_MODE_MASK) == NB_KICK_CLOSE_SPEC || (do_kick & NB_KICK_OPEN_ON_READ)) return hipErrorInvalidValue;
-    if (hook == HOOK_AT_RUN_TIME && (is_f64 || !hooks)) return hipErrorInvalidValue;
-    return nb::pick<2, 3>(dim, [&](auto D) {
-        if (is_f64)
-            return nb::pick<HOOK_NONE>(hook, [&](auto H) {
-                return launch_r<double, D.value, H.value>(pos_in, pos_out, vel, acc, mass, cap, sizes, work, items, prm, do_kick,
-                                                          lanes, hooks, stop, t, st);
+    if (hipError_t err = nb_ens_step_check(a, do_kick, t)) return err;       // (a.n: the capacity)
+    if (!a.sizes || !a.work || a.items < 1) return hipErrorInvalidValue;
+    if (a.hook == HOOK_AT_RUN_TIME && (a.is_f64 || !a.hooks)) return hipErrorInvalidValue;
+    return nb::pick<2, 3>(a.dim, [&](auto D) {
+        auto launch = [&](auto real, auto H) {
+            using T = typename decltype(real)::type;
+            // ONE workgroup size: the ladder's block is not a choice here
+            return nb::pick_small_step<ER_BLOCK>(a.lanes, ER_BLOCK, stop != nullptr, [&](auto S, auto, auto ST) {
+                hipLaunchKernelGGL((ens_step_ragged_kernel<T, D.value, H.value, S.value, ST.value>), dim3(a.items), dim3(ER_BLOCK),
+                                   0, st, (const T *)a.pos_in, (T *)a.pos_out, (T *)a.vel, (T *)a.acc, (const T *)a.mass, a.n,
+                                   a.sizes, a.work, (const EnsScalars<T> *)a.prm, do_kick, a.hooks, stop, t);
+                return hipGetLastError();
             });
-        return nb::pick<HOOK_NONE, HOOK_BF16, HOOK_F16, HOOK_AT_RUN_TIME>(hook, [&](auto H) {
-            return launch_r<float, D.value, H.value>(pos_in, pos_out, vel, acc, mass, cap, sizes, work, items, prm, do_kick, lanes,
-                                                     hooks, stop, t, st);
+        };
+        if (a.is_f64) return nb::pick<HOOK_NONE>(a.hook, [&](auto H) { return launch(nb::real_tag<double>{}, H); });
+        return nb::pick<HOOK_NONE, HOOK_BF16, HOOK_F16, HOOK_AT_RUN_TIME>(a.hook, [&](auto H) {
+            return launch(nb::real_tag<float>{}, H);
         });
     });
 }

@@ -109,79 +109,62 @@ ens_kick_drift_kernel(T *__restrict__ pos, T *__restrict__ vel, const T *__restr
     }
 }
 
-template <typename T, int D, int HOOK>
-hipError_t launch_e(const void *pos_in, void *pos_out, void *vel, void *acc, const void *mass, int members, int n, const void *prm,
-                    int do_kick, int lanes, const int *stop, int t, hipStream_t st)
-{
-    return nb::pick<64, 32, 16>(lanes, [&](auto S) {
-        return nb::pick<512, 256>(nb_small_block(n), [&](auto BS) {
-            return nb::pick_bool(stop != nullptr, [&](auto ST) {
-                hipLaunchKernelGGL((ens_step_kernel<T, D, HOOK, S.value, BS.value, ST.value>),
-                                   dim3(nb_small_blocks(n, lanes), members), dim3(BS.value), 0, st, (const T *)pos_in, (T *)pos_out,
-                                   (T *)vel, (T *)acc, (const T *)mass, n, (const EnsScalars<T> *)prm, do_kick, stop, t);
-                return hipGetLastError();
-            });
-        });
-    });
-}
-
 }  // namespace
 
-hipError_t nb_launch_ens_step(const void *pos_in, void *pos_out, void *vel, void *acc, const void *mass, int members, int n,
-                              int dim, int is_f64, int hook, const void *prm, int do_kick, int lanes, const int *stop, int t,
-                              hipStream_t st)
+hipError_t nb_ens_step_check(const EnsStepArgs &a, int do_kick, int t)
 {
-    if (members < 1 || members > NB_ENS_MAX_MEMBERS || n < 1 || t < 0) return hipErrorInvalidValue;
-    if ((do_kick & NB_KICK_MODE_MASK) == NB_KICK_CLOSE_SPEC || (do_kick & NB_KICK_OPEN_ON_READ)) return hipErrorInvalidValue;
-    return nb::pick<2, 3>(dim, [&](auto D) {
-        if (is_f64)
-            return nb::pick<HOOK_NONE>(hook, [&](auto H) {
-                return launch_e<double, D.value, H.value>(pos_in, pos_out, vel, acc, mass, members, n, prm, do_kick, lanes, stop, t, st);
-            });
-        return nb::pick<HOOK_NONE, HOOK_BF16, HOOK_F16>(hook, [&](auto H) {
-            return launch_e<float, D.value, H.value>(pos_in, pos_out, vel, acc, mass, members, n, prm, do_kick, lanes, stop, t, st);
-        });
-    });
-}
-
-hipError_t nb_launch_ens_step_mixed(const float *pos_in, float *pos_out, float *vel, float *acc, const float *mass, int members,
-                                    int n, int dim, const void *prm, int do_kick, int lanes, const int *hooks, const int *stop,
-                                    int t, hipStream_t st)
-{
-    if (members < 1 || members > NB_ENS_MAX_MEMBERS || n < 1 || !hooks || t < 0) return hipErrorInvalidValue;
-    if ((do_kick & NB_KICK_MODE_MASK) == NB_KICK_CLOSE_SPEC || (do_kick & NB_KICK_OPEN_ON_READ)) return hipErrorInvalidValue;
-    return nb::pick<2, 3>(dim, [&](auto D) {
-        return nb::pick<64, 32, 16>(lanes, [&](auto S) {
-            return nb::pick<512, 256>(nb_small_block(n), [&](auto BS) {
-                return nb::pick_bool(stop != nullptr, [&](auto ST) {
-                    hipLaunchKernelGGL((ens_step_mixed_kernel<D.value, S.value, BS.value, ST.value>),
-                                       dim3(nb_small_blocks(n, lanes), members), dim3(BS.value), 0, st, pos_in, pos_out, vel, acc,
-                                       mass, n, (const EnsScalars<float> *)prm, do_kick, hooks, stop, t);
-                    return hipGetLastError();
-                });
-            });
-        });
-    });
-}
-
-hipError_t nb_launch_ens_grid_step(const float *pos_in, float *pos_out, float *vel, float *acc, const float *mass, int members,
-                                   int n, int dim, const void *prm, int do_kick, int lanes, const GridTables *tabs, double *part,
-                                   const int *stop, int t, hipStream_t st)
-{
-    if (members < 1 || members > NB_ENS_MAX_MEMBERS || n < 1 || !tabs || t < 0) return hipErrorInvalidValue;
+    if (a.members < 1 || a.members > NB_ENS_MAX_MEMBERS || a.n < 1 || t < 0) return hipErrorInvalidValue;
     const int km = do_kick & NB_KICK_MODE_MASK;
     if (km == NB_KICK_CLOSE_SPEC || (do_kick & NB_KICK_OPEN_ON_READ)) return hipErrorInvalidValue;
-    if (part && km != NB_KICK_NONE) return hipErrorInvalidValue;      // INT8 / INT4: the finish launch carries the kicks
-    return nb::pick<2, 3>(dim, [&](auto D) {
-        return nb::pick<64, 32, 16>(lanes, [&](auto S) {
-            return nb::pick<512, 256>(nb_small_block(n), [&](auto BS) {
-                return nb::pick_bool(stop != nullptr, [&](auto ST) {
-                    hipLaunchKernelGGL((ens_grid_step_kernel<D.value, S.value, BS.value, ST.value>),
-                                       dim3(nb_small_blocks(n, lanes), members), dim3(BS.value), 0, st, pos_in, pos_out, vel, acc,
-                                       mass, n, (const EnsScalars<float> *)prm, do_kick, tabs, part, stop, t);
-                    return hipGetLastError();
-                });
+    if (a.part && km != NB_KICK_NONE) return hipErrorInvalidValue;      // INT8 / INT4: the finish launch carries the kicks
+    return hipSuccess;
+}
+
+hipError_t nb_launch_ens_step(const EnsStepArgs &a, int do_kick, const int *stop, int t, hipStream_t st)
+{
+    if (hipError_t err = nb_ens_step_check(a, do_kick, t)) return err;
+    return nb::pick<2, 3>(a.dim, [&](auto D) {
+        auto launch = [&](auto real, auto H) {
+            using T = typename decltype(real)::type;
+            return nb::pick_small_step<512, 256>(a.lanes, nb_small_block(a.n), stop != nullptr, [&](auto S, auto BS, auto ST) {
+                hipLaunchKernelGGL((ens_step_kernel<T, D.value, H.value, S.value, BS.value, ST.value>),
+                                   dim3(nb_small_blocks(a.n, a.lanes), a.members), dim3(BS.value), 0, st, (const T *)a.pos_in,
+                                   (T *)a.pos_out, (T *)a.vel, (T *)a.acc, (const T *)a.mass, a.n, (const EnsScalars<T> *)a.prm,
+                                   do_kick, stop, t);
+                return hipGetLastError();
             });
+        };
+        if (a.is_f64) return nb::pick<HOOK_NONE>(a.hook, [&](auto H) { return launch(nb::real_tag<double>{}, H); });
+        return nb::pick<HOOK_NONE, HOOK_BF16, HOOK_F16>(a.hook, [&](auto H) { return launch(nb::real_tag<float>{}, H); });
+    });
+}
+
+hipError_t nb_launch_ens_step_mixed(const EnsStepArgs &a, int do_kick, const int *stop, int t, hipStream_t st)
+{
+    if (hipError_t err = nb_ens_step_check(a, do_kick, t)) return err;
+    if (a.is_f64 || !a.hooks) return hipErrorInvalidValue;
+    return nb::pick<2, 3>(a.dim, [&](auto D) {
+        return nb::pick_small_step<512, 256>(a.lanes, nb_small_block(a.n), stop != nullptr, [&](auto S, auto BS, auto ST) {
+            hipLaunchKernelGGL((ens_step_mixed_kernel<D.value, S.value, BS.value, ST.value>),
+                               dim3(nb_small_blocks(a.n, a.lanes), a.members), dim3(BS.value), 0, st, (const float *)a.pos_in,
+                               (float *)a.pos_out, (float *)a.vel, (float *)a.acc, (const float *)a.mass, a.n,
+                               (const EnsScalars<float> *)a.prm, do_kick, a.hooks, stop, t);
+            return hipGetLastError();
+        });
+    });
+}
+
+hipError_t nb_launch_ens_grid_step(const EnsStepArgs &a, int do_kick, const int *stop, int t, hipStream_t st)
+{
+    if (hipError_t err = nb_ens_step_check(a, do_kick, t)) return err;
+    if (a.is_f64 || !a.tabs) return hipErrorInvalidValue;
+    return nb::pick<2, 3>(a.dim, [&](auto D) {
+        return nb::pick_small_step<512, 256>(a.lanes, nb_small_block(a.n), stop != nullptr, [&](auto S, auto BS, auto ST) {
+            hipLaunchKernelGGL((ens_grid_step_kernel<D.value, S.value, BS.value, ST.value>),
+                               dim3(nb_small_blocks(a.n, a.lanes), a.members), dim3(BS.value), 0, st, (const float *)a.pos_in,
+                               (float *)a.pos_out, (float *)a.vel, (float *)a.acc, (const float *)a.mass, a.n,
+                               (const EnsScalars<float> *)a.prm, do_kick, a.tabs, a.part, stop, t);
+            return hipGetLastError();
         });
     });
 }

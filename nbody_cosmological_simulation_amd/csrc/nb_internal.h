@@ -343,13 +343,31 @@ struct EnsScalars {                 // the scalars of one member: the ONE declar
 static_assert(sizeof(EnsScalars<double>) == 4 * sizeof(double) && sizeof(EnsScalars<float>) == 4 * sizeof(float),
               "the device array is dense: one record per member, no padding");
 constexpr int NB_ENS_MAX_MEMBERS = 1024;
-hipError_t nb_launch_ens_step(const void *pos_in, void *pos_out, void *vel, void *acc, const void *mass, int members, int n,
-                              int dim, int is_f64, int hook, const void *prm, int do_kick, int lanes, const int *stop, int t,
-                              hipStream_t st);
-// members of different cast modes (fp32 state): hooks is device, one of HOOK_NONE / HOOK_BF16 / HOOK_F16 per member
-hipError_t nb_launch_ens_step_mixed(const float *pos_in, float *pos_out, float *vel, float *acc, const float *mass, int members,
-                                    int n, int dim, const void *prm, int do_kick, int lanes, const int *hooks, const int *stop,
-                                    int t, hipStream_t st);
+// What a step launch of an ensemble reads, whichever of the five step kernels runs: the handle (nb_ens_api.cpp) fills ONE
+// record at creation and every launcher below takes it; per launch only do_kick, stop, t and the stream are passed.
+struct EnsWork;
+struct EnsStepArgs {
+    void *pos_in, *pos_out;         // device, (members, n, dim) of the storage type; a launch reads pos_in, and a
+                                    // NB_KICK_CLOSE_OPEN one leaves the drifted positions in pos_out (the caller swaps the two)
+    void *vel, *acc;                // device, (members, n, dim)
+    const void *mass;               // device, (members, n)
+    int members, n, dim, is_f64;    // n: the capacity under `sizes`
+    int hook;                       // compiled in (HOOK_NONE / HOOK_BF16 / HOOK_F16), HOOK_AT_RUN_TIME with `hooks`, HOOK_GRID
+    int lanes;                      // 16 / 32 / 64 lanes per target
+    const void *prm;                // device, one EnsScalars of the storage type per member
+    const int *hooks;               // members of different cast modes: device, one hook per member; else null
+    const int *sizes;               // members of different sizes: device, `members` ints in [1, n]; else null, and
+    const EnsWork *work;            // ... the work list of the ragged step, `items` entries
+    int items;
+    const GridTables *tabs;         // grid modes: device, one per member; else null
+    double *part;                   // INT8 / INT4: members * nb_small_blocks * 2 doubles of {min, max}; else null
+    int max_levels;                 // grid modes: the largest level count of the members
+};
+// what every step launcher asks first: members, n, t, and the kick modes an ensemble launch cannot carry
+hipError_t nb_ens_step_check(const EnsStepArgs &a, int do_kick, int t);
+hipError_t nb_launch_ens_step(const EnsStepArgs &a, int do_kick, const int *stop, int t, hipStream_t st);
+// members of different cast modes (fp32 state): a.hooks holds one of HOOK_NONE / HOOK_BF16 / HOOK_F16 per member
+hipError_t nb_launch_ens_step_mixed(const EnsStepArgs &a, int do_kick, const int *stop, int t, hipStream_t st);
 // Members of different sizes (nb_ens_create_ragged; nb_ens_ragged.hip): n above is then the CAPACITY -- member b lives at
 // offset b * n and owns the first sizes[b] rows (sizes: device, `members` ints in [1, n]); no kernel touches the padding
 // rows behind them.  The step runs over a 1-D list of `items` work items (device; nb_plan_ragged, nb_plan.h), one workgroup
@@ -361,10 +379,7 @@ struct EnsWork {
     int member, blk;                // the member and which NB_ENS_RAGGED_BLOCK / lanes of its targets
 };
 constexpr int NB_ENS_RAGGED_BLOCK = 512;
-hipError_t nb_launch_ens_step_ragged(const void *pos_in, void *pos_out, void *vel, void *acc, const void *mass, int members,
-                                     int cap, int dim, int is_f64, int hook, const void *prm, int do_kick, int lanes,
-                                     const int *sizes, const EnsWork *work, int items, const int *hooks, const int *stop, int t,
-                                     hipStream_t st);
+hipError_t nb_launch_ens_step_ragged(const EnsStepArgs &a, int do_kick, const int *stop, int t, hipStream_t st);
 // opening kick + drift of every member with its own dt (two roundings per line, like nb_launch_kick_drift)
 hipError_t nb_launch_ens_kick_drift(void *pos, void *vel, const void *acc, int members, int n, int dim, int is_f64,
                                     const void *prm, const int *stop, int t, hipStream_t st, const int *sizes = nullptr);
@@ -380,9 +395,7 @@ hipError_t nb_launch_ens_kick_drift(void *pos, void *vel, const void *acc, int m
 //                                     ONE value for all members (256 or 16: the force grid is the mode's, not CUSTOM's)
 hipError_t nb_launch_ens_r2max_tables(const float *pos, int members, int n, int dim, const void *prm, GridTables *tabs,
                                       const int *levels, float min_val, int allow_fast, const int *stop, int t, hipStream_t st);
-hipError_t nb_launch_ens_grid_step(const float *pos_in, float *pos_out, float *vel, float *acc, const float *mass, int members,
-                                   int n, int dim, const void *prm, int do_kick, int lanes, const GridTables *tabs, double *part,
-                                   const int *stop, int t, hipStream_t st);
+hipError_t nb_launch_ens_grid_step(const EnsStepArgs &a, int do_kick, const int *stop, int t, hipStream_t st);
 // CUSTOM members of up to NB_MAX_LUT levels (nb_ens_create_grid_wide), when a member exceeds NB_LUT_MIN:
 //   nb_launch_ens_r2max_tables        as above (levels in [2, NB_MAX_LUT]): a member above NB_LUT_MIN levels only gets its maximum
 //   nb_launch_ens_tables_wide         ... and its tables here, built as grid_tables_kernel builds a solo run's: one workgroup per
@@ -394,9 +407,7 @@ hipError_t nb_launch_ens_grid_step(const float *pos_in, float *pos_out, float *v
 //                                     caller, per member {s1[n], s2[n], {table-free pairs, table pairs}}
 hipError_t nb_launch_ens_tables_wide(int members, int max_levels, const void *prm, GridTables *tabs, const int *levels,
                                      float min_val, int allow_fast, const int *stop, int t, hipStream_t st);
-hipError_t nb_launch_ens_grid_step_wide(const float *pos_in, float *pos_out, float *vel, float *acc, const float *mass,
-                                        int members, int n, int dim, const void *prm, int do_kick, int lanes,
-                                        const GridTables *tabs, int max_levels, const int *stop, int t, hipStream_t st);
+hipError_t nb_launch_ens_grid_step_wide(const EnsStepArgs &a, int do_kick, const int *stop, int t, hipStream_t st);
 hipError_t nb_launch_ens_grid_bins(const float *pos, float *acc, const float *mass, int members, int n, int dim, const void *prm,
                                    int lanes, const GridTables *tabs, int max_levels, unsigned long long *bin_out, hipStream_t st);
 hipError_t nb_launch_ens_force_quant_finish(float *acc, int members, int count, int levels, const double *partials, int nblocks,

@@ -179,19 +179,26 @@ def state_dtype(precision_mode) -> torch.dtype:
     return torch.float64 if precision_mode == PrecisionMode.FLOAT64 else torch.float32
 
 
+def _typed(name, v, kind=numbers.Integral, what="an int"):
+    """`v` if it is a `kind` (numbers.Integral or numbers.Real) and no bool, else TypeError "`name` must be `what`, got
+    <type>"."""
+    if isinstance(v, bool) or not isinstance(v, kind):
+        raise TypeError(f"{name} must be {what}, got {type(v).__name__}")
+    return v
+
+
 def _scalar_or_list(value, noun, kind, what, check=None, loose=False):
     """An argument that is one value for all members or one per member -> a Python scalar or a list.  Tensors and numpy
     arrays / scalars go through tolist(), lists, tuples and other Sequences (range and the like) become lists.  Every
-    entry must be a `kind` (numbers.Integral or numbers.Real) and no bool, else TypeError "`noun` must be `what`, got
-    <type>"; `check(entry)` follows each entry's type test.  loose (the constructors' G / softening / dt, as they have
-    always been read): only tensors, lists and tuples count as sequences and float() alone judges their entries."""
+    entry must pass `_typed(noun, entry, kind, what)`; `check(entry)` follows each entry's type test.  loose (the
+    constructors' G / softening / dt, as they have always been read): only tensors, lists and tuples count as sequences and
+    float() alone judges their entries."""
     if isinstance(value, torch.Tensor) or not loose and type(value).__module__ == "numpy" and hasattr(value, "tolist"):
         value = value.tolist()
     elif isinstance(value, (list, tuple)) or not loose and isinstance(value, Sequence) and not isinstance(value, (str, bytes)):
         value = list(value)
     for v in (value if not loose else []) if isinstance(value, list) else [value]:
-        if isinstance(v, bool) or not isinstance(v, kind):
-            raise TypeError(f"{noun} must be {what}, got {type(v).__name__}")
+        _typed(noun, v, kind, what)
         if check is not None:
             check(v)
     return value
@@ -246,11 +253,36 @@ def check_mode_list(modes, members=None) -> list:
     return modes
 
 
+def _mode_or_list(precision_mode):
+    """One precision mode or a list of them, as the cast-mode constructors take it -> (modes, storage): the checked list
+    (`check_mode_list`; its length is the caller's to check) and the mode the state is stored and checked under -- the
+    list's one mode, else FLOAT32 -- or (None, precision_mode) for anything that is no list: the caller judges it."""
+    if not isinstance(precision_mode, (list, tuple)):
+        return None, precision_mode
+    modes = check_mode_list(precision_mode)
+    return modes, modes[0] if len(set(modes)) == 1 else PrecisionMode.FLOAT32
+
+
+def _check_tensor(name, t, member=None, shape=None, dtype=None, mode=None):
+    """The per-tensor tests of every state check, in this order: `t` is a tensor, has `shape` (None: not tested) and
+    `dtype` (None: not tested; mode: the settled dtype of that precision mode, and the refusal says so).  member: `t` is
+    entry `member` of the list `name`, and the refusals name it."""
+    label = name if member is None else f"{name}[{member}]"
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{label} must be a torch.Tensor" + ("" if member is None else f", got {type(t).__name__}"))
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{label} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    if dtype is not None and t.dtype != dtype:
+        if mode is None:
+            raise TypeError(f"{label} must be {dtype}, got {t.dtype}")
+        raise TypeError(f"{label} must be {dtype} under {mode.name} (got {t.dtype}): an ensemble holds settled state only; "
+                        "mixed dtypes and the promotion timeline are GalaxySimulation's")
+
+
 def _check_state(positions, velocities, masses, precision_mode, G, softening, dt, more_lists=()):
     """check_arguments behind the mode check; more_lists: lengths of further per-member lists a lone galaxy is broadcast over."""
     for name, t in (("positions", positions), ("velocities", velocities), ("masses", masses)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} must be a torch.Tensor")
+        _check_tensor(name, t)
     if positions.dim() == 2 and masses.dim() == 1:
         # one galaxy under a parameter sweep: as many members as the longest parameter list
         lens = [len(p) for p in (_param_list("G", G, None), _param_list("softening", softening, None),
@@ -272,9 +304,7 @@ def _check_state(positions, velocities, masses, precision_mode, G, softening, dt
         raise ValueError(f"B must be in [1, {MAX_MEMBERS}], got {B}")
     want = state_dtype(precision_mode)
     for name, t in (("positions", positions), ("velocities", velocities), ("masses", masses)):
-        if t.dtype != want:
-            raise TypeError(f"{name} must be {want} under {precision_mode.name} (got {t.dtype}): an ensemble holds settled "
-                            "state only; mixed dtypes and the promotion timeline are GalaxySimulation's")
+        _check_tensor(name, t, dtype=want, mode=precision_mode)
     if not 1 <= n <= MAX_STARS[want]:
         raise ValueError(f"N must be in [1, {MAX_STARS[want]}] for {want} state, got {n}: above it a single system fills the "
                          "chip (use GalaxySimulation)")
@@ -289,18 +319,13 @@ def check_ragged_arguments(positions, velocities, masses, precision_mode=Precisi
     GalaxyEnsemble takes it.  Returns (positions, velocities, masses, sizes, modes, G, softening, dt): the three as lists,
     the B star counts, the checked mode list (None for one mode) and the parameters as length-B lists; raises TypeError /
     ValueError naming the member."""
-    modes = None
-    if isinstance(precision_mode, (list, tuple)):
-        modes = check_mode_list(precision_mode)
-        storage = modes[0] if len(set(modes)) == 1 else PrecisionMode.FLOAT32
-    elif not isinstance(precision_mode, PrecisionMode):
+    modes, storage = _mode_or_list(precision_mode)
+    if modes is None and not isinstance(precision_mode, PrecisionMode):
         raise TypeError(f"precision_mode must be a PrecisionMode or a list of them, got {type(precision_mode).__name__}")
-    elif precision_mode not in _MODES:
+    if modes is None and precision_mode not in _MODES:
         raise ValueError(f"RaggedEnsemble runs the FLOAT64, FLOAT32, BFLOAT16 and FLOAT16 modes; {precision_mode.name} needs "
                          "per-member quantisation tables (the ragged grid modes are a follow-up; members of one size: "
                          "QuantizedEnsemble)")
-    else:
-        storage = precision_mode
     lists = []
     for name, seq in (("positions", positions), ("velocities", velocities), ("masses", masses)):
         if isinstance(seq, torch.Tensor) or isinstance(seq, (str, bytes)) or not isinstance(seq, Sequence):
@@ -320,8 +345,7 @@ def check_ragged_arguments(positions, velocities, masses, precision_mode=Precisi
     sizes, dim = [], None
     for b in range(B):
         for name, t in (("positions", positions[b]), ("velocities", velocities[b]), ("masses", masses[b])):
-            if not isinstance(t, torch.Tensor):
-                raise TypeError(f"{name}[{b}] must be a torch.Tensor, got {type(t).__name__}")
+            _check_tensor(name, t, b)
         if positions[b].dim() != 2 or masses[b].dim() != 1:
             raise ValueError(f"member {b}: positions must be (N, D) with (N,) masses, got {tuple(positions[b].shape)} and "
                              f"{tuple(masses[b].shape)}")
@@ -337,9 +361,7 @@ def check_ragged_arguments(positions, velocities, masses, precision_mode=Precisi
             raise ValueError(f"member {b}: positions {tuple(positions[b].shape)}, velocities {tuple(velocities[b].shape)} and "
                              f"masses {tuple(masses[b].shape)} disagree on (N, D)")
         for name, t in (("positions", positions[b]), ("velocities", velocities[b]), ("masses", masses[b])):
-            if t.dtype != want:
-                raise TypeError(f"{name}[{b}] must be {want} under {storage.name} (got {t.dtype}): an ensemble holds settled "
-                                "state only; mixed dtypes and the promotion timeline are GalaxySimulation's")
+            _check_tensor(name, t, b, dtype=want, mode=storage)
         if n > MAX_STARS[want]:
             raise ValueError(f"member {b} has N = {n}, above the limit of {MAX_STARS[want]} for {want} state: a single system "
                              "of that size fills the chip (use GalaxySimulation)")
@@ -356,24 +378,12 @@ def _level_list(value):
     return [int(v) for v in value] if isinstance(value, list) else int(value)
 
 
-def check_grid_arguments(positions, velocities, masses, precision_mode=PrecisionMode.INT8_SIM, custom_levels=None, G=0.001,
-                         softening=0.1, dt=0.01):
-    """Validate QuantizedEnsemble's constructor arguments without touching a device.  Returns (positions, velocities,
-    masses, levels, G, softening, dt) with the tensors shaped (B, N, D) / (B, N) and levels and the parameters as length-B
-    lists; raises ValueError / TypeError."""
-    if not isinstance(precision_mode, PrecisionMode):
-        raise TypeError(f"precision_mode must be a PrecisionMode, got {type(precision_mode).__name__}")
-    if precision_mode not in _GRID_MODES:
-        raise ValueError(f"QuantizedEnsemble runs the INT8_SIM, INT4_SIM and CUSTOM modes; {precision_mode.name} is "
-                         "GalaxyEnsemble's")
-    levels = _level_list(custom_levels)
-    if precision_mode != PrecisionMode.CUSTOM and levels is not None:
-        fixed = 256 if precision_mode == PrecisionMode.INT8_SIM else 16
-        raise ValueError(f"custom_levels belongs to the CUSTOM mode: {precision_mode.name} has {fixed} levels (pass None)")
+def _grid_arguments(positions, velocities, masses, precision_mode, levels, cap, tail, G, softening, dt):
+    """check_grid_arguments / check_fine_grid_arguments behind their own mode rules: `levels` (from _level_list) in
+    [MIN_LEVELS, cap] -- tail(v) ends the refusal of a v outside --, the state, and the levels as a length-B list."""
     for v in (levels if isinstance(levels, list) else [levels] if levels is not None else []):
-        if not MIN_LEVELS <= v <= MAX_LEVELS:
-            raise ValueError(f"custom_levels must be in [{MIN_LEVELS}, {MAX_LEVELS}], got {v}: above {MAX_LEVELS} a solo run "
-                             "leaves the one-launch step, so a member would have no bit-identical counterpart")
+        if not MIN_LEVELS <= v <= cap:
+            raise ValueError(f"custom_levels must be in [{MIN_LEVELS}, {cap}], got {v}{tail(v)}")
     positions, velocities, masses, G, softening, dt = _check_state(
         positions, velocities, masses, precision_mode, G, softening, dt, [len(levels)] if isinstance(levels, list) else [])
     B = int(positions.shape[0])
@@ -390,34 +400,41 @@ def check_grid_arguments(positions, velocities, masses, precision_mode=Precision
     return positions, velocities, masses, levels, G, softening, dt
 
 
+def check_grid_arguments(positions, velocities, masses, precision_mode=PrecisionMode.INT8_SIM, custom_levels=None, G=0.001,
+                         softening=0.1, dt=0.01):
+    """Validate QuantizedEnsemble's constructor arguments without touching a device.  Returns (positions, velocities,
+    masses, levels, G, softening, dt) with the tensors shaped (B, N, D) / (B, N) and levels and the parameters as length-B
+    lists; raises ValueError / TypeError."""
+    if not isinstance(precision_mode, PrecisionMode):
+        raise TypeError(f"precision_mode must be a PrecisionMode, got {type(precision_mode).__name__}")
+    if precision_mode not in _GRID_MODES:
+        raise ValueError(f"QuantizedEnsemble runs the INT8_SIM, INT4_SIM and CUSTOM modes; {precision_mode.name} is "
+                         "GalaxyEnsemble's")
+    levels = _level_list(custom_levels)
+    if precision_mode != PrecisionMode.CUSTOM and levels is not None:
+        fixed = 256 if precision_mode == PrecisionMode.INT8_SIM else 16
+        raise ValueError(f"custom_levels belongs to the CUSTOM mode: {precision_mode.name} has {fixed} levels (pass None)")
+    tail = (f": above {MAX_LEVELS} a solo run leaves the one-launch step, so a member would have no bit-identical "
+            "counterpart")
+    return _grid_arguments(positions, velocities, masses, precision_mode, levels, MAX_LEVELS, lambda v: tail, G, softening, dt)
+
+
 def check_fine_grid_arguments(positions, velocities, masses, custom_levels=None, G=0.001, softening=0.1, dt=0.01):
     """Validate FineGridEnsemble's constructor arguments without touching a device: check_grid_arguments under CUSTOM with
     the level range [2, MAX_FINE_LEVELS].  Returns (positions, velocities, masses, levels, G, softening, dt) as there; raises
     ValueError / TypeError."""
-    levels = _level_list(custom_levels)
-    for v in (levels if isinstance(levels, list) else [levels] if levels is not None else []):
-        if not MIN_LEVELS <= v <= MAX_FINE_LEVELS:
-            more = (": a solo GalaxySimulation(custom_levels=...) serves such grids through its generic kernel"
-                    if v > MAX_FINE_LEVELS else "")
-            raise ValueError(f"custom_levels must be in [{MIN_LEVELS}, {MAX_FINE_LEVELS}], got {v}{more}")
-    positions, velocities, masses, G, softening, dt = _check_state(
-        positions, velocities, masses, PrecisionMode.CUSTOM, G, softening, dt, [len(levels)] if isinstance(levels, list) else [])
-    B = int(positions.shape[0])
-    if levels is None:
-        levels = [DEFAULT_CUSTOM_LEVELS] * B
-    elif not isinstance(levels, list):
-        levels = [levels] * B
-    elif len(levels) != B:
-        raise ValueError(f"custom_levels has {len(levels)} entries for {B} members")
-    return positions, velocities, masses, levels, G, softening, dt
+    def tail(v):
+        return (": a solo GalaxySimulation(custom_levels=...) serves such grids through its generic kernel"
+                if v > MAX_FINE_LEVELS else "")
+    return _grid_arguments(positions, velocities, masses, PrecisionMode.CUSTOM, _level_list(custom_levels), MAX_FINE_LEVELS,
+                           tail, G, softening, dt)
 
 
 def check_record_arguments(num_ticks, every, members) -> list:
     """Validate run_recorded's arguments without touching a device.  Returns the tick offsets of the samples relative to
     the tick at entry, [0, every, 2 * every, ...] up to num_ticks; raises TypeError / ValueError."""
     for name, v in (("num_ticks", num_ticks), ("every", every), ("members", members)):
-        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
-            raise TypeError(f"{name} must be an int, got {type(v).__name__}")
+        _typed(name, v)
     num_ticks, every, members = int(num_ticks), int(every), int(members)
     if num_ticks < 0:
         raise ValueError(f"num_ticks must be >= 0, got {num_ticks}")
@@ -437,13 +454,11 @@ def check_member_ticks_arguments(num_ticks, every, members):
     sequence, tensor or numpy array of `members` ints, each >= 0; `every`: None (no samples) or an int >= 1.  Returns
     (budgets, offsets): the length-`members` list of budgets and the tick offsets of the samples relative to the tick at
     entry, [0, every, 2 * every, ...] up to the largest budget (None without samples); raises TypeError / ValueError."""
-    if isinstance(members, bool) or not isinstance(members, numbers.Integral):
-        raise TypeError(f"members must be an int, got {type(members).__name__}")
-    members = int(members)
+    members = int(_typed("members", members))
     if members < 1:
         raise ValueError(f"members must be >= 1, got {members}")
-    if every is not None and (isinstance(every, bool) or not isinstance(every, numbers.Integral)):
-        raise TypeError(f"every must be None or an int, got {type(every).__name__}")
+    if every is not None:
+        _typed("every", every, what="None or an int")
     num_ticks = _scalar_or_list(num_ticks, "num_ticks", numbers.Integral, "an int or a sequence of ints")
     if isinstance(num_ticks, list) and len(num_ticks) != members:
         raise ValueError(f"num_ticks has {len(num_ticks)} entries for {members} members")
@@ -584,15 +599,13 @@ def check_metrics_arguments(num_bins, max_radius, percentile, members):
     """Validate metrics()' arguments without touching a device.  Returns (num_bins, max_radius, percentile) with
     max_radius None (every member's own maximum radius) or a list of `members` floats; raises TypeError / ValueError."""
     for name, v in (("num_bins", num_bins), ("members", members)):
-        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
-            raise TypeError(f"{name} must be an int, got {type(v).__name__}")
+        _typed(name, v)
     num_bins, members = int(num_bins), int(members)
     if members < 1:
         raise ValueError(f"members must be >= 1, got {members}")
     if not 0 <= num_bins <= MAX_BINS:
         raise ValueError(f"num_bins must be in [0, {MAX_BINS}], got {num_bins}")
-    if isinstance(percentile, bool) or not isinstance(percentile, numbers.Real):
-        raise TypeError(f"percentile must be a number, got {type(percentile).__name__}")
+    _typed("percentile", percentile, numbers.Real, "a number")
     if percentile != percentile:
         raise ValueError("percentile is NaN")
     if max_radius is not None:
@@ -752,11 +765,9 @@ class GalaxyEnsemble:
     def __init__(self, positions, velocities, masses, precision_mode=PrecisionMode.FLOAT64,
                  G=0.001, softening=0.1, dt=0.01, device=None):
         self._handle = C.c_void_p()
-        modes = None
-        if isinstance(precision_mode, (list, tuple)):
+        modes, storage = _mode_or_list(precision_mode)
+        if modes is not None:
             # one mode per member: the state is checked under the storage mode, a lone galaxy is broadcast over the list
-            modes = check_mode_list(precision_mode)
-            storage = modes[0] if len(set(modes)) == 1 else PrecisionMode.FLOAT32
             positions, velocities, masses, self.G, self.softening, self.dt = _check_state(
                 positions, velocities, masses, storage, G, softening, dt, [len(modes)])
             check_mode_list(modes, int(positions.shape[0]))
@@ -782,13 +793,13 @@ class GalaxyEnsemble:
             dev = runtime.default_hip_device()
         cfg = N.NbEnsConfig(members=self.num_members, n=self.num_stars, dim=self._dim, mode=mode_code(precision_mode),
                             device=int(dev), flags=0)
-        self._create(cfg)
+        self._create(cfg, (_doubles(self.G), _doubles([s ** 2 for s in self.softening]), _doubles(self.dt)))
         self.set_state(positions=positions, velocities=velocities, masses=masses)
         N.check(N.lib().nb_ens_compute_accelerations(self._handle))
 
     # ------------------------------------------------------------------ native plumbing
-    def _create(self, cfg):
-        params = (_doubles(self.G), _doubles([s ** 2 for s in self.softening]), _doubles(self.dt))
+    def _create(self, cfg, params):
+        """The native handle of this kind of ensemble; params: the members' G, softening^2 and dt as C arrays."""
         if self._mixed:
             codes = (C.c_int32 * self.num_members)(*[mode_code(m) for m in self.precision_modes])
             N.check(N.lib().nb_ens_create_mixed(C.byref(self._handle), C.byref(cfg), codes, *params))
@@ -813,12 +824,7 @@ class GalaxyEnsemble:
 
     def _pointer(self, name, t):
         """(contiguous tensor kept alive by the caller, pointer, on_device) of an upload; shape and dtype checked."""
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} must be a torch.Tensor")
-        if tuple(t.shape) != self._shape(name):
-            raise ValueError(f"{name} must have shape {self._shape(name)}, got {tuple(t.shape)}")
-        if t.dtype != self._dtype:
-            raise TypeError(f"{name} must be {self._dtype}, got {t.dtype}")
+        _check_tensor(name, t, shape=self._shape(name), dtype=self._dtype)
         t = t.detach().contiguous()
         on_device = t.device.type == "cuda"
         if on_device:
@@ -891,23 +897,23 @@ class GalaxyEnsemble:
         offsets = check_record_arguments(num_ticks, every, self.num_members)
         return self._recorded_call("nb_ens_run_recorded", (int(num_ticks), int(every)), offsets, advance=int(num_ticks))
 
-    def _recorded_call(self, entry, head, offsets, tail=(), advance=None, own=None):
+    def _recorded_call(self, entry, head, offsets, tail=(), advance=None, own=None, energies=True):
         """One recorded native run: `entry`(handle, *head, kinetic, potential, capacity, on_device, &samples, *tail) with
-        room for one sample per offset (`offsets` None or empty: no buffers), the sample count checked, the clocks
-        advanced by `advance` / `own` (_advance; None: the caller does it).  Returns the EnergyHistory at the absolute
-        ticks, or None without samples."""
+        room for one sample per offset (`offsets` None or empty, or energies False: no energy buffers), the sample count
+        checked, the clocks advanced by `advance` / `own` (_advance; None: the caller does it).  Returns the EnergyHistory at
+        the absolute ticks, or None without energy samples."""
         S, B = len(offsets or ()), self.num_members
         ke = pe = None
-        if S:
+        if S and energies:
             ke = torch.empty((S, B), dtype=torch.float64, device=self.device)
             pe = torch.empty((S, B), dtype=torch.float64, device=self.device)
         got = C.c_int32()
         N.check(getattr(N.lib(), entry)(
-            self._handle, *head, C.c_void_p(ke.data_ptr()) if S else None, C.c_void_p(pe.data_ptr()) if S else None, S,
-            int(self.device.type == "cuda"), C.byref(got), *tail))
+            self._handle, *head, C.c_void_p(ke.data_ptr()) if ke is not None else None,
+            C.c_void_p(pe.data_ptr()) if pe is not None else None, S, int(self.device.type == "cuda"), C.byref(got), *tail))
         if got.value != S:
             raise RuntimeError(f"{entry} wrote {got.value} samples, expected {S}")
-        history = EnergyHistory([self.tick + o for o in offsets], ke, pe) if S else None
+        history = EnergyHistory([self.tick + o for o in offsets], ke, pe) if ke is not None else None
         if advance is not None:
             self._advance(advance, own=own)
         return history
@@ -952,9 +958,7 @@ class GalaxyEnsemble:
         per member), and after every batch the explosion test of `explosion_reason` on the device.  A member that trips
         it is halted there; nothing is read back before the end of the call."""
         import numpy as np
-        if isinstance(check_interval, bool) or not isinstance(check_interval, numbers.Integral):
-            raise TypeError(f"check_interval must be an int, got {type(check_interval).__name__}")
-        check_interval = int(check_interval)
+        check_interval = int(_typed("check_interval", check_interval))
         if check_interval < 1:
             raise ValueError(f"check_interval must be >= 1, got {check_interval}")
         budgets, _ = check_member_ticks_arguments(max_ticks, None, self.num_members)
@@ -1031,17 +1035,11 @@ class GalaxyEnsemble:
         baselines, offsets = check_divergence_arguments(num_ticks, every, baseline, self.num_members)
         S, B = len(offsets), self.num_members
         dv = [torch.empty((S, B), dtype=torch.float64, device=self.device) for _ in range(3)]
-        en = [torch.empty((S, B), dtype=torch.float64, device=self.device) for _ in range(2)] if energies else []
-        got = C.c_int32()
-        N.check(N.lib().nb_ens_run_diverged(
-            self._handle, int(num_ticks), int(every), (C.c_int32 * B)(*baselines), int(bool(energies)),
-            *[C.c_void_p(t.data_ptr()) for t in dv], *([C.c_void_p(t.data_ptr()) for t in en] or [None, None]), S,
-            int(self.device.type == "cuda"), C.byref(got)))
-        if got.value != S:
-            raise RuntimeError(f"nb_ens_run_diverged wrote {got.value} samples, expected {S}")
         ticks = [self.tick + o for o in offsets]
-        self._advance(int(num_ticks))
-        return DivergenceHistory(ticks, baselines, dv[0], dv[1], dv[2], EnergyHistory(ticks, en[0], en[1]) if energies else None)
+        head = (int(num_ticks), int(every), (C.c_int32 * B)(*baselines), int(bool(energies)),
+                *[C.c_void_p(t.data_ptr()) for t in dv])
+        energy = self._recorded_call("nb_ens_run_diverged", head, offsets, advance=int(num_ticks), energies=bool(energies))
+        return DivergenceHistory(ticks, baselines, dv[0], dv[1], dv[2], energy)
 
     def energies(self):
         """(kinetic, potential): float64 tensors of shape (B,) on `self.device`, all members evaluated in one batched
@@ -1132,10 +1130,9 @@ class QuantizedEnsemble(GalaxyEnsemble):
             positions, velocities, masses, precision_mode, custom_levels, G, softening, dt)
         self._construct(positions, velocities, masses, precision_mode, device)
 
-    def _create(self, cfg):
+    def _create(self, cfg, params):
         levels = (C.c_int32 * len(self.levels))(*self.levels) if self.precision_mode == PrecisionMode.CUSTOM else None
-        N.check(N.lib().nb_ens_create_grid(C.byref(self._handle), C.byref(cfg), levels, _doubles(self.G),
-                                           _doubles([s ** 2 for s in self.softening]), _doubles(self.dt)))
+        N.check(N.lib().nb_ens_create_grid(C.byref(self._handle), C.byref(cfg), levels, *params))
 
     def quant_debug(self) -> dict:
         """Grid internals of every member's last force evaluation, as GalaxySimulation.quant_debug() gives them for a solo
@@ -1175,10 +1172,9 @@ class FineGridEnsemble(QuantizedEnsemble):
             positions, velocities, masses, custom_levels, G, softening, dt)
         self._construct(positions, velocities, masses, PrecisionMode.CUSTOM, device)
 
-    def _create(self, cfg):
+    def _create(self, cfg, params):
         levels = (C.c_int32 * len(self.levels))(*self.levels)
-        N.check(N.lib().nb_ens_create_grid_wide(C.byref(self._handle), C.byref(cfg), levels, _doubles(self.G),
-                                                _doubles([s ** 2 for s in self.softening]), _doubles(self.dt)))
+        N.check(N.lib().nb_ens_create_grid_wide(C.byref(self._handle), C.byref(cfg), levels, *params))
 
 
 class RaggedEnsemble(GalaxyEnsemble):
@@ -1198,11 +1194,10 @@ class RaggedEnsemble(GalaxyEnsemble):
         self._construct(*padded, precision_mode, device, modes)       # (num_stars: the capacity, for the handle's shape)
         self.num_stars = list(sizes)
 
-    def _create(self, cfg):
+    def _create(self, cfg, params):
         B = self.num_members
         codes = (C.c_int32 * B)(*[mode_code(m) for m in self.precision_modes]) if self._mixed else None
-        N.check(N.lib().nb_ens_create_ragged(C.byref(self._handle), C.byref(cfg), (C.c_int32 * B)(*self._sizes), codes,
-                                             _doubles(self.G), _doubles([s ** 2 for s in self.softening]), _doubles(self.dt)))
+        N.check(N.lib().nb_ens_create_ragged(C.byref(self._handle), C.byref(cfg), (C.c_int32 * B)(*self._sizes), codes, *params))
 
     def _shape(self, name):
         return (self.num_members, self._capacity) if name == "masses" else (self.num_members, self._capacity, self._dim)
@@ -1220,13 +1215,7 @@ class RaggedEnsemble(GalaxyEnsemble):
         if len(members) != self.num_members:
             raise ValueError(f"{name} has {len(members)} entries for {self.num_members} members")
         for b, t in enumerate(members):
-            if not isinstance(t, torch.Tensor):
-                raise TypeError(f"{name}[{b}] must be a torch.Tensor, got {type(t).__name__}")
-            want = (self._sizes[b],) + self._shape(name)[2:]
-            if tuple(t.shape) != want:
-                raise ValueError(f"{name}[{b}] must have shape {want}, got {tuple(t.shape)}")
-            if t.dtype != self._dtype:
-                raise TypeError(f"{name}[{b}] must be {self._dtype}, got {t.dtype}")
+            _check_tensor(name, t, b, shape=(self._sizes[b],) + self._shape(name)[2:], dtype=self._dtype)
         out = torch.full(self._shape(name), float("nan"), dtype=self._dtype, device=members[0].device)
         for b, t in enumerate(members):
             out[b, :self._sizes[b]] = t.detach().to(out.device)

@@ -113,3 +113,45 @@ def test_no_gpu_means_loud_failure_not_fallback():
     p, v, m = (t[0] for t in state(1, 16, 2, torch.float32))
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         nb.GalaxyEnsemble(p, v, m, precision_mode=PM.FLOAT16, softening=[0.05, 0.1])
+
+
+# The refusals the five C creators share, in the order they are tested (null -> shape -> mode -> lists -> n limit ->
+# device): every creator gives the same return code and the same text, and leaves the handle null.  Modes and lists are
+# valid for every creator, so that each row reaches the refusal it names.
+_CREATORS = {     # name -> (cfg mode, the arguments between cfg and G as a function of (members, n))
+    "nb_ens_create": (_native.MODE_CODES["float32"], lambda b, n: ()),
+    "nb_ens_create_grid": (_native.MODE_CODES["custom"], lambda b, n: (None,)),
+    "nb_ens_create_grid_wide": (_native.MODE_CODES["custom"], lambda b, n: (None,)),
+    "nb_ens_create_mixed": (_native.MODE_CODES["float32"], lambda b, n: (_i32s([_native.MODE_CODES["float32"]] * b),)),
+    "nb_ens_create_ragged": (_native.MODE_CODES["float32"], lambda b, n: (_i32s([1] * b), None)),
+}
+_SHARED_REFUSALS = [    # (members, n, dim), return code, text
+    ((0, 16, 2), -1, "members must be in [1, 1024]"),
+    ((1025, 16, 2), -1, "members must be in [1, 1024]"),
+    ((2, 0, 2), -1, "n must be >= 1"),
+    ((2, 16, 4), -1, "dim must be 2 or 3"),
+    ((2, 3073, 2), -5, "above the one-launch step's limit of 3072"),
+    ((2, 16, 2), -2, "no CPU fallback"),
+]
+
+
+def _i32s(values):
+    import ctypes as C
+    return (C.c_int32 * max(len(values), 1))(*values)
+
+
+@pytest.mark.parametrize("shape, code, text", _SHARED_REFUSALS, ids=[r[2] + f" {r[0]}" for r in _SHARED_REFUSALS])
+@pytest.mark.parametrize("creator", list(_CREATORS))
+def test_every_creator_shares_the_refusals(creator, shape, code, text):
+    import ctypes as C
+    if code == -2 and torch.cuda.is_available():
+        pytest.skip("checks the no-GPU behaviour")
+    members, n, dim = shape
+    mode, lists = _CREATORS[creator]
+    cfg = _native.NbEnsConfig(members=members, n=n, dim=dim, mode=mode, device=0, flags=0)
+    params = [(C.c_double * max(members, 1))(*[0.01] * members) for _ in range(3)]
+    handle = C.c_void_p(1)        # (not null: the creator must clear it)
+    rc = getattr(_native.lib(), creator)(C.byref(handle), C.byref(cfg), *lists(members, n), *params)
+    assert rc == code
+    assert text in _native.last_error()
+    assert handle.value is None
