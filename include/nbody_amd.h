@@ -213,9 +213,25 @@ int nb_ens_create_mixed(nb_ens **out, const nb_ens_config *cfg, const int32_t *m
  * (those of a handle of the member's size alone, bit for bit).  nb_ens_divergence / nb_ens_run_diverged refuse a
  * baseline of another size than the member's (NB_ERR_INVALID naming both).  NB_ERR_UNSUPPORTED, as follow-ups:
  * nb_ens_metrics (ragged metrics), nb_ens_crash_measures and nb_ens_run_crash_watched (ragged crash watch),
- * nb_ens_quant_info and nb_ens_quant_bin_sums (ragged grid modes). */
+ * nb_ens_quant_info and nb_ens_quant_bin_sums (ragged grid modes: a handle of nb_ens_create_ragged_grid has them). */
 int nb_ens_create_ragged(nb_ens **out, const nb_ens_config *cfg, const int32_t *sizes, const int32_t *modes,
                          const double *G, const double *softening_sq, const double *dt);
+/* The grid modes for members of different sizes (the grid half of the same density sweeps: omega_point_test.py's
+ * "int8" / "int4" points and density_limit_test.py's "broken" runs are 256- and 16-level grids on r^2).  sizes and
+ * the padded layout as nb_ens_create_ragged; cfg->mode and levels as nb_ens_create_grid: NB_INT8_SIM, NB_INT4_SIM
+ * (levels must be NULL) or NB_CUSTOM with `members` level counts in [2, 256] or NULL for 64 everywhere (any other
+ * mode: NB_ERR_UNSUPPORTED; a count outside: NB_ERR_INVALID -- grids above 256 levels for members of different sizes
+ * are a follow-up, nb_ens_create_grid_wide serves members of one size).  Refusals in the order of every creator: null,
+ * shape, mode, levels, sizes, the fp32 limit on cfg->n, the device.
+ * An evaluation is nb_ens_create_grid's launches, whatever the sizes: max r^2 + tables (a workgroup beyond its
+ * member's size returns at once; the last of the member's OWN workgroups builds its tables), ONE force launch over
+ * the work list ("ens_grid_step_ragged_kernel", 512 threads per workgroup for every member) and under INT8 / INT4 the
+ * force snap + kicks.  Member b is bit-identical to the nb_sim of its own size, mode and levels -- state,
+ * accelerations, nb_ens_quant_info and nb_ens_quant_bin_sums (rows of cfg->n entries of which member b's first
+ * sizes[b] are written) -- and no kernel reads or writes a padding row.  Everything else is as on a handle of
+ * nb_ens_create_ragged, the three NB_ERR_UNSUPPORTED follow-ups included. */
+int nb_ens_create_ragged_grid(nb_ens **out, const nb_ens_config *cfg, const int32_t *sizes, const int32_t *levels,
+                              const double *G, const double *softening_sq, const double *dt);
 /* The work list of a ragged handle's force launch, without a device: `members` sizes (each >= 1), lanes 16 / 32 /
  * 64 lanes per target (a workgroup of 512 threads holds 512 / lanes targets).  *items = the number of work items;
  * work: NULL to ask for the count alone, else room for `capacity` items of {member, blk} (2 int32 each; capacity
@@ -354,7 +370,7 @@ int nb_ens_metrics(nb_ens *e, int32_t num_bins, const double *max_radius, double
 /* members; batched force launches issued since creation (nb_ens_compute_accelerations and one per tick;
  * the opening kick + drift launch of an nb_ens_step is not counted); name of the last force kernel
  * ("ens_step_kernel", "ens_step_mixed_kernel" on a handle of nb_ens_create_mixed, "ens_step_ragged_kernel" on a
- * handle of nb_ens_create_ragged, or "ens_grid_step_kernel" on a
+ * handle of nb_ens_create_ragged, "ens_grid_step_ragged_kernel" on one of nb_ens_create_ragged_grid, or "ens_grid_step_kernel" on a
  * grid-mode handle -- "ens_grid_step_wide_kernel" when a member exceeds 256 levels -- whose table and finish launches
  * are not counted either; "none" before the first).  Any output may be NULL. */
 int nb_ens_info(nb_ens *e, int32_t *members, int64_t *force_launches, const char **kernel_name);

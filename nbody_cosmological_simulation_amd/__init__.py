@@ -10,8 +10,9 @@ from .ensemble import (GalaxyEnsemble, QuantizedEnsemble, EnergyHistory, Ensembl
                        check_metrics_arguments, StabilityReport, check_member_ticks_arguments, explosion_reason,
                        CrashMeasures, CrashPointReport, crash_kind, crash_value, crash_severity, Divergence, DivergenceHistory,
                        check_mode_list, check_divergence_arguments, entropy_bits, divergence_rate, FineGridEnsemble,
-                       check_fine_grid_arguments, RaggedEnsemble, check_ragged_arguments)
+                       check_fine_grid_arguments, RaggedEnsemble, check_ragged_arguments, RaggedQuantizedEnsemble,
+                       check_ragged_grid_arguments)
 
-__all__ = ["GalaxySimulation", "GalaxyEnsemble", "QuantizedEnsemble", "FineGridEnsemble", "check_fine_grid_arguments", "RaggedEnsemble", "check_ragged_arguments", "EnergyHistory", "EnsembleMetrics", "check_record_arguments", "check_metrics_arguments", "StabilityReport", "check_member_ticks_arguments", "explosion_reason", "CrashMeasures", "CrashPointReport", "crash_kind", "crash_value", "crash_severity", "Divergence", "DivergenceHistory", "check_mode_list", "check_divergence_arguments", "entropy_bits", "divergence_rate", "run_comparison", "PrecisionMode", "quantize_distance_squared",
+__all__ = ["GalaxySimulation", "GalaxyEnsemble", "QuantizedEnsemble", "FineGridEnsemble", "check_fine_grid_arguments", "RaggedEnsemble", "check_ragged_arguments", "RaggedQuantizedEnsemble", "check_ragged_grid_arguments","EnergyHistory", "EnsembleMetrics", "check_record_arguments", "check_metrics_arguments", "StabilityReport", "check_member_ticks_arguments", "explosion_reason", "CrashMeasures", "CrashPointReport", "crash_kind", "crash_value", "crash_severity", "Divergence", "DivergenceHistory", "check_mode_list", "check_divergence_arguments", "entropy_bits", "divergence_rate", "run_comparison", "PrecisionMode", "quantize_distance_squared",
            "quantize_force", "_grid_quantize", "_grid_quantize_safe", "get_mode_from_string",
            "describe_mode"]

@@ -38,7 +38,7 @@ EXPORTS = [
     "nb_ens_run_members", "nb_ens_crash_measures", "nb_ens_run_crash_watched",
     "nb_ens_create_mixed", "nb_ens_divergence", "nb_ens_run_diverged",
     "nb_ens_create_grid_wide", "nb_ens_quant_bin_sums",
-    "nb_ens_create_ragged", "nb_ens_ragged_plan",
+    "nb_ens_create_ragged", "nb_ens_ragged_plan", "nb_ens_create_ragged_grid",
 ]
 
 
@@ -132,6 +132,7 @@ def lib():
         "nb_ens_create_grid": ([C.POINTER(vp), C.POINTER(NbEnsConfig), pi32, pdbl, pdbl, pdbl], C.c_int),
         "nb_ens_create_mixed": ([C.POINTER(vp), C.POINTER(NbEnsConfig), pi32, pdbl, pdbl, pdbl], C.c_int),
         "nb_ens_create_ragged": ([C.POINTER(vp), C.POINTER(NbEnsConfig), pi32, pi32, pdbl, pdbl, pdbl], C.c_int),
+        "nb_ens_create_ragged_grid": ([C.POINTER(vp), C.POINTER(NbEnsConfig), pi32, pi32, pdbl, pdbl, pdbl], C.c_int),
         "nb_ens_ragged_plan": ([pi32, i32, i32, pi32, i64, C.POINTER(C.c_int64)], C.c_int),
         "nb_ens_divergence": ([vp, pi32, vp, vp, vp, C.c_int], C.c_int),
         "nb_ens_run_diverged": ([vp, i32, i32, pi32, i32, vp, vp, vp, vp, vp, i64, C.c_int, pi32], C.c_int),

@@ -12,13 +12,14 @@
 // use.  Every device buffer is a DevBuf the handle owns, and what the step kernels read is listed once, in the handle's
 // EnsStepArgs (nb_internal.h).
 //
-// Creation.  The five nb_ens_create* entries are their own argument checks in front of ONE create(): the shared
+// Creation.  The six nb_ens_create* entries are their own argument checks in front of ONE create(): the shared
 // refusals in their order (null, shape, the entry's mode rule, the lists, the n limit, the device), every allocation and
 // upload, one wait, one failure exit.
 //
 // The launch train.  launch_force is one force evaluation: it picks the step launcher from what the record holds (tables:
 // a grid step behind the tables launches, with the finish launch under INT8 / INT4, which snaps the forces and carries
-// the kicks IN PLACE; sizes: the ragged step over the work list; hooks: the mixed step; else the uniform step) and notes
+// the kicks IN PLACE -- with sizes as well: the same three launches in their ragged forms; sizes: the ragged step over the
+// work list; hooks: the mixed step; else the uniform step) and notes
 // the kernel's name.  run_train is nb_ens_step's train of launches: one kick + drift, then one force launch per tick.  The
 // members' stop ticks, where a run has them, are a device array that every kernel of the tick path reads (nb_device.h)
 // and a watch kernel lowers on the device (nb_ens_watch.hip, nb_ens_crash.hip); without one the instantiations without
@@ -34,7 +35,7 @@
 // the capacity's shape).  nb_ens_energies, nb_ens_divergence, nb_ens_crash_measures and nb_ens_metrics are one sampler's
 // kernels alone on the resident state; nb_ens_quant_bin_sums runs the grid evaluation once more with the BINS
 // instantiation of the pair sweep, forces into a scratch buffer.  The entries whose kernels are one workgroup per member
-// of one shape, and the grid modes', refuse a ragged handle (refuse_ragged).
+// of one shape refuse a ragged handle, and the grid modes' read-outs one that is no grid handle (refuse_ragged).
 #include <algorithm>
 #include <cstddef>
 #include <cstring>
@@ -94,7 +95,8 @@ struct nb_ens {
     // grid modes only (nb_ens_create_grid, nb_ens_create_grid_wide)
     bool grid = false, fq = false;            // HOOK_GRID; INT8 / INT4: forces snapped (and kicks applied) by the finish launch
     int allow_fast = 1;                       // the table-free pair path may be used (NB_NO_GRID_FAST unset), as nb_sim reads it
-    int grid_blocks = 0;                      // workgroups per member of the grid step: min / max partials per member
+    int grid_blocks = 0;                      // workgroups per member of the grid step: min / max partials per member (members
+                                              // of different sizes: the capacity's, at the ragged launch's workgroup size)
     std::vector<int32_t> levels;              // per member
     // what is uploaded / read back around a run (free to rewrite: every call that uploads one waits before it returns)
     std::vector<int32_t> stops_host;          // members stop ticks, then members halt reasons
@@ -168,7 +170,7 @@ int launch_tables(nb_ens *e, const int *stop, int t)
     GridTables *tabs = e->dev.tabs.as<GridTables>();
     const int *levels = e->dev.levels.as<int>();
     HIPCHK(nb_launch_ens_r2max_tables((const float *)a.pos_in, a.members, a.n, a.dim, a.prm, tabs, levels, 0.01f, e->allow_fast,
-                                      stop, t, e->stream));
+                                      stop, t, e->stream, a.sizes));
     if (a.max_levels > NB_LUT_MIN)
         HIPCHK(nb_launch_ens_tables_wide(a.members, a.max_levels, a.prm, tabs, levels, 0.01f, e->allow_fast, stop, t, e->stream));
     return NB_OK;
@@ -192,6 +194,14 @@ int launch_force(nb_ens *e, int do_kick, const int *stop = nullptr, int t = 0)
         if (a.max_levels > NB_LUT_MIN) {        // (CUSTOM only: no force bounds, no finish launch)
             HIPCHK(nb_launch_ens_grid_step_wide(a, do_kick, stop, t, e->stream));
             name = "ens_grid_step_wide_kernel";
+        } else if (a.sizes) {                   // members of different sizes: the same three launches, each with `sizes`
+            HIPCHK(nb_launch_ens_grid_step_ragged(a, e->fq ? NB_KICK_NONE : do_kick, stop, t, e->stream));
+            if (e->fq)
+                HIPCHK(nb_launch_ens_force_quant_finish((float *)a.acc, a.members, a.n * a.dim, e->levels[0], a.part,
+                                                        e->grid_blocks, e->dev.fbounds.as<double>(), (float *)a.vel,
+                                                        (float *)a.pos_in, a.prm, do_kick, stop, t, e->stream, a.sizes, a.dim,
+                                                        NB_ENS_RAGGED_BLOCK / a.lanes));
+            name = "ens_grid_step_ragged_kernel";
         } else {
             HIPCHK(nb_launch_ens_grid_step(a, e->fq ? NB_KICK_NONE : do_kick, stop, t, e->stream));
             if (e->fq)      // levels[0]: under INT8 / INT4 every member has the mode's 256 / 16 levels
@@ -499,7 +509,7 @@ int run_sampled(nb_ens *e, const SampledRun &r)
 }
 
 // the entries a handle of nb_ens_create_ragged refuses: their kernels are one workgroup per member of the handle's n, or
-// the grid modes'
+// the grid modes' (which serve a handle of nb_ens_create_ragged_grid)
 int refuse_ragged(const nb_ens *e, const char *entry, const char *follow_up)
 {
     if (e->step.sizes)
@@ -610,7 +620,8 @@ int create(const CreateSpec &s, ModeRule mode_rule)
         e->grid = true;
         e->fq = cfg->mode != NB_CUSTOM;
         e->allow_fast = knobs.no_grid_fast ? 0 : 1;
-        e->grid_blocks = nb_small_blocks(cfg->n, a.lanes);
+        // (a ragged handle: the one workgroup size of its launch, not the capacity's solo choice)
+        e->grid_blocks = s.sizes ? nb_ens_ragged_blocks(cfg->n, a.lanes) : nb_small_blocks(cfg->n, a.lanes);
         e->levels = lv;
         a.max_levels = *std::max_element(lv.begin(), lv.end());
         // zeroed once: every evaluation puts a member's maximum and arrival counter back (grid_tables_body)
@@ -717,6 +728,23 @@ int nb_ens_create_ragged(nb_ens **out, const nb_ens_config *cfg, const int32_t *
         if (modes && cfg->mode != NB_FLOAT32)
             return fail(NB_ERR_UNSUPPORTED, "nb_ens_create_ragged: with a mode list cfg->mode must be NB_FLOAT32, the storage mode "
                                             "of every cast mode (got mode %d)", cfg->mode);
+        return (int)NB_OK;
+    });
+}
+
+int nb_ens_create_ragged_grid(nb_ens **out, const nb_ens_config *cfg, const int32_t *sizes, const int32_t *levels, const double *G,
+                              const double *softening_sq, const double *dt)
+{
+    if (!sizes) return fail(NB_ERR_INVALID, "null argument");
+    CreateSpec s{out, cfg, G, softening_sq, dt};
+    s.levels = levels; s.level_cap = NB_LUT_MIN; s.sizes = sizes;
+    s.above_cap = "the ragged wide grid is a follow-up (members of one size: nb_ens_create_grid_wide)";
+    return create(s, [&] {
+        if (cfg->mode != NB_INT8_SIM && cfg->mode != NB_INT4_SIM && cfg->mode != NB_CUSTOM)
+            return fail(NB_ERR_UNSUPPORTED, "nb_ens_create_ragged_grid runs the INT8_SIM, INT4_SIM and CUSTOM modes (got mode "
+                                            "%d): the other modes are nb_ens_create_ragged's", cfg->mode);
+        if (cfg->mode != NB_CUSTOM && levels)
+            return fail(NB_ERR_INVALID, "levels must be NULL under INT8_SIM / INT4_SIM (256 / 16 levels)");
         return (int)NB_OK;
     });
 }
@@ -1032,8 +1060,10 @@ int nb_ens_info(nb_ens *e, int32_t *members, int64_t *force_launches, const char
 int nb_ens_quant_info(nb_ens *e, double *out)
 {
     if (!e || !out) return fail(NB_ERR_INVALID, "null argument");
-    if (int rc = refuse_ragged(e, "nb_ens_quant_info", "the ragged grid modes")) return rc;
-    if (!e->grid) return fail(NB_ERR_UNSUPPORTED, "quant info is only defined for the grid modes (nb_ens_create_grid)");
+    if (!e->grid) {        // (a ragged GRID handle -- nb_ens_create_ragged_grid -- is served; a ragged cast handle says why not)
+        if (int rc = refuse_ragged(e, "nb_ens_quant_info", "the ragged grid modes")) return rc;
+        return fail(NB_ERR_UNSUPPORTED, "quant info is only defined for the grid modes (nb_ens_create_grid)");
+    }
     DeviceGuard guard(e->cfg.device);
     const size_t B = (size_t)e->cfg.members;
     // the scalars behind the tables of every member, not the 48 KB of tables in front of them
@@ -1059,9 +1089,11 @@ int nb_ens_quant_info(nb_ens *e, double *out)
 int nb_ens_quant_bin_sums(nb_ens *e, int64_t *sum_k, int64_t *sum_kw, int64_t *pairs)
 {
     if (!e) return fail(NB_ERR_INVALID, "null handle");
-    if (int rc = refuse_ragged(e, "nb_ens_quant_bin_sums", "the ragged grid modes")) return rc;
-    if (!e->grid) return fail(NB_ERR_UNSUPPORTED, "the quant-bin read-out is only defined for the grid modes (nb_ens_create_grid, "
-                                                  "nb_ens_create_grid_wide)");
+    if (!e->grid) {
+        if (int rc = refuse_ragged(e, "nb_ens_quant_bin_sums", "the ragged grid modes")) return rc;
+        return fail(NB_ERR_UNSUPPORTED, "the quant-bin read-out is only defined for the grid modes (nb_ens_create_grid, "
+                                        "nb_ens_create_grid_wide)");
+    }
     if (!e->have_pos || !e->have_mass) return fail(NB_ERR_INVALID, "positions/masses not set");
     DeviceGuard guard(e->cfg.device);
     const EnsStepArgs &a = e->step;
@@ -1071,18 +1103,24 @@ int nb_ens_quant_bin_sums(nb_ens *e, int64_t *sum_k, int64_t *sum_kw, int64_t *p
     unsigned long long *bin_out = e->dev.bin_out.as<unsigned long long>();
     HIPCHK(hipMemsetAsync(bin_out, 0, bytes, e->stream));
     if (int rc = launch_tables(e, nullptr, 0)) return rc;
-    HIPCHK(nb_launch_ens_grid_bins((const float *)a.pos_in, e->dev.bin_acc.as<float>(), (const float *)a.mass, a.members, a.n,
-                                   a.dim, a.prm, a.lanes, a.tabs, a.max_levels, bin_out, e->stream));
+    if (a.sizes)
+        HIPCHK(nb_launch_ens_grid_bins_ragged(a, e->dev.bin_acc.as<float>(), bin_out, e->stream));
+    else
+        HIPCHK(nb_launch_ens_grid_bins((const float *)a.pos_in, e->dev.bin_acc.as<float>(), (const float *)a.mass, a.members, a.n,
+                                       a.dim, a.prm, a.lanes, a.tabs, a.max_levels, bin_out, e->stream));
     std::vector<unsigned long long> host(B * per);
     HIPCHK(hipMemcpyAsync(host.data(), bin_out, bytes, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     for (size_t b = 0; b < B; ++b) {
+        // a ragged member's block is packed for its own size nb; of its rows of the (members, n) outputs only the first nb
+        // entries are written
         const unsigned long long *h = host.data() + b * per;
-        for (size_t i = 0; i < n; ++i) {
+        const size_t nb = a.sizes ? (size_t)e->sizes_host[b] : n;
+        for (size_t i = 0; i < nb; ++i) {
             if (sum_k) sum_k[b * n + i] = (int64_t)h[i];
-            if (sum_kw) sum_kw[b * n + i] = (int64_t)h[n + i];
+            if (sum_kw) sum_kw[b * n + i] = (int64_t)h[nb + i];
         }
-        if (pairs) { pairs[2 * b] = (int64_t)h[2 * n]; pairs[2 * b + 1] = (int64_t)h[2 * n + 1]; }
+        if (pairs) { pairs[2 * b] = (int64_t)h[2 * nb]; pairs[2 * b + 1] = (int64_t)h[2 * nb + 1]; }
     }
     return NB_OK;
 }

@@ -17,6 +17,12 @@
 //
 // The hook is compiled in (a uniform handle) or HOOK_AT_RUN_TIME with hooks[member] (a mode list), as ens_step_kernel and
 // ens_step_mixed_kernel have it; the stop rule is theirs (nb_device.h), with blk from the work item.
+//
+// The grid modes (nb_ens_create_ragged_grid: INT8 / INT4 / CUSTOM up to NB_LUT_MIN levels) run small_grid_body over the
+// same work list (ens_grid_step_ragged_kernel), member b with its own tables.  There a pair's factor depends on which
+// pairs share its WAVE (the table-free path's ballot), so the argument above needs one more line: a wave is 64 / S
+// consecutive targets over all their sources, and its first target is a multiple of 64 / S at 256 and at 512 threads
+// alike -- the set of pairs in a wave, hence every factor, is the solo run's at either workgroup size.
 #include "nb_dispatch.h"
 #include "nb_small_body.h"
 #include "nb_internal.h"
@@ -55,6 +61,40 @@ ens_step_ragged_kernel(const T *__restrict__ pos_in, T *__restrict__ pos_out, T 
                                              p.G, p.eps2, p.half_dt, p.dt, do_kick, nullptr, hook_rt);
 }
 
+// grid hook over the work list: ens_grid_step_kernel's arguments and stop rule (nb_ensemble.hip) with the member, its size
+// and its target block from the work item.  Under INT8 / INT4 (part != null) workgroup w.blk of member b leaves its
+// {min, max} pair at part[(b * stride + w.blk) * 2], stride = nb_ens_ragged_blocks(cap, lanes): a member uses the first
+// ceil(sizes[b] / (ER_BLOCK / S)) pairs of its row.  BINS (nb_ens_quant_bin_sums; without stops, kicks or bounds): acc is
+// the caller's scratch, and member b's read-out goes to bin_out + b (2 cap + 2), laid out for the member's OWN n --
+// {s1[n], s2[n], {table-free pairs, table pairs}} -- the words behind them are not written.
+// waves per SIMD: 8, as the cast kernel above; ens_grid_step_kernel comes out there at 512 threads by itself
+// (profiles/ensemble_ragged_grid_step_resources.txt).
+template <int D, int S, bool STOPS, bool BINS>
+__global__ void __launch_bounds__(ER_BLOCK)
+ens_grid_step_ragged_kernel(const float *__restrict__ pos_in, float *__restrict__ pos_out, float *__restrict__ vel,
+                            float *__restrict__ acc, const float *__restrict__ mass, int cap, const int *__restrict__ sizes,
+                            const EnsWork *__restrict__ work, const EnsScalars<float> *__restrict__ prm, int do_kick,
+                            const GridTables *__restrict__ tabs, double *__restrict__ part, int stride,
+                            unsigned long long *__restrict__ bin_out, const int *__restrict__ stop, int t)
+{
+    static_assert(!(BINS && STOPS), "the bin read-out is an observer: no member is stopped for it");
+    const EnsWork w = work[blockIdx.x];              // member and target block: uniform per workgroup
+    const int b = w.member;
+    const int n = ens_member_count<true>(sizes, b, 1, cap);
+    const EnsScalars<float> p = prm[b];
+    const size_t o = (size_t)b * cap;
+    const int left = ens_ticks_left<STOPS>(stop, b, t);
+    if (STOPS && left <= 1) {
+        if (!part) ens_carry_positions<float, D, S, ER_BLOCK>(w.blk, pos_in + o * D, pos_out + o * D, n);   // (INT8 / INT4: no ping-pong)
+        if (left <= 0) return;
+        do_kick = ens_kick_mode(left, do_kick);
+    }
+    small_grid_body<D, S, BINS, ER_BLOCK>(w.blk, pos_in + o * D, pos_out + o * D, vel + o * D, acc + o * D, mass + o, n, p.G,
+                                          p.eps2, p.half_dt, p.dt, do_kick, tabs + b,
+                                          part ? part + (size_t)b * 2 * stride : nullptr,
+                                          BINS ? bin_out + (size_t)b * (2 * (size_t)cap + 2) : nullptr);
+}
+
 }  // namespace
 
 hipError_t nb_launch_ens_step_ragged(const EnsStepArgs &a, int do_kick, const int *stop, int t, hipStream_t st)
@@ -76,6 +116,37 @@ hipError_t nb_launch_ens_step_ragged(const EnsStepArgs &a, int do_kick, const in
         if (a.is_f64) return nb::pick<HOOK_NONE>(a.hook, [&](auto H) { return launch(nb::real_tag<double>{}, H); });
         return nb::pick<HOOK_NONE, HOOK_BF16, HOOK_F16, HOOK_AT_RUN_TIME>(a.hook, [&](auto H) {
             return launch(nb::real_tag<float>{}, H);
+        });
+    });
+}
+
+hipError_t nb_launch_ens_grid_step_ragged(const EnsStepArgs &a, int do_kick, const int *stop, int t, hipStream_t st)
+{
+    if (hipError_t err = nb_ens_step_check(a, do_kick, t)) return err;       // (a.n: the capacity)
+    if (!a.sizes || !a.work || a.items < 1 || a.is_f64 || !a.tabs) return hipErrorInvalidValue;
+    if (a.max_levels < 2 || a.max_levels > NB_LUT_MIN) return hipErrorInvalidValue;
+    return nb::pick<2, 3>(a.dim, [&](auto D) {
+        return nb::pick_small_step<ER_BLOCK>(a.lanes, ER_BLOCK, stop != nullptr, [&](auto S, auto, auto ST) {
+            hipLaunchKernelGGL((ens_grid_step_ragged_kernel<D.value, S.value, ST.value, false>), dim3(a.items), dim3(ER_BLOCK), 0,
+                               st, (const float *)a.pos_in, (float *)a.pos_out, (float *)a.vel, (float *)a.acc,
+                               (const float *)a.mass, a.n, a.sizes, a.work, (const EnsScalars<float> *)a.prm, do_kick, a.tabs,
+                               a.part, nb_ens_ragged_blocks(a.n, a.lanes), nullptr, stop, t);
+            return hipGetLastError();
+        });
+    });
+}
+
+hipError_t nb_launch_ens_grid_bins_ragged(const EnsStepArgs &a, float *acc, unsigned long long *bin_out, hipStream_t st)
+{
+    if (a.members < 1 || a.members > NB_ENS_MAX_MEMBERS || a.n < 1 || !acc || !bin_out) return hipErrorInvalidValue;
+    if (!a.sizes || !a.work || a.items < 1 || a.is_f64 || !a.tabs) return hipErrorInvalidValue;
+    if (a.max_levels < 2 || a.max_levels > NB_LUT_MIN) return hipErrorInvalidValue;
+    return nb::pick<2, 3>(a.dim, [&](auto D) {
+        return nb::pick<64, 32, 16>(a.lanes, [&](auto S) {
+            hipLaunchKernelGGL((ens_grid_step_ragged_kernel<D.value, S.value, false, true>), dim3(a.items), dim3(ER_BLOCK), 0, st,
+                               (const float *)a.pos_in, nullptr, nullptr, acc, (const float *)a.mass, a.n, a.sizes, a.work,
+                               (const EnsScalars<float> *)a.prm, (int)NB_KICK_NONE, a.tabs, nullptr, 0, bin_out, nullptr, 0);
+            return hipGetLastError();
         });
     });
 }

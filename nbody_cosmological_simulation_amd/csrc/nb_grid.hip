@@ -651,16 +651,18 @@ grid_quantize_safe_tab_kernel(const float *__restrict__ in, float *__restrict__ 
 constexpr int NB_R2MAX_SPLIT = 8;
 
 // behind r2max_block, shared by the solo and the batched kernel: count this workgroup's arrival at *tab; the last of
-// `gridDim.x * gridDim.y` builds the tables from the finished maximum, the others return (*levels is read by the last only).
+// `arrivals` builds the tables from the finished maximum, the others return (*levels is read by the last only).  arrivals:
+// the workgroups that call this for *tab in the launch -- gridDim.x * gridDim.y where every workgroup of a member works,
+// the member's own count where some return before they get here (ens_r2max_tables_ragged_kernel).
 // WIDE_OK (batched kernel): a grid above NB_LUT_MIN levels has multi-chunk tables, which ens_tables_wide_kernel builds from
 // the maximum left in tab->r2max_bits -- the last workgroup only puts the arrival counter back for that launch.
 template <bool WIDE_OK = false>
 __device__ __forceinline__ void r2max_last_builds_tables(GridTables *tab, const int *levels, float G, float eps2,
-                                                         float min_val, int allow_fast)
+                                                         float min_val, int allow_fast, unsigned int arrivals)
 {
     static_assert(NB_BLOCK == NB_LUT_MIN, "the last workgroup runs the single-block tables code");
     __shared__ unsigned int s_bits;
-    if (!last_block_arrives(&tab->blocks_done, gridDim.x * gridDim.y)) return;
+    if (!last_block_arrives(&tab->blocks_done, arrivals)) return;
     if (WIDE_OK && *levels > NB_LUT_MIN) {
         if (threadIdx.x == 0) tab->blocks_done = 0u;
         return;
@@ -677,7 +679,7 @@ r2max_tables_kernel(const float *__restrict__ pos, ForceGeom g, float eps2, Grid
                     float G, float min_val, int allow_fast)
 {
     r2max_block<D, R, NB_R2MAX_SPLIT>(pos, g, eps2, tab);
-    r2max_last_builds_tables(tab, &levels, G, eps2, min_val, allow_fast);
+    r2max_last_builds_tables(tab, &levels, G, eps2, min_val, allow_fast, gridDim.x * gridDim.y);
 }
 
 // The same for the B members of an ensemble (nb_ens handles) in one launch: blockIdx.z is the member, blockIdx.x / .y its
@@ -698,7 +700,35 @@ ens_r2max_tables_kernel(const float *__restrict__ pos, ForceGeom g, const EnsSca
     GridTables *tab = tabs + b;
     const float G = prm[b].G, eps2 = prm[b].eps2;
     r2max_block<D, 1, NB_R2MAX_SPLIT>(pos + (size_t)b * g.n * D, g, eps2, tab);
-    r2max_last_builds_tables<true>(tab, levels + b, G, eps2, min_val, allow_fast);
+    r2max_last_builds_tables<true>(tab, levels + b, G, eps2, min_val, allow_fast, gridDim.x * gridDim.y);
+}
+
+// The same for members of different sizes (nb_ens_create_ragged_grid; every member at most NB_LUT_MIN levels).  The launch
+// grid and the source chunks are cut for the capacity g.n; member b owns the first sizes[b] rows of its slice, so its
+// targets and its sources end at sizes[b].  A workgroup whose target block or source chunk starts at or beyond sizes[b]
+// has no pair of the member: it returns before it touches the member's maximum or arrival counter.  The others are
+// ceil(sizes[b] / targets per workgroup) * ceil(sizes[b] / chunk_len) -- the member's OWN arrival count, which the last of
+// them is recognised by; no workgroup waits for another.  The maximum is exact, so maximum and tables are those of the
+// member's solo run, and no padding row is read (r2max_block clamps targets and sources to the member's last star).
+template <int D, bool STOPS>
+__global__ void __launch_bounds__(NB_BLOCK)
+ens_r2max_tables_ragged_kernel(const float *__restrict__ pos, ForceGeom g, const EnsScalars<float> *__restrict__ prm,
+                               GridTables *__restrict__ tabs, const int *__restrict__ levels, float min_val, int allow_fast,
+                               const int *__restrict__ stop, int t, const int *__restrict__ sizes)
+{
+    constexpr int PER_BLOCK = NB_BLOCK / NB_R2MAX_SPLIT;     // targets per workgroup (r2max_block)
+    const int b = blockIdx.z;
+    if (ens_ticks_left<STOPS>(stop, b, t) <= 0) return;
+    const int n = sizes[b];
+    if ((int)blockIdx.x * PER_BLOCK >= n || (int)blockIdx.y * g.chunk_len >= n) return;
+    GridTables *tab = tabs + b;
+    const float G = prm[b].G, eps2 = prm[b].eps2;
+    const float *mine = pos + (size_t)b * g.n * D;           // (g.n: still the capacity, the stride of a slice)
+    const unsigned int arrivals = (unsigned int)((n + PER_BLOCK - 1) / PER_BLOCK) * (unsigned int)((n + g.chunk_len - 1) / g.chunk_len);
+    g.n = n;
+    g.j_end = n;                                             // (j_begin = 0)
+    r2max_block<D, 1, NB_R2MAX_SPLIT>(mine, g, eps2, tab);
+    r2max_last_builds_tables(tab, levels + b, G, eps2, min_val, allow_fast, arrivals);
 }
 
 // The tables of the members above NB_LUT_MIN levels, behind ens_r2max_tables_kernel: blockIdx.y is the member, blockIdx.x
@@ -962,7 +992,8 @@ hipError_t nb_launch_r2max_tables(const float *pos, const ForceGeom &g, int dim,
 }
 
 hipError_t nb_launch_ens_r2max_tables(const float *pos, int members, int n, int dim, const void *prm, GridTables *tabs,
-                                      const int *levels, float min_val, int allow_fast, const int *stop, int t, hipStream_t st)
+                                      const int *levels, float min_val, int allow_fast, const int *stop, int t, hipStream_t st,
+                                      const int *sizes)
 {
     if (members < 1 || members > NB_ENS_MAX_MEMBERS || n < 1 || !tabs || !levels || !prm || t < 0) return hipErrorInvalidValue;
     ForceGeom g{};
@@ -970,6 +1001,11 @@ hipError_t nb_launch_ens_r2max_tables(const float *pos, int members, int n, int 
     const dim3 grid = r2max_tables_grid(g, members, (n + NB_TJ - 1) / NB_TJ);
     return nb::pick<2, 3>(dim, [&](auto D) {
         return nb::pick_bool(stop != nullptr, [&](auto ST) {
+            if (sizes) {        // the geometry is the capacity's; every member cuts its own part out of it
+                hipLaunchKernelGGL((ens_r2max_tables_ragged_kernel<D.value, ST.value>), grid, dim3(NB_BLOCK), 0, st, pos, g,
+                                   (const EnsScalars<float> *)prm, tabs, levels, min_val, allow_fast, stop, t, sizes);
+                return hipGetLastError();
+            }
             hipLaunchKernelGGL((ens_r2max_tables_kernel<D.value, ST.value>), grid, dim3(NB_BLOCK), 0, st, pos, g,
                                (const EnsScalars<float> *)prm, tabs, levels, min_val, allow_fast, stop, t);
             return hipGetLastError();

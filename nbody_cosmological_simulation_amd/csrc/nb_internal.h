@@ -380,6 +380,18 @@ struct EnsWork {
 };
 constexpr int NB_ENS_RAGGED_BLOCK = 512;
 hipError_t nb_launch_ens_step_ragged(const EnsStepArgs &a, int do_kick, const int *stop, int t, hipStream_t st);
+// The grid modes of such a handle (nb_ens_create_ragged_grid; levels up to NB_LUT_MIN), the same three launches per
+// evaluation as below with every member's own size: nb_launch_ens_r2max_tables with `sizes`, then
+//   nb_launch_ens_grid_step_ragged    small_grid_body over the work list with tabs[b]; part (INT8 / INT4, else null):
+//                                     members * nb_ens_ragged_blocks(n, lanes) * 2 doubles, a row per member of which it
+//                                     fills the first ceil(sizes[b] / (NB_ENS_RAGGED_BLOCK / lanes)) pairs
+//   nb_launch_ens_grid_bins_ragged    its BINS instantiation (the bin read-out): forces to the scratch `acc`, no kicks;
+//                                     bin_out: members * (2 n + 2) words, zeroed by the caller; member b's block holds
+//                                     {s1[sizes[b]], s2[sizes[b]], {table-free pairs, table pairs}} packed for its OWN size
+// and nb_launch_ens_force_quant_finish with `sizes` (INT8 / INT4).
+inline int nb_ens_ragged_blocks(int n, int lanes) { const int tg = NB_ENS_RAGGED_BLOCK / lanes; return (n + tg - 1) / tg; }
+hipError_t nb_launch_ens_grid_step_ragged(const EnsStepArgs &a, int do_kick, const int *stop, int t, hipStream_t st);
+hipError_t nb_launch_ens_grid_bins_ragged(const EnsStepArgs &a, float *acc, unsigned long long *bin_out, hipStream_t st);
 // opening kick + drift of every member with its own dt (two roundings per line, like nb_launch_kick_drift)
 hipError_t nb_launch_ens_kick_drift(void *pos, void *vel, const void *acc, int members, int n, int dim, int is_f64,
                                     const void *prm, const int *stop, int t, hipStream_t st, const int *sizes = nullptr);
@@ -393,8 +405,11 @@ hipError_t nb_launch_ens_kick_drift(void *pos, void *vel, const void *acc, int m
 //   nb_launch_ens_force_quant_finish  INT8 / INT4: folds a member's partials into bounds[2 b] = {min, max}, snaps its
 //                                     count = n * dim forces to `levels` values and applies the kicks in place; `levels` is
 //                                     ONE value for all members (256 or 16: the force grid is the mode's, not CUSTOM's)
+// sizes (members of different sizes, levels up to NB_LUT_MIN; else null): member b's maximum is taken over its first sizes[b]
+// rows of a slice of n, by the workgroups whose targets and sources lie below sizes[b]; the others return at once
 hipError_t nb_launch_ens_r2max_tables(const float *pos, int members, int n, int dim, const void *prm, GridTables *tabs,
-                                      const int *levels, float min_val, int allow_fast, const int *stop, int t, hipStream_t st);
+                                      const int *levels, float min_val, int allow_fast, const int *stop, int t, hipStream_t st,
+                                      const int *sizes = nullptr);
 hipError_t nb_launch_ens_grid_step(const EnsStepArgs &a, int do_kick, const int *stop, int t, hipStream_t st);
 // CUSTOM members of up to NB_MAX_LUT levels (nb_ens_create_grid_wide), when a member exceeds NB_LUT_MIN:
 //   nb_launch_ens_r2max_tables        as above (levels in [2, NB_MAX_LUT]): a member above NB_LUT_MIN levels only gets its maximum
@@ -410,9 +425,12 @@ hipError_t nb_launch_ens_tables_wide(int members, int max_levels, const void *pr
 hipError_t nb_launch_ens_grid_step_wide(const EnsStepArgs &a, int do_kick, const int *stop, int t, hipStream_t st);
 hipError_t nb_launch_ens_grid_bins(const float *pos, float *acc, const float *mass, int members, int n, int dim, const void *prm,
                                    int lanes, const GridTables *tabs, int max_levels, unsigned long long *bin_out, hipStream_t st);
+// sizes (members of different sizes; else null), with dim and tg = the targets per workgroup of the force launch: count
+// and nblocks are then the strides of a member's slice and of its row of partials, of which it owns the first
+// sizes[b] * dim elements and ceil(sizes[b] / tg) pairs
 hipError_t nb_launch_ens_force_quant_finish(float *acc, int members, int count, int levels, const double *partials, int nblocks,
                                             double *bounds, float *vel, float *pos, const void *prm, int kick, const int *stop,
-                                            int t, hipStream_t st);
+                                            int t, hipStream_t st, const int *sizes = nullptr, int dim = 1, int tg = 1);
 // ---- explosion watch of an ensemble (nb_ens_watch.hip) ------------------------------------------------------------------
 // ONE launch on `st`, one workgroup per member, behind the energy launches of sampled tick `t` (sample `sample` of the
 // history kinetic / potential, index sample * members + b).  A member that is still running (stop[b] >= t, reason[b] == 0)

@@ -306,21 +306,29 @@ force_quant_finish_kernel(float *__restrict__ acc, int64_t count, int levels, co
 // ITS member's nblocks partials (partials: members * nblocks pairs), block 0 of a member leaves {min, max} in
 // bounds[2 b], and the member's count = n * D forces are snapped and kicked with the member's own dt.
 // Per-member stops (nb_device.h): a stopped member keeps its forces, bounds and state; one on its last tick only closes.
-template <bool STOPS>
+// RAGGED (sizes, dim, tg: nb_device.h, as ens_kick_drift_kernel has it): count and nblocks are the STRIDES of a member's
+// slice and of its row of partials; it owns the first sizes[m] * dim elements and the first ceil(sizes[m] / tg) pairs (tg:
+// the targets per workgroup of the force launch that wrote them).  Min and max do not depend on how the partials were
+// cut, so the bounds and the snapped forces are those of the member's solo run; nothing behind a member's own is touched.
+template <bool STOPS, bool RAGGED>
 __global__ void __launch_bounds__(256)
 ens_force_quant_finish_kernel(float *__restrict__ acc, int count, int levels, const double *__restrict__ partials, int nblocks,
                               double *__restrict__ bounds, float *__restrict__ vel, float *__restrict__ pos,
-                              const EnsScalars<float> *__restrict__ prm, int kick, const int *__restrict__ stop, int t)
+                              const EnsScalars<float> *__restrict__ prm, int kick, const int *__restrict__ stop, int t,
+                              const int *__restrict__ sizes, int dim, int tg)
 {
     const int m = blockIdx.y;
     const int left = ens_ticks_left<STOPS>(stop, m, t);
     if (left <= 0) return;
     kick = ens_kick_mode(left, kick);
+    const int mine = ens_member_count<RAGGED>(sizes, m, dim, count);
+    if (RAGGED && (int)blockIdx.x * 256 >= mine) return;       // (never block 0, which leaves the bounds: mine >= dim)
+    const int pairs = RAGGED ? (mine / dim + tg - 1) / tg : nblocks;
     // one pair per workgroup of the member's force launch
-    const ForceGrid g = force_grid_from_partials(partials + (size_t)m * 2 * nblocks, nblocks, levels, bounds + 2 * m);
+    const ForceGrid g = force_grid_from_partials(partials + (size_t)m * 2 * nblocks, pairs, levels, bounds + 2 * m);
     const float half_dt = prm[m].half_dt, dt = prm[m].dt;
     const size_t o = (size_t)m * count;
-    for (int k = blockIdx.x * 256 + threadIdx.x; k < count; k += gridDim.x * 256) {
+    for (int k = blockIdx.x * 256 + threadIdx.x; k < mine; k += gridDim.x * 256) {
         const size_t idx = o + k;
         float a = acc[idx];
         if (!g.passthrough) a = lin_quant<float>(a, g.mn, g.range, g.lm1, nullptr);
@@ -666,16 +674,20 @@ hipError_t nb_launch_force_quant_finish(float *acc, int64_t count, int levels, c
 
 hipError_t nb_launch_ens_force_quant_finish(float *acc, int members, int count, int levels, const double *partials, int nblocks,
                                             double *bounds, float *vel, float *pos, const void *prm, int kick, const int *stop, int t,
-                                            hipStream_t st)
+                                            hipStream_t st, const int *sizes, int dim, int tg)
 {
     if (members < 1 || members > NB_ENS_MAX_MEMBERS || count < 1 || nblocks < 1 || levels < 2 || t < 0) return hipErrorInvalidValue;
     if (kick != NB_KICK_NONE && kick != NB_KICK_CLOSE && kick != NB_KICK_CLOSE_OPEN) return hipErrorInvalidValue;
+    if (sizes && (dim < 1 || tg < 1 || count % dim != 0)) return hipErrorInvalidValue;
     int gx = (count + 255) / 256;
     gx = gx > 2048 ? 2048 : gx;
     return nb::pick_bool(stop != nullptr, [&](auto ST) {
-        hipLaunchKernelGGL(ens_force_quant_finish_kernel<ST.value>, dim3(gx, members), dim3(256), 0, st, acc, count, levels, partials,
-                           nblocks, bounds, vel, pos, (const EnsScalars<float> *)prm, kick, stop, t);
-        return hipGetLastError();
+        return nb::pick_bool(sizes != nullptr, [&](auto RG) {
+            hipLaunchKernelGGL((ens_force_quant_finish_kernel<ST.value, RG.value>), dim3(gx, members), dim3(256), 0, st, acc, count,
+                               levels, partials, nblocks, bounds, vel, pos, (const EnsScalars<float> *)prm, kick, stop, t, sizes,
+                               dim, tg);
+            return hipGetLastError();
+        });
     });
 }
 

@@ -4,7 +4,7 @@
 // HOOK_AT_RUN_TIME (fp32): one of the three cast hooks as a workgroup-uniform argument (ens_step_mixed_kernel);
 // small_grid_body: the grid hook (fp32, tables, bin read-out).  Included by nb_small.hip (small_step_kernel: one system
 // per launch, target block = blockIdx.x), nb_ensemble.hip (ens_step_kernel / ens_grid_step_kernel: many systems per
-// launch), nb_ens_ragged.hip (ens_step_ragged_kernel: systems of different sizes per launch, target block from a work list)
+// launch), nb_ens_ragged.hip (ens_step_ragged_kernel / ens_grid_step_ragged_kernel: systems of different sizes per launch, target block from a work list)
 // and nb_ens_grid_wide.hip (ens_grid_step_wide_kernel, ens_grid_bins_kernel): the SAME code, so a member of an ensemble rounds every sum exactly as the solo step does.
 #pragma once
 #include "nb_device.h"

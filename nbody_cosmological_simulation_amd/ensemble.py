@@ -135,7 +135,21 @@ does not depend on the workgroup size, so the one size of the launch serves ever
 for bit; step, run, run_recorded, run_members, run_watched, divergence and run_diverged are inherited, the last two with
 baselines of the member's own size (ValueError otherwise).  `num_stars` is the list of sizes; the array attributes return
 lists of per-member tensors and `set_state` / `set_accelerations` take them.  `metrics`, `run_crash_watched` and
-`crash_measures` raise NotImplementedError: ragged metrics, the ragged crash watch and the ragged grid modes are follow-ups.
+`crash_measures` raise NotImplementedError: ragged metrics and the ragged crash watch are follow-ups.
+
+The grid half of those sweeps -- the scan's "int8" / "int4" points and the density test's "broken" runs are 256- and
+16-level grids on r^2 -- is `RaggedQuantizedEnsemble`'s: a `RaggedEnsemble` under INT8_SIM, INT4_SIM or CUSTOM with
+`custom_levels` per member (2 .. 256; `check_ragged_grid_arguments`), fp32 state, N_b up to 3072 (C-ABI
+nb_ens_create_ragged_grid).  A tick is QuantizedEnsemble's launches whatever the sizes: max r^2 + tables over all members
+(a workgroup beyond its member's size returns at once, and the last of the member's OWN workgroups builds its tables), ONE
+force launch over the work list ("ens_grid_step_ragged_kernel") and under INT8 / INT4 the force snap + kicks.  Contract:
+member b is bit-identical to `GalaxySimulation(..., precision_mode, custom_levels=levels[b])` of its own size, no
+tolerance -- positions, velocities and accelerations after every tick, the `quant_debug()` values (length-B arrays, as
+QuantizedEnsemble's) and the bins of `quant_bin_sums()` (`sum_k` / `sum_kw`: lists of per-member (N_b,) arrays) -- because
+a wave holds the same pairs at the ragged launch's 512 threads as at the 256 a solo run takes for N in 2049 .. 3072
+(DESIGN.md 4.9); no kernel reads or writes a padding row; a stopped member keeps the tables and force bounds of its last
+evaluation.  Everything RaggedEnsemble inherits works, and its three refusals stand; a member above 256 levels is refused
+(ValueError: the ragged wide grid is a follow-up, `FineGridEnsemble` serves members of one size).
 
 Not covered: more than 4096 levels (a solo `GalaxySimulation` serves them through its generic kernel), INT8 / INT4 beside
 CUSTOM members, FLOAT64 or grid-mode members beside cast-mode members, stopping members on a divergence
@@ -326,6 +340,15 @@ def check_ragged_arguments(positions, velocities, masses, precision_mode=Precisi
         raise ValueError(f"RaggedEnsemble runs the FLOAT64, FLOAT32, BFLOAT16 and FLOAT16 modes; {precision_mode.name} needs "
                          "per-member quantisation tables (the ragged grid modes are a follow-up; members of one size: "
                          "QuantizedEnsemble)")
+    positions, velocities, masses, sizes, G, softening, dt = _check_ragged_state(positions, velocities, masses, storage, G,
+                                                                                 softening, dt, modes)
+    return positions, velocities, masses, sizes, modes, G, softening, dt
+
+
+def _check_ragged_state(positions, velocities, masses, storage, G, softening, dt, modes=None, more_lists=()):
+    """check_ragged_arguments / check_ragged_grid_arguments behind their own mode rules: the three lists, every member's
+    tensors under the storage mode `storage`, the sizes and the parameters as length-B lists.  modes: a mode list, whose
+    length is checked once B is known; more_lists: (name, length) of further per-member lists, checked the same way."""
     lists = []
     for name, seq in (("positions", positions), ("velocities", velocities), ("masses", masses)):
         if isinstance(seq, torch.Tensor) or isinstance(seq, (str, bytes)) or not isinstance(seq, Sequence):
@@ -341,6 +364,9 @@ def check_ragged_arguments(positions, velocities, masses, precision_mode=Precisi
         raise ValueError(f"B must be in [1, {MAX_MEMBERS}], got {B}")
     if modes is not None:
         check_mode_list(modes, B)
+    for name, length in more_lists:
+        if length != B:
+            raise ValueError(f"{name} has {length} entries for {B} members")
     want = state_dtype(storage)
     sizes, dim = [], None
     for b in range(B):
@@ -366,7 +392,7 @@ def check_ragged_arguments(positions, velocities, masses, precision_mode=Precisi
             raise ValueError(f"member {b} has N = {n}, above the limit of {MAX_STARS[want]} for {want} state: a single system "
                              "of that size fills the chip (use GalaxySimulation)")
         sizes.append(n)
-    return (positions, velocities, masses, sizes, modes, _param_list("G", G, B), _param_list("softening", softening, B),
+    return (positions, velocities, masses, sizes, _param_list("G", G, B), _param_list("softening", softening, B),
             _param_list("dt", dt, B))
 
 
@@ -428,6 +454,41 @@ def check_fine_grid_arguments(positions, velocities, masses, custom_levels=None,
                 if v > MAX_FINE_LEVELS else "")
     return _grid_arguments(positions, velocities, masses, PrecisionMode.CUSTOM, _level_list(custom_levels), MAX_FINE_LEVELS,
                            tail, G, softening, dt)
+
+
+def check_ragged_grid_arguments(positions, velocities, masses, precision_mode=PrecisionMode.INT8_SIM, custom_levels=None,
+                                G=0.001, softening=0.1, dt=0.01):
+    """Validate RaggedQuantizedEnsemble's constructor arguments without touching a device: the lists of
+    check_ragged_arguments (fp32 state) under the mode and level rules of check_grid_arguments.  Returns (positions,
+    velocities, masses, sizes, levels, G, softening, dt): the three as lists, the B star counts, and the levels and the
+    parameters as length-B lists; raises TypeError / ValueError naming the member."""
+    if not isinstance(precision_mode, PrecisionMode):
+        raise TypeError(f"precision_mode must be a PrecisionMode, got {type(precision_mode).__name__}")
+    if precision_mode not in _GRID_MODES:
+        raise ValueError(f"RaggedQuantizedEnsemble runs the INT8_SIM, INT4_SIM and CUSTOM modes; {precision_mode.name} is "
+                         "RaggedEnsemble's")
+    levels = _level_list(custom_levels)
+    if precision_mode != PrecisionMode.CUSTOM and levels is not None:
+        fixed = 256 if precision_mode == PrecisionMode.INT8_SIM else 16
+        raise ValueError(f"custom_levels belongs to the CUSTOM mode: {precision_mode.name} has {fixed} levels (pass None)")
+    for v in (levels if isinstance(levels, list) else [levels] if levels is not None else []):
+        if not MIN_LEVELS <= v <= MAX_LEVELS:
+            tail = (f": above {MAX_LEVELS} levels with members of different sizes is a follow-up (members of one size: "
+                    "FineGridEnsemble)") if v > MAX_LEVELS else ""
+            raise ValueError(f"custom_levels must be in [{MIN_LEVELS}, {MAX_LEVELS}], got {v}{tail}")
+    positions, velocities, masses, sizes, G, softening, dt = _check_ragged_state(
+        positions, velocities, masses, precision_mode, G, softening, dt,
+        more_lists=[("custom_levels", len(levels))] if isinstance(levels, list) else ())
+    B = len(sizes)
+    if precision_mode == PrecisionMode.INT8_SIM:
+        levels = [256] * B
+    elif precision_mode == PrecisionMode.INT4_SIM:
+        levels = [16] * B
+    elif levels is None:
+        levels = [DEFAULT_CUSTOM_LEVELS] * B
+    elif not isinstance(levels, list):
+        levels = [levels] * B
+    return positions, velocities, masses, sizes, levels, G, softening, dt
 
 
 def check_record_arguments(num_ticks, every, members) -> list:
@@ -1271,3 +1332,43 @@ class RaggedEnsemble(GalaxyEnsemble):
         """Not implemented for members of different sizes."""
         raise NotImplementedError("RaggedEnsemble.crash_measures: the ragged crash watch is a follow-up (members of one size: "
                                   "GalaxyEnsemble)")
+
+
+class RaggedQuantizedEnsemble(RaggedEnsemble):
+    """A RaggedEnsemble under INT8_SIM, INT4_SIM or CUSTOM: members of their own star counts, every member with its own
+    quantisation tables and, under CUSTOM, its own number of grid levels (`custom_levels`: None = 64, an int, or one per
+    member; 2 .. 256).  `levels` holds the B level counts in force.  Everything else is RaggedEnsemble's, refusals
+    included (see the module docstring)."""
+
+    def __init__(self, positions, velocities, masses, precision_mode=PrecisionMode.INT8_SIM, custom_levels=None,
+                 G=0.001, softening=0.1, dt=0.01, device=None):
+        self._handle = C.c_void_p()
+        positions, velocities, masses, sizes, self.levels, self.G, self.softening, self.dt = check_ragged_grid_arguments(
+            positions, velocities, masses, precision_mode, custom_levels, G, softening, dt)
+        self._sizes, self._capacity = list(sizes), max(sizes)
+        self.num_members, self._dim = len(sizes), int(positions[0].shape[1])
+        self._dtype = positions[0].dtype
+        padded = [self._padded(name, t) for name, t in (("positions", positions), ("velocities", velocities), ("masses", masses))]
+        self._construct(*padded, precision_mode, device)              # (num_stars: the capacity, for the handle's shape)
+        self.num_stars = list(sizes)
+
+    def _create(self, cfg, params):
+        B = self.num_members
+        levels = (C.c_int32 * B)(*self.levels) if self.precision_mode == PrecisionMode.CUSTOM else None
+        N.check(N.lib().nb_ens_create_ragged_grid(C.byref(self._handle), C.byref(cfg), (C.c_int32 * B)(*self._sizes), levels,
+                                                  *params))
+
+    quant_debug = QuantizedEnsemble.quant_debug
+
+    def quant_bin_sums(self) -> dict:
+        """QuantizedEnsemble.quant_bin_sums() for members of different sizes: `sum_k` and `sum_kw` are lists of per-member
+        (N_b,) int64 numpy arrays, `pairs_table_free`, `pairs_table` and `levels` (B,) int64 arrays.  An observer."""
+        import numpy as np
+        B, cap = self.num_members, self._capacity
+        s1, s2, pairs = np.zeros((B, cap), np.int64), np.zeros((B, cap), np.int64), np.zeros((B, 2), np.int64)
+        N.check(N.lib().nb_ens_quant_bin_sums(self._handle, C.c_void_p(s1.ctypes.data), C.c_void_p(s2.ctypes.data),
+                                              C.c_void_p(pairs.ctypes.data)))
+        return dict(sum_k=[s1[b, :n].copy() for b, n in enumerate(self._sizes)],
+                    sum_kw=[s2[b, :n].copy() for b, n in enumerate(self._sizes)],
+                    pairs_table_free=pairs[:, 0].copy(), pairs_table=pairs[:, 1].copy(),
+                    levels=np.asarray(self.levels, np.int64))
